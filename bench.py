@@ -15,7 +15,13 @@ has its own 100 M k-mers of a 100 M x N batch.  A 1-GPU run also times the shard
 case (k-mers drawn from the text, >=1 hit each), `--workload mixed` configs[4] (8..30-mers; shards
 balanced by the sum of the lengths).
 
-The JSON line also carries
+A plain run sets up (index, k-mers, the probe step that sizes the buffers), warms up, times --steps steps, writes the last
+step's results if --dump-outputs is given, and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step
+and a `config` that describes the run.  --full adds everything else below -- the per-kernel events, the roofline tallies,
+the CPU baseline and the checks against the oracle and the committed digests, the other workloads and sizes of the same
+run -- as separate measurements after the timed steps.
+
+With --full the JSON line also carries
   roofline         -- the dominant kernel.  Seed-order path: COMPULSORY bytes of orderedSearchKernel (distinct
                       128-B lines per search level, tallied on the device by an instrumented launch, plus records
                       read and results stored) / that kernel's HIP-event time, against the 8 TB/s HBM peak; the
@@ -115,8 +121,19 @@ def parse():
     p.add_argument("--dump-dir", default=None,
                    help="testing: every rank writes its shard's counts / hit offsets / positions to <dir>/rank<r>.npz")
     p.add_argument("--record-digests", default=None,
-                   help="append this run's per-shard digests to the JSON file (how tests/golden/bench_digests.json is made)")
-    return p.parse_args()
+                   help="append this run's per-shard digests to the JSON file (how tests/golden/bench_digests.json is made; needs --full)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the timed steps: per-kernel events, rooflines, CPU baseline, oracle and digest checks, the secondary "
+                        "workloads and the scaling proxy (the --no-* options above switch parts of it off)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, a fixed seeded sample "
+                        "of the batch; see dump_outputs)")
+    args = p.parse_args()
+    if args.record_digests and not args.full:
+        p.error("--record-digests needs --full (the digests are computed there)")
+    if args.dump_outputs and args.sharding == "seed_bucket":
+        p.error("--dump-outputs: the contiguous sharding's results only")
+    return args
 
 
 def launch_ranks(args):
@@ -863,9 +880,84 @@ def gpu_state(card=0):
     return out or None
 
 
+def gpu_clocks(card=0):
+    """the clocks this box runs at (boxes of the pool differ by several per cent on the same code: the line says which one it
+    was).  Read from sysfs -- no child process: a process that has initialised the GPU must not start one."""
+    clocks = None
+    try:
+        import glob
+        cards = sorted(glob.glob("/sys/class/drm/card[0-9]*/device/pp_dpm_sclk"))
+        if cards:
+            base = os.path.dirname(cards[min(card, len(cards) - 1)])
+            clocks = {}
+            for name in ("sclk", "mclk", "fclk"):
+                path = os.path.join(base, f"pp_dpm_{name}")
+                if os.path.exists(path):
+                    levels = open(path).read().split("\n")
+                    current = [ln for ln in levels if ln.strip().endswith("*")]
+                    clocks[name] = (current[0].split(":")[1].replace("*", "").strip() if current else None)
+                    clocks[name + "_max"] = levels[-2].split(":")[1].replace("*", "").strip() if len(levels) > 1 and ":" in levels[-2] else None
+    except Exception:  # noqa: BLE001  (reporting only)
+        clocks = None
+    return clocks
+
+
 def profile_file(kind, name):
     path = os.path.join(ROOT, "profiles", PROFILE_ROUND, f"{kind}_{name}.json")
     return (json.load(open(path)), f"profiles/{PROFILE_ROUND}/{kind}_{name}.json") if os.path.exists(path) else (None, None)
+
+
+DUMP_SAMPLE = 1 << 18  # k-mers of the seeded sample
+DUMP_HIT_KMERS = 1 << 18  # k-mers with hits, the first ones in k-mer order
+DUMP_POSITIONS = 1 << 21  # positions per group (the first k-mers whose whole lists fit)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, torch, np, first, q, counts, ranges=None, hit_off=None, positions=None):
+    """--dump-outputs: the results of the last timed step in their dense form -- `counts` (q, int32 storage of the uint32
+    counts), and when the batch was located `ranges` (2 q: sp, ep per k-mer, {1, 0} where there is no hit), `hit_off`
+    (q + 1) and `positions` (in k-mer order; None when only a window of them is resident) -- written as float64 .npy files
+    (every value is an integer below 2^53: exact).  Two groups of k-mers, whatever form the step used:
+      sample_<name>     a seeded sample of DUMP_SAMPLE k-mer numbers, the same for the same arguments: kmers (global numbers),
+                        counts, ranges, hit_offsets (into positions), positions (the first sampled k-mers whose lists fit
+                        DUMP_POSITIONS);
+      found_<name>      the first DUMP_HIT_KMERS k-mers with at least one hit, in k-mer order, with the same arrays;
+    and totals = [k-mers, k-mers with hits, hits].  At most 52 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    dev = counts.device
+    cnt = counts[:q].to(torch.int64) & 0xFFFFFFFF
+    if hit_off is not None:
+        cnt = hit_off[1:q + 1] - hit_off[:q]  # (counts of located k-mers are the lengths of their lists)
+    located = ranges is not None and hit_off is not None
+
+    def save(name, t):
+        a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+    def group(prefix, idx):
+        c = cnt[idx]
+        save(prefix + "kmers", idx + first)
+        save(prefix + "counts", c)
+        if not located:
+            return
+        r = ranges[: 2 * q].view(q, 2)[idx].clone()
+        r[c == 0] = torch.tensor([1, 0], dtype=r.dtype, device=dev)
+        save(prefix + "ranges", r)
+        off = torch.zeros(idx.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(c, 0, out=off[1:])
+        save(prefix + "hit_offsets", off)
+        if positions is None:
+            return
+        keep = int(torch.searchsorted(off[1:], torch.tensor([DUMP_POSITIONS], device=dev), right=True).item())
+        total = int(off[keep].item())
+        at = torch.repeat_interleave(hit_off[idx[:keep]] - off[:keep], c[:keep], output_size=total)
+        save(prefix + "positions", positions[at + torch.arange(total, dtype=torch.int64, device=dev)])
+
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(q, min(q, DUMP_SAMPLE), replace=False))
+    group("sample_", torch.from_numpy(sample.astype(np.int64)).to(dev))
+    with_hits = torch.nonzero(cnt).flatten()
+    group("found_", with_hits[:DUMP_HIT_KMERS])
+    save("totals", [q, with_hits.numel(), int(cnt.sum().item())])
 
 
 def seed_bucket_run(args, L, api, digest, shard, torch, np, dev, g, ix, d_chars, Q, first, batch_total, K, n, rank, world, build_s):
@@ -966,42 +1058,47 @@ def seed_bucket_run(args, L, api, digest, shard, torch, np, dev, g, ix, d_chars,
     state = run(args.steps)
     barrier()
     dt = shard.max_over_ranks((time.perf_counter() - t0) / args.steps, world, dev)
-    # digests keyed by the k-mers' numbers in the whole batch: my share of the order + my own general k-mers
-    m, left = state["m"], state["left"]
-    dc = dp = 0
-    hits = 0
-    if m:
-        ids = state["k"][:m].to(torch.int64)
-        lens = state["o"][1:m + 1] - state["o"][:m]
-        hits = int(state["o"][m].item())
-        dc += digest.counts_digest_keyed(ids, lens)
-        dp += digest.positions_digest_keyed(ids, state["o"][: m + 1], state["p"][: max(hits, 1)])
-    if left < Q:  # (located here too: ranges -> offsets -> positions over the tail)
-        gm = Q - left
-        gr = state["gr"][2 * left:].contiguous()
-        go = torch.zeros(gm + 1, dtype=torch.int64, device=dev)
-        gsc = torch.empty(api.GpuIndex.scan_scratch_bytes(gm), dtype=torch.uint8, device=dev)
-        total = g.hit_offsets(gr.data_ptr(), gm, go.data_ptr(), gsc.data_ptr())
-        gp = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
-        g.locate(gr.data_ptr(), go.data_ptr(), gm, total, gp.data_ptr())
-        torch.cuda.synchronize()
-        gids = state["gk"][left:].to(torch.int64)
-        dc += digest.counts_digest_keyed(gids, go[1:] - go[:-1])
-        dp += digest.positions_digest_keyed(gids, go, gp)
-        hits += total
-    parts = shard.gather_objects((rank, m + (Q - left), hits, dc & digest.MASK, dp & digest.MASK), world)
+    digests = None
+    if args.full:
+        # digests keyed by the k-mers' numbers in the whole batch: my share of the order + my own general k-mers
+        m, left = state["m"], state["left"]
+        dc = dp = 0
+        hits = 0
+        if m:
+            ids = state["k"][:m].to(torch.int64)
+            lens = state["o"][1:m + 1] - state["o"][:m]
+            hits = int(state["o"][m].item())
+            dc += digest.counts_digest_keyed(ids, lens)
+            dp += digest.positions_digest_keyed(ids, state["o"][: m + 1], state["p"][: max(hits, 1)])
+        if left < Q:  # (located here too: ranges -> offsets -> positions over the tail)
+            gm = Q - left
+            gr = state["gr"][2 * left:].contiguous()
+            go = torch.zeros(gm + 1, dtype=torch.int64, device=dev)
+            gsc = torch.empty(api.GpuIndex.scan_scratch_bytes(gm), dtype=torch.uint8, device=dev)
+            total = g.hit_offsets(gr.data_ptr(), gm, go.data_ptr(), gsc.data_ptr())
+            gp = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+            g.locate(gr.data_ptr(), go.data_ptr(), gm, total, gp.data_ptr())
+            torch.cuda.synchronize()
+            gids = state["gk"][left:].to(torch.int64)
+            dc += digest.counts_digest_keyed(gids, go[1:] - go[:-1])
+            dp += digest.positions_digest_keyed(gids, go, gp)
+            hits += total
+        parts = shard.gather_objects((rank, m + (Q - left), hits, dc & digest.MASK, dp & digest.MASK), world)
+        if rank == 0:
+            total_c = sum(p[3] for p in parts) & digest.MASK
+            total_p = sum(p[4] for p in parts) & digest.MASK
+            assert sum(p[1] for p in parts) == batch_total, "the ranks' shares of the order do not add up to the batch"
+            key = digest.key(args.alphabet, args.workload, args.mode, n, str(K), args.seed_k, args.sa_ratio, args.query_offset, batch_total)
+            dig = {"counts": f"{total_c:016x}", "positions": f"{total_p:016x}"}
+            committed = digest.load_golden().get(key)
+            assert committed is None or committed == dig, f"seed-bucket sharding: digests {dig} differ from the committed {committed}"
+            if args.record_digests:
+                known = json.load(open(args.record_digests)) if os.path.exists(args.record_digests) else {}
+                known[key] = dig
+                json.dump(known, open(args.record_digests, "w"), indent=1, sort_keys=True)
+            digests = dict(dig, status="match" if committed else "unknown", shards=world,
+                           per_rank=[{"rank": p[0], "kmers": p[1], "hits": p[2]} for p in parts])
     if rank == 0:
-        total_c = sum(p[3] for p in parts) & digest.MASK
-        total_p = sum(p[4] for p in parts) & digest.MASK
-        assert sum(p[1] for p in parts) == batch_total, "the ranks' shares of the order do not add up to the batch"
-        key = digest.key(args.alphabet, args.workload, args.mode, n, str(K), args.seed_k, args.sa_ratio, args.query_offset, batch_total)
-        dig = {"counts": f"{total_c:016x}", "positions": f"{total_p:016x}"}
-        committed = digest.load_golden().get(key)
-        assert committed is None or committed == dig, f"seed-bucket sharding: digests {dig} differ from the committed {committed}"
-        if args.record_digests:
-            known = json.load(open(args.record_digests)) if os.path.exists(args.record_digests) else {}
-            known[key] = dig
-            json.dump(known, open(args.record_digests, "w"), indent=1, sort_keys=True)
         out = {"metric": "Mkmers/sec located, GRCh38 nucleotide index", "value": round(batch_total / dt / 1e6, 2), "unit": "Mkmers/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "strong",
                "vs_baseline": None, "dtype": "u64", "data": "synthetic",
@@ -1013,8 +1110,7 @@ def seed_bucket_run(args, L, api, digest, shard, torch, np, dev, g, ix, d_chars,
                           "batch_kmers": batch_total, "buckets": buckets, "index_build_s": round(build_s, 2), "timing_collective": shard.timing_backend() or "none (one rank)",
                           "batches_in_flight": 2 if pipelined else 1, "host_waits_per_step": 1},
                "roofline": None, "cpu_baseline": None,
-               "digests": dict(dig, status="match" if committed else "unknown", shards=world,
-                               per_rank=[{"rank": p[0], "kmers": p[1], "hits": p[2]} for p in parts])}
+               "digests": digests}
         print(json.dumps(out), flush=True)
     if world > 1:
         barrier()
@@ -1143,7 +1239,7 @@ def main():
     # the default run also reports the dense-hit case (every k-mer located, ~7 LF steps per hit) beside the headline:
     # its k-mers are drawn from the text now, searched after everything else
     d_planted = None
-    if (args.workload == "random" and not amino and world == 1 and not args.no_secondary and args.mode == "locate"
+    if (args.full and args.workload == "random" and not amino and world == 1 and not args.no_secondary and args.mode == "locate"
             and args.text == "uniform"):
         d_planted = torch.empty(Q * K, dtype=torch.uint8, device=dev)
         assert L.awfmGpuSynthPlantedQueries(d_planted.data_ptr(), first, Q, K, 103, d_text.data_ptr(), n, None) == 1
@@ -1170,7 +1266,7 @@ def main():
     stream = torch.cuda.current_stream().cuda_stream
     narrow_counts = ix.bwt_length < (1 << 32)  # 32-bit counts are exact: hit offsets can be scanned from them
     ordered = g.search_hits_is_ordered(d_offsets is not None, K, Q)
-    if ordered:
+    if ordered and args.full:
         os.environ["AWFM_GPU_TIME_ORDERED"] = "1"  # HIP events around the dominant kernel inside the library, logged per search
     locate = args.mode == "locate"
     dense_only = bool(os.environ.get("AWFM_BENCH_DENSE_RESULTS"))
@@ -1487,12 +1583,13 @@ def main():
     if args.streams > 1 and not whole.windowed:
         lanes.extend(Lane(False) for _ in range(args.streams - 1))
         ensure_positions(whole.hits)
-    # the warm-up steps carry the events that split a step into its search call and its locate kernels (reporting); the timed
-    # steps carry none: a recorded event is a packet of its own in the queue, about 5 us of idle device each
+    # (--full) the warm-up steps carry the events that split a step into its search call and its locate kernels (reporting); the
+    # timed steps carry none: a recorded event is a packet of its own in the queue, about 5 us of idle device each
     for _ in range(max(args.warmup, 1)):
-        step(whole, True)
+        step(whole, args.full)
     torch.cuda.synchronize()
-    g.ordered_kernel_log()  # the log of the library's own kernel brackets starts with the timed steps
+    if args.full:
+        g.ordered_kernel_log()  # the log of the library's own kernel brackets starts with the timed steps
     barrier()
     t_start = time.perf_counter()
     run_steps(whole, args.steps)
@@ -1502,6 +1599,99 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     value = batch_total / (elapsed / args.steps) / 1e6  # Mkmers/s over all ranks
     check_against_probe(whole, args.steps)
+    kdesc = f"{args.mixed_lengths[0]}..{args.mixed_lengths[1]}-mers" if args.workload == "mixed" else f"{K}-mers"
+    metric = "Mkmers/sec located, GRCh38 nucleotide index" if not amino else "Mkmers/sec located, amino index"
+    form_names = {"order": "every k-mer {k-mer number, range} in search order + hit offsets and positions in that order",
+                  "list": "list of the k-mers with hits {k-mer number, range} in k-mer order + hit offsets over the list + positions",
+                  "dense": "range / count under every k-mer number + hit offsets over the batch + positions"}
+
+    def run_config(deep_build, image_bytes, image_deep_k, image_described, length_tables_built):
+        """what the line says of the run, plain or --full"""
+        per = "per GPU" if args.scaling == "weak" else f"in total, sharded over {world} rank(s)"
+        deep_build_s, deep_transient = deep_build
+        config = {"workload": f"{args.queries / 1e6:g} M {args.workload} {kdesc} {per}, {args.mode}, "
+                              f"{n / 1e9:g} G{'res' if amino else 'bp'} {args.text} synthetic {args.alphabet} text"
+                              f"{' (GRCh38-sized)' if n >= 3_000_000_000 and not amino else ''}, "
+                              f"SA ratio {args.sa_ratio}, seed table k={args.seed_k}",
+                  "parallelism": f"index replica per GPU, query batch sharded over {world} rank(s), no collective",
+                  "batch_kmers": batch_total, "rank0_kmers": Q,
+                  "timing_collective": shard.timing_backend() or "none (one rank)",
+                  "hits_per_step_rank0": int(whole.hits), "host_waits_per_step": 0 if not whole.windowed else "one per window",
+                  # consecutive steps alternate between this many streams, each with its own result buffers and scratch slot
+                  "streams": 1 if whole.windowed else len(lanes),
+                  "index_build_s": round(build_s, 2),
+                  "device_image_bytes": image_bytes, "device_seed_k": image_deep_k, "device_image": image_described,
+                  # the deeper table's construction, whoever started it (the library by itself at awfmGpuIndexAcquire, inside
+                  # index_build_s; or --device-seed-k): wall seconds and the device memory held beyond the table at the peak.  In
+                  # this process it follows the GPU index builder; 0.55 s in most runs, 4-6 s in some -- one hipMalloc, the first the
+                  # runtime cannot serve from blocks it holds (memory to hand back or to scrub after the process before); in a process
+                  # that reads its index from a file the construction takes 0.6 s (scripts/first_call_probe.py; device_seed_rebuild_s
+                  # of --full)
+                  "device_seed_build_s": round(deep_build_s, 2), "device_seed_transient_bytes": int(deep_transient),
+                  # of which inside the hipMalloc calls (the table's 34 GB): the seconds some runs show are the allocation, not the kernels
+                  "device_seed_alloc_s": round(deep_first_alloc_s, 2),
+                  "device_dense_sa": dense_sa_default, "device_dense_sa_build_s": round(dense_s, 2),
+                  "search_path": ({"order": "awfmGpuSearchHitsInOrder", "list": "awfmGpuSearchHitsCompact",
+                                   "dense": "awfmGpuSearchHitsSparse" if narrow_counts else "awfmGpuSearchHits"}[whole.form] if locate
+                                  else "awfmGpuSearchHits") + (", seed order" if ordered else ", mixedLookupSearchKernel" if small_mixed_lookup else ", general kernel"),
+                  "result_format": form_names[whole.form] if locate else "count under every k-mer number",
+                  "result_format_probe_ms": getattr(whole, "form_probe_ms", None),  # mixed-length dense-hit batches: one search call of each form, timed by the probe
+                  "lookup_front": {0: "both front ends launched, the sample decides on the device", 1: "lookup kernel only (predicted from an earlier step's sample)",
+                                   2: "ordered kernels only (predicted from an earlier step's sample)"}.get(lookup_front, "no sample"),
+                  "list_tail": "awfmGpuListLocateOnDevice (one launch)" if locate and whole.form == "list" and list_tail else None}
+        lt_bytes, lt_s = length_tables_built
+        if lt_bytes:  # built by the probe step of a mixed-length batch (awfm_mixed_lookup_kernel.h): device-only, kept with the image
+            config["length_tables_bytes"] = lt_bytes
+            config["length_tables_build_s"] = round(lt_s, 3)
+        clocks = gpu_clocks(max(args.force_device, 0) if world == 1 else local_rank)
+        if clocks:
+            config["gpu_clocks"] = clocks
+            for name in ("sclk", "mclk", "fclk"):
+                if name in clocks:
+                    config[f"gpu_{name}"] = str(clocks[name])
+        return config
+
+    def dump_shard(positions):
+        """--dump-dir (testing): this rank's shard results in the dense form, for a check against the oracle outside the bench"""
+        os.makedirs(args.dump_dir, exist_ok=True)
+        dump = {"first": np.uint64(first), "queries": np.uint64(Q)}
+        if args.mode == "count":
+            dump["counts"] = d_counts.cpu().numpy().view(np.uint32)
+        else:
+            dump["ranges"] = d_ranges.cpu().numpy().view(np.uint64).reshape(Q, 2)
+            dump["hit_offsets"] = d_hit_off.cpu().numpy().view(np.uint64)
+            if not whole.windowed:
+                dump["positions"] = positions[: whole.hits].cpu().numpy().view(np.uint64)
+        np.savez(os.path.join(args.dump_dir, f"rank{rank}.npz"), **dump)
+
+    # which front end(s) the last timed step launched: 0 both (the sample's verdict stays on the device), 1 the lookup kernel
+    # only / 2 the ordered kernels only (the verdict of an earlier step had reached the host: awfmGpuLastLookupFront), -1: no sample
+    lookup_front = g.last_lookup_front()
+    # (a mixed-length batch below the seed-order size on an image with its tables per k-mer length: the lookup kernel alone)
+    small_mixed_lookup = bool(d_offsets is not None and not ordered and not amino and g.length_tables[0] and g.last_ordered_kernel_is_lookup())
+
+    if not args.full:
+        # ---- a plain run: the last step's results when asked for, and the line ----
+        if args.dump_dir or args.dump_outputs:
+            positions = to_dense(whole)
+            if args.dump_dir:
+                dump_shard(positions)
+            if args.dump_outputs and rank == 0:
+                dump_outputs(args.dump_outputs, torch, np, first, Q, d_counts, d_ranges if locate else None,
+                             d_hit_off if locate else None, positions if locate and not whole.windowed else None)
+        if rank == 0:
+            config = run_config(g.deep_seed_build if args.device_seed_k >= 0 else deep_first_build, g.device_bytes,
+                                g.deep_seed_k or args.seed_k, g.describe(), g.length_tables)
+            config["bench_wall_s"] = round(time.time() - T_START, 1)  # this process from its first line to its JSON line
+            out = {"metric": metric, "value": round(value, 2), "unit": "Mkmers/s", "n_gpus": world, "steps": args.steps,
+                   "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": args.scaling,
+                   "vs_baseline": None, "dtype": "u64", "data": "synthetic", "config": config}
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            barrier()
+            dist.destroy_process_group()
+        return
+
     search_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in whole.events]))
     locate_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in whole.events])) if locate else 0.0
     kernel_log = g.ordered_kernel_log() if ordered else []
@@ -1509,11 +1699,6 @@ def main():
     lookup_first = bool(ordered and g.last_ordered_kernel_is_lookup())  # the dominant kernel of every step was encodeLookupKernel
     # (no seed-order path: the hits-only search is awfmGpuSearch, which takes large batches through exactLookupSearchKernel)
     exact_looked_up = bool(not ordered and g.last_search_was_exact_lookup())
-    # which front end(s) the last timed step launched: 0 both (the sample's verdict stays on the device), 1 the lookup kernel
-    # only / 2 the ordered kernels only (the verdict of an earlier step had reached the host: awfmGpuLastLookupFront), -1: no sample
-    lookup_front = g.last_lookup_front()
-    # (a mixed-length batch below the seed-order size on an image with its tables per k-mer length: the lookup kernel alone)
-    small_mixed_lookup = bool(d_offsets is not None and not ordered and not amino and g.length_tables[0] and g.last_ordered_kernel_is_lookup())
     lookup_kept = g.last_ordered_kept() if lookup_first else 0  # before any other search re-uses the scratch
     amino_looked_up = bool(amino_lookup and whole.ordered and g.last_ordered_kernel_is_lookup())  # aminoLookupSearchKernel did the timed steps (its sample said so)
     lookup_kept_amino = g.last_ordered_kept() if amino_looked_up else 0  # k-mers still alive after their table entry
@@ -1531,17 +1716,11 @@ def main():
     state["positions"] = to_dense(whole)
     state["sparse"] = False  # (the dense arrays are complete: ranges of the k-mers without hits are {1, 0}, counts are written)
 
-    if args.dump_dir:  # testing: this rank's shard results, for a check against the oracle outside the bench
-        os.makedirs(args.dump_dir, exist_ok=True)
-        dump = {"first": np.uint64(first), "queries": np.uint64(Q)}
-        if args.mode == "count":
-            dump["counts"] = d_counts.cpu().numpy().view(np.uint32)
-        else:
-            dump["ranges"] = d_ranges.cpu().numpy().view(np.uint64).reshape(Q, 2)
-            dump["hit_offsets"] = d_hit_off.cpu().numpy().view(np.uint64)
-            if not state["windowed"]:
-                dump["positions"] = state["positions"][: state["hits"]].cpu().numpy().view(np.uint64)
-        np.savez(os.path.join(args.dump_dir, f"rank{rank}.npz"), **dump)
+    if args.dump_dir:
+        dump_shard(state["positions"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, np, first, Q, d_counts, d_ranges if locate else None, d_hit_off if locate else None,
+                     state["positions"] if locate and not whole.windowed else None)
 
     # ---- digests of this rank's results; rank 0 checks all ranks' against the committed digests of the 1-rank run ----
     kmer_name = f"{args.mixed_lengths[0]}-{args.mixed_lengths[1]}" if args.workload == "mixed" else str(K)
@@ -1574,7 +1753,6 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.record_digests)), exist_ok=True)
         json.dump(known, open(args.record_digests, "w"), indent=1, sort_keys=True)
 
-    kdesc = f"{args.mixed_lengths[0]}..{args.mixed_lengths[1]}-mers" if args.workload == "mixed" else f"{K}-mers"
     # ---- roofline of the dominant kernel ----
     tally = g.search_tally(d_chars.data_ptr(), off_ptr, K, Q)
     rank_bytes = RANK_BYTES_AMINO if amino else RANK_BYTES_DNA
@@ -2438,65 +2616,12 @@ def main():
         from avxwindowfmindex_amd import synth as _synth
         secondary["wide"] = wide_leg(L, api, digest, _synth, torch, np, dev, record_digests=args.record_digests)
 
-    # the clocks this box runs at (boxes of the pool differ by several per cent on the same code: the line says which one it
-    # was).  Read from sysfs -- no child process: a process that has initialised the GPU must not start one.
-    clocks = None
-    try:
-        import glob
-        cards = sorted(glob.glob("/sys/class/drm/card[0-9]*/device/pp_dpm_sclk"))
-        if cards:
-            base = os.path.dirname(cards[min(max(args.force_device, 0) if world == 1 else local_rank, len(cards) - 1)])
-            clocks = {}
-            for name in ("sclk", "mclk", "fclk"):
-                path = os.path.join(base, f"pp_dpm_{name}")
-                if os.path.exists(path):
-                    levels = open(path).read().split("\n")
-                    current = [ln for ln in levels if ln.strip().endswith("*")]
-                    clocks[name] = (current[0].split(":")[1].replace("*", "").strip() if current else None)
-                    clocks[name + "_max"] = levels[-2].split(":")[1].replace("*", "").strip() if len(levels) > 1 and ":" in levels[-2] else None
-    except Exception:  # noqa: BLE001  (reporting only)
-        clocks = None
-    per = "per GPU" if args.scaling == "weak" else f"in total, sharded over {world} rank(s)"
-    deep_build_s, deep_transient = deep_first_build if args.device_seed_k < 0 else deep_last_build
     deep_rebuild_s = deep_last_build[0]
-    form_names = {"order": "every k-mer {k-mer number, range} in search order + hit offsets and positions in that order",
-                  "list": "list of the k-mers with hits {k-mer number, range} in k-mer order + hit offsets over the list + positions",
-                  "dense": "range / count under every k-mer number + hit offsets over the batch + positions"}
-    config = {"workload": f"{args.queries / 1e6:g} M {args.workload} {kdesc} {per}, {args.mode}, "
-                          f"{n / 1e9:g} G{'res' if amino else 'bp'} {args.text} synthetic {args.alphabet} text"
-                          f"{' (GRCh38-sized)' if n >= 3_000_000_000 and not amino else ''}, "
-                          f"SA ratio {args.sa_ratio}, seed table k={args.seed_k}",
-              "parallelism": f"index replica per GPU, query batch sharded over {world} rank(s), no collective",
-              "batch_kmers": batch_total, "rank0_kmers": Q,
-              "timing_collective": shard.timing_backend() or "none (one rank)",
-              "hits_per_step_rank0": int(state["hits"]), "locate_kernels_ms": round(locate_ms, 3),
-              "search_call_ms": round(search_ms, 3), "host_waits_per_step": 0 if not whole.windowed else "one per window",
-              # consecutive steps alternate between this many streams, each with its own result buffers and scratch slot
-              "streams": 1 if whole.windowed else len(lanes),
-              "index_build_s": round(build_s, 2),
-              "device_image_bytes": image_bytes, "device_seed_k": image_deep_k, "device_image": image_described,
-              # the deeper table's construction, whoever started it (the library by itself at awfmGpuIndexAcquire, inside
-              # index_build_s; or --device-seed-k): wall seconds and the device memory held beyond the table at the peak.  In
-              # this process it follows the GPU index builder; 0.55 s in most runs, 4-6 s in some -- one hipMalloc, the first the
-              # runtime cannot serve from blocks it holds (memory to hand back or to scrub after the process before); in a process
-              # that reads its index from a file the construction takes 0.6 s (scripts/first_call_probe.py; device_seed_rebuild_s here)
-              "device_seed_build_s": round(deep_build_s, 2), "device_seed_transient_bytes": int(deep_transient),
-              # of which inside the hipMalloc calls (the table's 34 GB): the seconds some runs show are the allocation, not the kernels
-              "device_seed_alloc_s": round(deep_first_alloc_s, 2),
-              "device_seed_rebuild_s": round(deep_rebuild_s, 2),  # the same construction once more (after roofline_general dropped the table): the allocator has the memory at hand
-              "device_dense_sa": dense_sa_default, "device_dense_sa_build_s": round(dense_s, 2),
-              "search_path": ({"order": "awfmGpuSearchHitsInOrder", "list": "awfmGpuSearchHitsCompact",
-                               "dense": "awfmGpuSearchHitsSparse" if narrow_counts else "awfmGpuSearchHits"}[whole.form] if locate
-                              else "awfmGpuSearchHits") + (", seed order" if ordered else ", mixedLookupSearchKernel" if small_mixed_lookup else ", general kernel"),
-              "result_format": form_names[whole.form] if locate else "count under every k-mer number",
-              "result_format_probe_ms": getattr(whole, "form_probe_ms", None),  # mixed-length dense-hit batches: one search call of each form, timed by the probe
-              "lookup_front": {0: "both front ends launched, the sample decides on the device", 1: "lookup kernel only (predicted from an earlier step's sample)",
-                               2: "ordered kernels only (predicted from an earlier step's sample)"}.get(lookup_front, "no sample"),
-              "list_tail": "awfmGpuListLocateOnDevice (one launch)" if locate and whole.form == "list" and list_tail else None}
-    lt_bytes, lt_s = length_tables_built
-    if lt_bytes:  # built by the probe step of a mixed-length batch (awfm_mixed_lookup_kernel.h): device-only, kept with the image
-        config["length_tables_bytes"] = lt_bytes
-        config["length_tables_build_s"] = round(lt_s, 3)
+    config = run_config(deep_first_build if args.device_seed_k < 0 else deep_last_build, image_bytes, image_deep_k, image_described,
+                        length_tables_built)
+    config.update(locate_kernels_ms=round(locate_ms, 3), search_call_ms=round(search_ms, 3),
+                  # the same construction once more (after roofline_general dropped the table): the allocator has the memory at hand
+                  device_seed_rebuild_s=round(deep_rebuild_s, 2))
     if dense_form:  # flat copies for readers that keep scalars only
         config["dense_form"] = dense_form
         config["dense_form_ms_per_step"] = dense_form["ms_per_step"]
@@ -2520,11 +2645,6 @@ def main():
             config["wide_roofline_frac"] = secondary["wide"]["random"]["roofline"]["frac"]
             config["wide_planted_value"] = secondary["wide"]["planted"]["value"]
             config["wide_planted_ms_per_step"] = secondary["wide"]["planted"]["ms_per_step"]
-    if clocks:
-        config["gpu_clocks"] = clocks
-        for name in ("sclk", "mclk", "fclk"):
-            if name in clocks:
-                config[f"gpu_{name}"] = str(clocks[name])
     if kernel_log:
         doms = [(f if lookup_first else k) for f, k in kernel_log]
         config["dominant_kernel_ms_first_min_max"] = [round(doms[0], 3), round(min(doms), 3), round(max(doms), 3)]
@@ -2541,8 +2661,7 @@ def main():
         config["scaling_proxy_8_ms"] = e8["ms_max"]
     config["bench_wall_s"] = round(time.time() - T_START, 1)  # this process from its first line to its JSON line (imports, index, every leg)
     out = {
-        "metric": "Mkmers/sec located, GRCh38 nucleotide index" if not amino else "Mkmers/sec located, amino index",
-        "value": round(value, 2), "unit": "Mkmers/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "metric": metric, "value": round(value, 2), "unit": "Mkmers/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         # the same metric for k-mers that OCCUR (drawn from the text: every one located), which is what a seed-and-extend caller
         # sends -- the headline's random 21-mers almost never occur, and lookup first is at its best on them
         "value_present_kmers": secondary["value"] if secondary and "value" in secondary else None,

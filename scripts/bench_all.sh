@@ -10,7 +10,7 @@ run() { # name [ENV=..]... -- bench args
   name=$1; shift
   if [ -n "${ONLY:-}" ]; then case " $ONLY " in *" $name "*) ;; *) return 0;; esac; fi
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" python3 bench.py "$@" 2>"$OUT/$name.err" | tail -1 > "$OUT/bench_$name.json"
+  env "${envs[@]}" python3 bench.py --full "$@" 2>"$OUT/$name.err" | tail -1 > "$OUT/bench_$name.json"
 }
 run default -- --steps 20 --warmup 5
 run count -- --mode count

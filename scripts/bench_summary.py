@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""one-screen summary of a bench.py JSON line (usage: bench_summary.py <file>)"""
+"""one-screen summary of a `bench.py --full` JSON line (usage: bench_summary.py <file>)"""
 import json
 import sys
 

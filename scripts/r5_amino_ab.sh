@@ -2,7 +2,7 @@
 # amino 2e9 / 2e8: lookup forced, general forced, default; planted too (--workload planted)
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/${1:-r5_amino}; mkdir -p "$OUT"
-COMMON="--alphabet amino --no-cpu --no-e2e --no-shard-proxy --no-dense-form --steps 5 --warmup 2"
+COMMON="--alphabet amino --full --no-cpu --no-e2e --no-shard-proxy --no-dense-form --steps 5 --warmup 2"
 for n in 2e9 2e8; do
   for w in random planted; do
     for v in "" "AWFM_GPU_AMINO_LOOKUP=1" "AWFM_GPU_AMINO_LOOKUP=0"; do

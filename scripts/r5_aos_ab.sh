@@ -5,7 +5,7 @@ mkdir -p $out
 for v in "default" "AWFM_GPU_AOS_CHUNK=524288" "AWFM_GPU_AOS_CHUNK=262144" "AWFM_GPU_AOS_CHUNK=2097152" "AWFM_GPU_DEVICES=0,0,0,0" "AWFM_GPU_DEVICES=0,0,0,0 AWFM_GPU_AOS_CHUNK=524288"; do
   name=$(echo "$v" | tr ' =,' '___')
   if [ "$v" = "default" ]; then envs=(); else envs=($v); fi
-  env "${envs[@]}" python bench.py --no-cpu --no-secondary --no-shard-proxy --general-steps 0 --steps 3 --warmup 1 --no-dense-form > $out/$name.json 2> $out/$name.err
+  env "${envs[@]}" python bench.py --full --no-cpu --no-secondary --no-shard-proxy --general-steps 0 --steps 3 --warmup 1 --no-dense-form > $out/$name.json 2> $out/$name.err
   python - "$out/$name.json" "$v" <<'PY'
 import json,sys
 try:

@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=$1; shift
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p "$OUT"
-COMMON="--no-cpu --no-e2e --no-secondary --no-shard-proxy --no-dense-form --general-steps 0 --steps 40 --warmup 5 --queries ${QUERIES:-12500000} ${EXTRA:-}"
+COMMON="--full --no-cpu --no-e2e --no-secondary --no-shard-proxy --no-dense-form --general-steps 0 --steps 40 --warmup 5 --queries ${QUERIES:-12500000} ${EXTRA:-}"
 for rep in 1 2 3; do
   for v in "" "$@"; do
     name=$(echo "${v:-default}" | tr ' =' '__')

@@ -6,7 +6,7 @@ TAG=${1:-r5_base}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu --no-e2e --no-secondary --no-shard-proxy --no-dense-form --general-steps 0 --steps 5 --warmup 2"
+COMMON="--full --no-cpu --no-e2e --no-secondary --no-shard-proxy --no-dense-form --general-steps 0 --steps 5 --warmup 2"
 rocprofv3 --kernel-trace --output-format csv -d "$OUT/random" -- python3 "$ROOT/bench.py" $COMMON --queries 12500000 > "$OUT/random.log" 2>&1
 python3 "$ROOT/scripts/trace_gaps.py" "$OUT/random" --around lookupSearch 3 > "$OUT/random_gaps.txt" 2>&1
 rocprofv3 --kernel-trace --output-format csv -d "$OUT/planted" -- python3 "$ROOT/bench.py" $COMMON --queries 12500000 --workload planted > "$OUT/planted.log" 2>&1

@@ -44,6 +44,47 @@ def test_world_size_must_match_gpus_flag():
     assert r.returncode != 0 and "WORLD_SIZE is 1" in (r.stderr + r.stdout)
 
 
+def test_record_digests_needs_full(tmp_path):
+    """the digests are computed by --full only: a plain run asked to record them refuses before it touches anything"""
+    r = _run_bench(["--record-digests", str(tmp_path / "digests.json")], timeout=120)
+    assert r.returncode != 0 and "--record-digests needs --full" in r.stderr
+    assert not (tmp_path / "digests.json").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_outputs_of_its_last_step(oracle, require_gpu, tmp_path):
+    """a plain run (no --full) prints the headline line only, and --dump-outputs writes what its last timed step computed --
+    a seeded sample of the batch and the first k-mers with hits -- which must be the oracle's results for those k-mers"""
+    from avxwindowfmindex_amd import synth
+    n, Q, K, seed_k = 3_000_000, 2_000_000, 21, 8
+    out = tmp_path / "outputs"
+    line = _line(_run_bench(["--gpus", "1", "--text-len", "3e6", "--queries", "2e6", "--kmer", str(K), "--seed-k", str(seed_k),
+                             "--workload", "planted", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line
+    assert line["steps"] == 3 and line["n_gpus"] == 1
+    assert line["value"] == pytest.approx(Q / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3 + 0.0006 / line["ms_per_step"])
+    assert not any(key in line for key in ("roofline", "cpu_baseline", "digests", "secondary", "scaling_proxy"))
+    txt = synth.text(2, n)
+    oi = oracle.Index.from_text(txt.tobytes(), oracle.DNA, 8, seed_k)
+    chars, offsets = synth.fixed_csr(synth.planted_queries(103, Q, K, txt))
+    sp, ep, cnt, _ = oi.batch_search(chars, offsets, threads=8)
+    ho, pos, _ = oi.batch_locate(sp, ep, threads=8)
+    assert np.array_equal(np.load(out / "totals.npy"), [Q, np.count_nonzero(cnt), cnt.sum()])
+    for group in ("sample_", "found_"):
+        got = {name: np.load(out / f"{group}{name}.npy") for name in ("kmers", "counts", "ranges", "hit_offsets", "positions")}
+        assert all(a.dtype == np.float64 for a in got.values())
+        kmers = got["kmers"].astype(np.int64)
+        assert len(kmers) == min(Q, 1 << 18) and np.all(np.diff(kmers) > 0)
+        assert np.array_equal(got["counts"], cnt[kmers])
+        hit = cnt[kmers] > 0
+        assert np.array_equal(got["ranges"][hit, 0], sp[kmers][hit]) and np.array_equal(got["ranges"][hit, 1], ep[kmers][hit])
+        assert np.all(got["ranges"][~hit] == [1, 0])
+        assert np.array_equal(np.diff(got["hit_offsets"]), got["counts"]) and got["hit_offsets"][0] == 0
+        want = np.concatenate([pos[ho[k]:ho[k + 1]] for k in kmers])
+        assert len(got["positions"]) == len(want) and np.array_equal(got["positions"], want)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload,mode", [("planted", "locate"), ("random", "count")])
 def test_two_ranks_on_one_gpu_search_their_own_shards(oracle, awfm, require_gpu, tmp_path, workload, mode):
@@ -96,7 +137,7 @@ def test_n_rank_digests_equal_the_one_rank_run(require_gpu, tmp_path, workload, 
     mixed lengths cut by the sum of the lengths; weak: the 2-rank batch is the 1-rank batch plus a second one)"""
     golden = str(tmp_path / "digests.json")
     common = ["--text-len", "3e6", "--queries", "1e6", "--kmer", "15", "--seed-k", "8", "--workload", workload, "--mode", mode,
-              "--no-cpu", "--no-e2e", "--no-secondary", "--general-steps", "0", "--steps", "1", "--warmup", "1"]
+              "--full", "--no-cpu", "--no-e2e", "--no-secondary", "--general-steps", "0", "--steps", "1", "--warmup", "1"]
     one = _line(_run_bench(common + ["--gpus", "1", "--scaling", scaling, "--record-digests", golden]))
     assert one["digests"]["status"] == "unknown"  # nothing committed for this toy configuration
     if scaling == "weak":  # the second rank's batch, recorded by a 1-rank run that starts at its first k-mer
@@ -129,7 +170,7 @@ def test_seed_bucket_sharding_digests_equal_the_contiguous_one_rank_run(require_
     digest the ordinary 1-rank run of the same batch recorded; and so must the 1-rank run of the new mode itself."""
     golden = str(tmp_path / "digests.json")
     common = ["--text-len", "3e6", "--queries", "1e6", "--kmer", "21", "--seed-k", "8", "--workload", "planted", "--mode", "locate",
-              "--no-cpu", "--no-e2e", "--no-secondary", "--general-steps", "0", "--steps", "1", "--warmup", "1", "--scaling", "strong"]
+              "--full", "--no-cpu", "--no-e2e", "--no-secondary", "--general-steps", "0", "--steps", "1", "--warmup", "1", "--scaling", "strong"]
     one = _line(_run_bench(common + ["--gpus", "1", "--record-digests", golden]))
     os.environ["AWFM_BENCH_DIGESTS"] = golden
     try:
@@ -155,7 +196,7 @@ def test_two_ranks_on_two_distinct_gpus_over_rccl(require_gpu, tmp_path):
     if _lib.lib().awfmGpuDeviceCount() < 2:
         pytest.skip("needs two GPUs")
     golden = str(tmp_path / "digests.json")
-    common = ["--text-len", "3e6", "--queries", "1e6", "--kmer", "15", "--seed-k", "8", "--workload", "planted", "--no-cpu",
+    common = ["--text-len", "3e6", "--queries", "1e6", "--kmer", "15", "--seed-k", "8", "--workload", "planted", "--full", "--no-cpu",
               "--no-e2e", "--no-secondary", "--general-steps", "0", "--steps", "2", "--warmup", "1", "--scaling", "strong"]
     _line(_run_bench(common + ["--gpus", "1", "--record-digests", golden]))
     os.environ["AWFM_BENCH_DIGESTS"] = golden
