@@ -841,13 +841,17 @@ __global__ void relayoutAminoKernel(const unsigned long long *__restrict__ ref, 
 
 }  // namespace
 
-struct AwFmGpuIndex {
-  /* a lane: a second host-side handle on the device image of `shares` (same device buffers, own staging
-   * buffers and locks), so that two host threads can overlap their pack/scatter with each other's transfers
-   * and kernels without a second copy of the index; owns none of the device arrays */
-  AwFmGpuIndex *shares = nullptr;
-  int device = 0;
-  bool amino = false;
+struct AwFmGpuIndex;
+/* Locks of an image and its handles, in the one order they are taken:
+ *   awfm_gpu_image.hip's tableMutex (the registry) -> streamMutex -> handlesMutex -> for each handle in handle order: aosMutex ->
+ *   workMutex -> orderMutex -> lengthMutex -> joinMutex.
+ * A search takes one handle's locks in that order (AoS lane -> host-buffer call -> ordered search).  AwFmGpuExclusive is the only
+ * holder of the locks of more than one handle: every change of an image's view (DevIndex and the arrays behind it) happens inside
+ * it.  Nobody takes tableMutex while holding a handle's lock. */
+
+/* the device image of an index on one device, shared by its handles (AwFmGpuIndex): everything of it that can change after it is
+ * made exists here once */
+struct AwFmGpuImage {
   DevIndex dev{};
   void *dBlocks = nullptr;
   void *dSuper = nullptr;
@@ -861,7 +865,7 @@ struct AwFmGpuIndex {
   uint64_t deepSeedTransientBytes = 0;  /* device memory that construction held beyond the table itself, at its peak */
   void *dDeepBig = nullptr; /* the deeper table's lengths of 65535 and more, by where the range begins (DevIndex::deepBigBySp) */
   /* optional tables of the k-mer lengths below the deeper table's (awfmGpuBuildLengthTables), built by the first
-   * mixed-length batch that can use them; owned by the primary, found there by its lanes (under lengthMutex) */
+   * mixed-length batch that can use them (under lengthMutex) */
   std::mutex lengthMutex;
   void *dLengthTable = nullptr;
   unsigned lengthDepths = 0; /* levels 1 .. lengthDepths */
@@ -881,10 +885,47 @@ struct AwFmGpuIndex {
   std::string accelNotes;
   uint64_t deviceBytes = 0;
   uint64_t numBlocks = 0; /* device blocks (128 positions each) */
+  /* Accelerators built BEHIND the first searches (round 6).  An image made by awfmGpuIndexAcquireAll -- the drop-in entry
+   * points' way -- is usable as soon as its blocks, seed table, sampled array and pair image are on the device (the reference's
+   * index is usable the moment awFmReadIndexFromFile returns, ref src/AwFmFile.c:195-449); its deeper table and full suffix array
+   * are made by a thread of their own on a stream of their own and installed between two calls (awfmGpuAdoptAccelerators).
+   * Searches give the reference's results with or without them.  accelState: 0 nothing pending, 1 being built, 2 built and
+   * waiting to be installed.  The thread is joined by awfm_gpu_image.hip's joinBuilder alone, under joinMutex. */
+  std::mutex joinMutex;
+  std::thread accelThread;
+  std::atomic<int> accelState{0};
+  struct PendingAccel {
+    void *deepTable = nullptr, *deepBig = nullptr;
+    uint64_t deepBytes = 0, deepBigBytes = 0, deepTransient = 0;
+    unsigned deepK = 0, deepFormat = 0, deepNext = 0, numDeepBig = 0;
+    double deepSeconds = 0.0, deepAllocSeconds = 0.0;
+    void *dense = nullptr;
+    bool denseWide = false;
+    uint64_t denseBytes = 0;
+    double denseSeconds = 0.0;
+    std::string notes;
+  } pendingAccel;
+  /* chunked host-buffer pipeline (awfm_gpu_stream.hip): three slots of device buffers + page-locked staging,
+   * created on first use, one batch at a time, run on the primary handle */
+  std::mutex streamMutex;
+  struct AwFmGpuStreamState *streamState = nullptr;
+  /* the handles on the image: [0] the primary (awfmGpuIndexCreate's, or lane 0 of the registry), then the lanes the drop-in entry
+   * points add for a device named again in $AWFM_GPU_DEVICES -- each with its own staging and locks, so that two host threads
+   * overlap their pack/scatter with each other's transfers and kernels without a second copy of the index */
+  std::mutex handlesMutex;
+  std::vector<AwFmGpuIndex *> handles;
+};
+
+/* one caller's handle on an image: its staging, its scratch, its locks and its selections */
+struct AwFmGpuIndex {
+  AwFmGpuImage *image = nullptr;
+  int lane = 0; /* its place in image->handles: 0 the primary */
+  int device = 0; /* (fixed when the image is made, the same in all its handles) */
+  bool amino = false;
+  int numCUs = 256;
   AwFmGpuKernel kernel = AWFM_GPU_KERNEL_AUTO;
   /* testing: run the 64-bit-position kernels although bwtLength < 2^32 (awfmGpuIndexSetWide, $AWFM_GPU_FORCE_WIDE) */
   bool forceWide = false;
-  int numCUs = 256;
   /* grow-only workspace for the host-buffer entry points */
   std::mutex workMutex;
   void *dWork = nullptr;
@@ -895,7 +936,7 @@ struct AwFmGpuIndex {
   void *dSparse = nullptr; /* temporaries of awfmGpuSortHits, grow-only (under orderMutex) */
   size_t sparseBytes = 0;
   hipEvent_t windowEvent[2] = {nullptr, nullptr}; /* the two hit windows in flight of awfmGpuLocateHostWindows */
-  /* ordered search path (awfm_gpu_ordered.hip): grow-only scratch shared by all searches on this image;
+  /* ordered search path (awfm_gpu_ordered.hip): grow-only scratch shared by all searches on this handle;
    * the event orders its re-use across streams */
   int orderMode = -1; /* -1 auto, 0 off, 1 on */
   std::mutex orderMutex;
@@ -969,32 +1010,9 @@ struct AwFmGpuIndex {
     unsigned agreed = 0;
   } predict;
   int lastSearchExact = 0; /* awfmGpuLastSearchWasExactLookup */
-  /* Accelerators built BEHIND the first searches (round 6).  An image made by awfmGpuIndexAcquireAll -- the drop-in entry
-   * points' way -- is usable as soon as its blocks, seed table, sampled array and pair image are on the device (the reference's
-   * index is usable the moment awFmReadIndexFromFile returns, ref src/AwFmFile.c:195-449); its deeper table and full suffix array
-   * are made by a thread of their own on a stream of their own and installed between two calls (awfmGpuAdoptAccelerators).
-   * Searches give the reference's results with or without them.  accelState: 0 nothing pending, 1 being built, 2 built and
-   * waiting to be installed. */
-  std::thread accelThread;
-  std::atomic<int> accelState{0};
-  struct PendingAccel {
-    void *deepTable = nullptr, *deepBig = nullptr;
-    uint64_t deepBytes = 0, deepBigBytes = 0, deepTransient = 0;
-    unsigned deepK = 0, deepFormat = 0, deepNext = 0, numDeepBig = 0;
-    double deepSeconds = 0.0, deepAllocSeconds = 0.0;
-    void *dense = nullptr;
-    bool denseWide = false;
-    uint64_t denseBytes = 0;
-    double denseSeconds = 0.0;
-    std::string notes;
-  } pendingAccel;
   std::mutex aosMutex;       /* serialises the AoS entry points (they share the pinned buffers) */
   void *pinned[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t pinnedBytes[4] = {0, 0, 0, 0};
-  /* chunked host-buffer pipeline (awfm_gpu_stream.hip): three slots of device buffers + page-locked staging,
-   * created on first use, one batch at a time */
-  std::mutex streamMutex;
-  struct AwFmGpuStreamState *streamState = nullptr;
 };
 
 /* Test and diagnostics hooks -- none of them selects a faster path --, all behind ONE environment variable:
@@ -1050,13 +1068,13 @@ inline uint64_t awfmSuperBytes(uint64_t bwtLength, bool amino, unsigned superShi
 /* 32-bit BWT positions in the kernels: exact whenever bwtLength < 2^32 (ref src/AwFmIndex.h:88-91 is 64-bit
  * throughout; the NARROW = false instantiations are that arithmetic) */
 inline bool awfmImageNarrow(const AwFmGpuIndex *g) {
-  return !g->forceWide && g->dev.bwtLength < (1ull << 32) && (g->amino || g->dev.numSuper == 1);
+  return !g->forceWide && g->image->dev.bwtLength < (1ull << 32) && (g->amino || g->image->dev.numSuper == 1);
 }
 
 /* where the kernels that use the pair image keep its 32-bit superblock bases (64 B per 2^23 positions): in dynamic LDS,
  * or read from memory beside the blocks */
 inline bool awfmPairSuperInLds(const AwFmGpuIndex *g) {
-  return g->dev.numPairSuper * (kPairSuperStride * 4u) <= 32768u; /* measured: 4.46 ms from LDS against 4.91 ms from memory (10^8 random 21-mers) */
+  return g->image->dev.numPairSuper * (kPairSuperStride * 4u) <= 32768u; /* measured: 4.46 ms from LDS against 4.91 ms from memory (10^8 random 21-mers) */
 }
 
 /* RAII hipSetDevice */
@@ -1099,30 +1117,26 @@ inline size_t alignUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 /* the image's full suffix array as a kernel argument */
 inline DenseSa denseSaOf(const AwFmGpuIndex *g) {
   DenseSa sa;
-  sa.words = (const unsigned *)g->dDenseSa;
-  sa.wide = g->denseWide ? 1u : 0u;
+  sa.words = (const unsigned *)g->image->dDenseSa;
+  sa.wide = g->image->denseWide ? 1u : 0u;
   return sa;
 }
-/* awfm_gpu_image.hip: the image's grow-only work buffer (the caller holds workMutex); lanes that cooperate on one k-mer in the
- * general kernel and the walk; the lanes of a primary image */
+/* awfm_gpu_image.hip: the handle's grow-only work buffer (the caller holds workMutex); lanes that cooperate on one k-mer in the
+ * general kernel and the walk */
 enum AwFmReturnCode awfmGpuEnsureWork(AwFmGpuIndex *g, size_t bytes);
 int awfmGpuLanesPerQuery(const AwFmGpuIndex *g);
-std::vector<AwFmGpuIndex *> awfmGpuLanesOf(const AwFmGpuIndex *primary);
-/* holds the work and AoS locks of every lane of a primary image for the lifetime of the object */
-struct AwFmGpuLaneLocks {
-  std::vector<AwFmGpuIndex *> lanes;
-  explicit AwFmGpuLaneLocks(const AwFmGpuIndex *primary) : lanes(awfmGpuLanesOf(primary)) {
-    for (AwFmGpuIndex *lane : lanes) {
-      lane->aosMutex.lock();
-      lane->workMutex.lock();
-    }
-  }
-  ~AwFmGpuLaneLocks() {
-    for (AwFmGpuIndex *lane : lanes) {
-      lane->workMutex.unlock();
-      lane->aosMutex.unlock();
-    }
-  }
+/* Nobody is inside a search through any handle of the image for the lifetime of the object (lock order: above AwFmGpuImage):
+ * handlesMutex, then every handle's aosMutex, workMutex and orderMutex -- all of them (`held`), or, not waiting, none.  Every
+ * change of the image's view happens inside one; a handle is added to the image only between them. */
+struct AwFmGpuExclusive {
+  explicit AwFmGpuExclusive(AwFmGpuImage *image, bool wait = true);
+  ~AwFmGpuExclusive();
+  AwFmGpuExclusive(const AwFmGpuExclusive &) = delete;
+  AwFmGpuExclusive &operator=(const AwFmGpuExclusive &) = delete;
+  bool held = false;
+
+ private:
+  std::vector<std::mutex *> locked;
 };
 /* awfm_gpu_locate.hip: LF-walk + sampled-SA kernels over `totalHits` BWT positions stored in dPositions (in place, or to `out`);
  * stepCap != 0: the construction of the full suffix array (walks given up after so many steps are parked) */
@@ -1135,9 +1149,8 @@ enum AwFmReturnCode awfmGpuApplyDenseSaAuto(AwFmGpuIndex *g);
 enum AwFmReturnCode awfmGpuBuildDenseSaAuto(const AwFmGpuIndex *g, void **arrayOut, bool *wideOut, uint64_t *bytesOut, double *secondsOut,
                                             std::string *notes);
 /* awfm_gpu_image.hip: installs what an image's builder thread has finished.  wait: join the thread first (the explicit
- * entry points); otherwise only when it is done and the image's locks are free right now.  lanes: the image's lanes, listed by
- * a caller that holds the registry's lock (NULL: looked up here) */
-void awfmGpuAdoptAccelerators(AwFmGpuIndex *g, bool wait, const std::vector<AwFmGpuIndex *> *lanes = nullptr);
+ * entry points); otherwise only when it is done and no handle of the image is inside a search right now */
+void awfmGpuAdoptAccelerators(AwFmGpuImage *image, bool wait);
 
 /* blocks + superblock table of the device image from reference-layout blocks already on the device (current device,
  * null stream).  dBlocks / dSuper are allocated by the caller: awfmDeviceBlocks x awfmDeviceBlockBytes, awfmSuperBytes.
@@ -1160,11 +1173,11 @@ int awfmGpuAminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
 AwFmGpuIndex *awfmGpuIndexAdopt(const struct AwFmIndex *index, int device, void *dBlocks, void *dSuper, unsigned superShift,
                                 void *dSeed, void *dSa, void *dPrefix, unsigned long long sentinelPos, uint64_t deviceBytes);
 void awfmGpuIndexRegister(const struct AwFmIndex *index, AwFmGpuIndex *g);
-/* awfm_gpu_pair.hip: builds (enable) or drops the pair image of a primary nucleotide image; the caller holds whatever
- * locks the image needs and copies the view into its lanes */
+/* awfm_gpu_pair.hip: builds (enable) or drops the pair image of a nucleotide image; the caller holds whatever locks the image
+ * needs */
 enum AwFmReturnCode awfmGpuApplyPairImage(AwFmGpuIndex *g, bool enable);
 /* awfm_gpu_stream.hip: drops the pipeline slots of an image (called by awfmGpuIndexDestroy) */
-void awfmGpuStreamStateFree(AwFmGpuIndex *g);
+void awfmGpuStreamStateFree(AwFmGpuImage *image);
 /* hit offsets of a chunk without a host wait: exclusive scan of the 32-bit counts (dCounts != NULL) or of the range
  * lengths into dHitOffsets[0..n], the total also copied to *pinnedTotal (page-locked) on the stream */
 enum AwFmReturnCode awfmGpuHitOffsetsAsync(AwFmGpuIndex *g, const uint32_t *dCounts, const struct AwFmSearchRange *dRanges,

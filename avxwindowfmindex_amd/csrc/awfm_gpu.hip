@@ -28,7 +28,7 @@
 
 
 namespace {
-/* `dev`: the image view the kernel gets -- g->dev, or a copy with a field changed for this launch only (the tally
+/* `dev`: the image view the kernel gets -- g->image->dev, or a copy with a field changed for this launch only (the tally
  * prices the reference algorithm without the deeper table) so that the shared image is never edited */
 template <bool AMINO, int G, bool CSR, bool TALLY, bool NARROW>
 void launchSearchKernelN(const AwFmGpuIndex *g, const DevIndex &dev, hipStream_t s, const uint8_t *dChars,
@@ -47,7 +47,7 @@ void launchPairSearchKernel(const AwFmGpuIndex *g, const DevIndex &dev, hipStrea
   /* the 16 pair bases of every superblock in dynamic LDS, as in the ordered kernel (same box, 10^8 random 21-mers:
    * 11.4-11.7 ms against 12.8-12.9 ms with the bases read from memory) */
   const bool inLds = NARROW && awfmPairSuperInLds(g);
-  const size_t lds = inLds ? (size_t)g->dev.numPairSuper * 64u : 0u;
+  const size_t lds = inLds ? (size_t)g->image->dev.numPairSuper * 64u : 0u;
   DevIndex view = dev;
   view.pairSuperInLds = inLds ? 1u : 0u;
   const unsigned grid = gridFor(nq, g, searchKernel<false, 4, CSR, false, NARROW, false, true>, kThreads / 4, lds);
@@ -123,16 +123,16 @@ static enum AwFmReturnCode searchGeneral(AwFmGpuIndex *g, const uint8_t *dChars,
     if (did > 0) return AwFmSuccess;
     if (did < 0 && did != -(int)AwFmAllocationFailure) return (enum AwFmReturnCode)(-did);
   }
-  if (!g->amino && lanes == 4 && g->dev.pairBlocks) {
+  if (!g->amino && lanes == 4 && g->image->dev.pairBlocks) {
     const unsigned long long *off = (const unsigned long long *)dOffsets;
     const bool narrow = awfmImageNarrow(g);
 #define AWFM_PAIR_GO(CSRV, NR) \
-  launchPairSearchKernel<CSRV, NR>(g, g->dev, s, dChars, off, fixedLength, numQueries, (ulonglong2 *)dRanges, dCounts)
+  launchPairSearchKernel<CSRV, NR>(g, g->image->dev, s, dChars, off, fixedLength, numQueries, (ulonglong2 *)dRanges, dCounts)
     if (off) narrow ? AWFM_PAIR_GO(true, true) : AWFM_PAIR_GO(true, false);
     else narrow ? AWFM_PAIR_GO(false, true) : AWFM_PAIR_GO(false, false);
 #undef AWFM_PAIR_GO
   } else {
-    launchSearch<false>(g, g->dev, lanes, s, dChars, (const unsigned long long *)dOffsets, fixedLength, numQueries,
+    launchSearch<false>(g, g->image->dev, lanes, s, dChars, (const unsigned long long *)dOffsets, fixedLength, numQueries,
                         (ulonglong2 *)dRanges, dCounts, nullptr);
   }
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
@@ -212,7 +212,7 @@ enum AwFmReturnCode awfmGpuSearchTally(AwFmGpuIndex *g, const uint8_t *dChars, c
     /* the tally prices the reference algorithm (index seed table), so this launch gets a copy of
      * the image view without the device-only deeper table; the image itself is not touched (other threads may
      * be searching through it) */
-    DevIndex plain = g->dev;
+    DevIndex plain = g->image->dev;
     if (!awfmGpuDiag("tally_with_deep")) { /* (diagnostics: what the kernel executes behind the deeper table) */
       plain.deepSeed = nullptr;
       plain.deepK = 0;

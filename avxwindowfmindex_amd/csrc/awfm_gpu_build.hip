@@ -796,7 +796,7 @@ bool awfmGpuBuildDeepSeedTable(const AwFmGpuIndex *g, unsigned deepK, void **tab
   if (formatOut) *formatOut = 0;
   if (bigOut) *bigOut = nullptr;
   u64 curBytes = 0; /* the level the next one is made from (0: the index's own table) */
-  const unsigned K = g->dev.seedK;
+  const unsigned K = g->image->dev.seedK;
   /* nucleotide: up to 16 characters (2^32 entries); amino: up to 7 (20^7 = 1.28 * 10^9 entries, the index a 32-bit sum) */
   if (deepK <= K || deepK > (g->amino ? 7u : 16u) || K == 0) {
     awfmGpuSetError("deep seed table: seedK < deepK <= 16 (nucleotide) / 7 (amino)");
@@ -807,20 +807,20 @@ bool awfmGpuBuildDeepSeedTable(const AwFmGpuIndex *g, unsigned deepK, void **tab
   u64 len = 1;
   for (unsigned i = 0; i < K; i++) len *= card;
   DeviceBuffer cur, nxt, big;
-  const ulonglong2 *parent = g->dev.seed;
+  const ulonglong2 *parent = g->image->dev.seed;
   const bool narrow = awfmImageNarrow(g);
   /* the table's entries (DevIndex::deepNarrow): 8 bytes {sp, length} where the image runs 32-bit positions (every amino
    * image below 2^32), 8 bytes sp36 | length12 | next16 (nucleotide) or sp36 | length8 | next20 (amino) for the images that run
    * 64-bit ones, up to 2^36 positions (round 6), 16 bytes {sp, ep} for everything else */
-  const unsigned format = g->dev.bwtLength < (1ull << 32) && narrow ? 1u
-                          : (formatOut && bigOut && g->dev.bwtLength < (1ull << kDeepWideMaxBits) ? 2u : 0u);
+  const unsigned format = g->image->dev.bwtLength < (1ull << 32) && narrow ? 1u
+                          : (formatOut && bigOut && g->image->dev.bwtLength < (1ull << kDeepWideMaxBits) ? 2u : 0u);
   if (format == 2u) {
-    const size_t bigBytes = ((size_t)(g->dev.bwtLength >> (g->amino ? kAminoWideBigShift : kDeepWideBigShift)) + 2u) * 8u;
+    const size_t bigBytes = ((size_t)(g->image->dev.bwtLength >> (g->amino ? kAminoWideBigShift : kDeepWideBigShift)) + 2u) * 8u;
     if (!big.alloc(bigBytes)) return false;
     BUILD_TRY(awfmGpuSetupMemset(big.p, 0, bigBytes));
   }
   /* two levels per pass through the pair image where the image has one (deepSeedPairLevelKernel) */
-  const bool pairLevels = !g->amino && g->dev.pairBlocks;
+  const bool pairLevels = !g->amino && g->image->dev.pairBlocks;
   const bool pairSuperInLds = pairLevels && narrow && awfmPairSuperInLds(g);
   for (unsigned L = K; L < deepK;) {
     const unsigned levels = pairLevels && deepK - L >= 2u ? 2u : 1u;
@@ -840,9 +840,9 @@ bool awfmGpuBuildDeepSeedTable(const AwFmGpuIndex *g, unsigned deepK, void **tab
     const unsigned grid = (unsigned)(blocks < resident ? blocks : resident);
     u64 *bigAt = big.as<u64>();
     if (levels == 2u) {
-      DevIndex dev = g->dev;
+      DevIndex dev = g->image->dev;
       dev.pairSuperInLds = pairSuperInLds ? 1u : 0u;
-      const size_t lds = pairSuperInLds ? (size_t)g->dev.numPairSuper * 64u : 0u;
+      const size_t lds = pairSuperInLds ? (size_t)g->image->dev.numPairSuper * 64u : 0u;
       const u64 pairBlocks = (outLen + kSeedGroupsPerBlock - 1) / kSeedGroupsPerBlock;
       const unsigned pairGrid = (unsigned)(pairBlocks < resident ? pairBlocks : resident);
 #define AWFM_PAIR_LEVEL(O, NR) \
@@ -857,17 +857,17 @@ bool awfmGpuBuildDeepSeedTable(const AwFmGpuIndex *g, unsigned deepK, void **tab
       const u64 aminoBlocks = (outLen + kThreads / 4 - 1) / (kThreads / 4);
       const unsigned aminoGrid = (unsigned)(aminoBlocks < resident ? aminoBlocks : resident);
       if (out == 2u)
-        hipLaunchKernelGGL((aminoDeepSeedLevelKernel<2>), dim3(aminoGrid), dim3(kThreads), 0, awfmGpuSetupStream, g->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
+        hipLaunchKernelGGL((aminoDeepSeedLevelKernel<2>), dim3(aminoGrid), dim3(kThreads), 0, awfmGpuSetupStream, g->image->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
       else if (out == 1u)
-        hipLaunchKernelGGL((aminoDeepSeedLevelKernel<1>), dim3(aminoGrid), dim3(kThreads), 0, awfmGpuSetupStream, g->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
+        hipLaunchKernelGGL((aminoDeepSeedLevelKernel<1>), dim3(aminoGrid), dim3(kThreads), 0, awfmGpuSetupStream, g->image->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
       else
-        hipLaunchKernelGGL((aminoDeepSeedLevelKernel<0>), dim3(aminoGrid), dim3(kThreads), 0, awfmGpuSetupStream, g->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
+        hipLaunchKernelGGL((aminoDeepSeedLevelKernel<0>), dim3(aminoGrid), dim3(kThreads), 0, awfmGpuSetupStream, g->image->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
     } else if (out == 2u)
-      hipLaunchKernelGGL((deepSeedLevelKernel<kUnroll, 2>), dim3(grid), dim3(kThreads), 0, awfmGpuSetupStream, g->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
+      hipLaunchKernelGGL((deepSeedLevelKernel<kUnroll, 2>), dim3(grid), dim3(kThreads), 0, awfmGpuSetupStream, g->image->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
     else if (out == 1u)
-      hipLaunchKernelGGL((deepSeedLevelKernel<kUnroll, 1>), dim3(grid), dim3(kThreads), 0, awfmGpuSetupStream, g->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
+      hipLaunchKernelGGL((deepSeedLevelKernel<kUnroll, 1>), dim3(grid), dim3(kThreads), 0, awfmGpuSetupStream, g->image->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
     else
-      hipLaunchKernelGGL((deepSeedLevelKernel<kUnroll, 0>), dim3(grid), dim3(kThreads), 0, awfmGpuSetupStream, g->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
+      hipLaunchKernelGGL((deepSeedLevelKernel<kUnroll, 0>), dim3(grid), dim3(kThreads), 0, awfmGpuSetupStream, g->image->dev, parent, len, outLen, nxt.as<ulonglong2>(), bigAt);
     BUILD_TRY(hipGetLastError());
     BUILD_TRY(awfmGpuSetupSync());
     clock_gettime(CLOCK_MONOTONIC, &tc);
@@ -895,11 +895,11 @@ bool awfmGpuBuildLengthTables(const AwFmGpuIndex *g, unsigned maxDepth, void **t
   *bigOut = nullptr;
   /* the entries follow the deeper table's format (DevIndex::deepNarrow): {sp, length} beside format 1, sp36 | length28 beside
    * format 2 */
-  if (g->amino || maxDepth < 1u || maxDepth > 15u || (g->dev.deepNarrow != 1u && g->dev.deepNarrow != 2u)) {
+  if (g->amino || maxDepth < 1u || maxDepth > 15u || (g->image->dev.deepNarrow != 1u && g->image->dev.deepNarrow != 2u)) {
     awfmGpuSetError("length tables: nucleotide images with an 8-byte deeper table, k-mer lengths 1..15");
     return false;
   }
-  const bool wide = g->dev.deepNarrow == 2u;
+  const bool wide = g->image->dev.deepNarrow == 2u;
   DeviceGuard guard(g->device);
   const u64 entries = awfmLengthTableAt(maxDepth + 1u);
   DeviceBuffer table, big;
@@ -910,25 +910,25 @@ bool awfmGpuBuildLengthTables(const AwFmGpuIndex *g, unsigned maxDepth, void **t
   }
   uint2 *base = table.as<uint2>();
   u64 *bigAt = big.as<u64>();
-  if (wide) hipLaunchKernelGGL(lengthLettersKernel<true>, dim3(1), dim3(64), 0, 0, g->dev, base, bigAt);
-  else hipLaunchKernelGGL(lengthLettersKernel<false>, dim3(1), dim3(64), 0, 0, g->dev, base, bigAt);
+  if (wide) hipLaunchKernelGGL(lengthLettersKernel<true>, dim3(1), dim3(64), 0, 0, g->image->dev, base, bigAt);
+  else hipLaunchKernelGGL(lengthLettersKernel<false>, dim3(1), dim3(64), 0, 0, g->image->dev, base, bigAt);
   BUILD_TRY(hipGetLastError());
   const u64 resident = (u64)g->numCUs * 8u;
   u64 len = 4;
   for (unsigned d = 1; d < maxDepth; d++, len *= 4u) { /* level d + 1 */
     const u64 outLen = len * 4u;
     uint2 *out = base + awfmLengthTableAt(d + 1u);
-    if (d + 1u == g->dev.seedK && g->dev.seed) {
+    if (d + 1u == g->image->dev.seedK && g->image->dev.seed) {
       const u64 blocks = (outLen + 255u) / 256u;
       const unsigned grid = (unsigned)(blocks < resident ? blocks : resident);
-      if (wide) hipLaunchKernelGGL(lengthFromSeedKernel<true>, dim3(grid), dim3(256), 0, 0, g->dev.seed, outLen, out, bigAt, d + 1u);
-      else hipLaunchKernelGGL(lengthFromSeedKernel<false>, dim3(grid), dim3(256), 0, 0, g->dev.seed, outLen, out, bigAt, d + 1u);
+      if (wide) hipLaunchKernelGGL(lengthFromSeedKernel<true>, dim3(grid), dim3(256), 0, 0, g->image->dev.seed, outLen, out, bigAt, d + 1u);
+      else hipLaunchKernelGGL(lengthFromSeedKernel<false>, dim3(grid), dim3(256), 0, 0, g->image->dev.seed, outLen, out, bigAt, d + 1u);
     } else {
       const u64 blocks = (outLen + kSeedGroupsPerBlock - 1) / kSeedGroupsPerBlock;
       const unsigned grid = (unsigned)(blocks < resident ? blocks : resident);
       const uint2 *parent = (const uint2 *)(base + awfmLengthTableAt(d));
-      if (wide) hipLaunchKernelGGL(lengthLevelKernel<true>, dim3(grid), dim3(kThreads), 0, 0, g->dev, parent, len, outLen, out, bigAt, d + 1u);
-      else hipLaunchKernelGGL(lengthLevelKernel<false>, dim3(grid), dim3(kThreads), 0, 0, g->dev, parent, len, outLen, out, bigAt, d + 1u);
+      if (wide) hipLaunchKernelGGL(lengthLevelKernel<true>, dim3(grid), dim3(kThreads), 0, 0, g->image->dev, parent, len, outLen, out, bigAt, d + 1u);
+      else hipLaunchKernelGGL(lengthLevelKernel<false>, dim3(grid), dim3(kThreads), 0, 0, g->image->dev, parent, len, outLen, out, bigAt, d + 1u);
     }
     BUILD_TRY(hipGetLastError());
   }

@@ -38,20 +38,14 @@ enum AwFmReturnCode awfmGpuIndexSetDenseSa(AwFmGpuIndex *g, int enable) {
     setError("awfmGpuIndexSetDenseSa: null image");
     return AwFmNullPtrError;
   }
-  if (g->shares) {
+  if (g->lane) {
     setError("awfmGpuIndexSetDenseSa: set it on the primary image, not on a lane");
     return AwFmIllegalPositionError;
   }
-  awfmGpuAdoptAccelerators(g, true); /* (whatever is still being built behind the first searches) */
+  awfmGpuAdoptAccelerators(g->image, true); /* (whatever is still being built behind the first searches) */
   DeviceGuard guard(g->device);
-  AwFmGpuLaneLocks lanes(g);
-  std::lock_guard<std::mutex> lock(g->workMutex);
-  const enum AwFmReturnCode rc = applyDenseSa(g, enable != 0);
-  for (AwFmGpuIndex *lane : lanes.lanes) {
-    lane->dDenseSa = g->dDenseSa;
-    lane->denseWide = g->denseWide;
-  }
-  return rc;
+  AwFmGpuExclusive section(g->image);
+  return applyDenseSa(g, enable != 0);
 }
 
 /* the caller holds whatever locks the image needs (none for an image nobody else has a pointer to yet) */
@@ -246,27 +240,27 @@ struct DenseBuilt {
   bool denseWide = false;
   uint64_t denseSaBytes = 0;
 };
-static enum AwFmReturnCode buildDenseSaWide(AwFmGpuIndex *image, bool capped, DenseBuilt *g);
-static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *image, bool capped, DenseBuilt *g);
+static enum AwFmReturnCode buildDenseSaWide(AwFmGpuIndex *g, bool capped, DenseBuilt *out);
+static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *g, bool capped, DenseBuilt *out);
 static enum AwFmReturnCode applyDenseSa(AwFmGpuIndex *g, bool enable, bool capped) {
   (void)awfmGpuSetupSync();
-  if (g->dDenseSa) (void)hipFree(g->dDenseSa);
-  g->dDenseSa = nullptr;
-  g->denseSaBytes = 0;
-  g->denseWide = false;
+  if (g->image->dDenseSa) (void)hipFree(g->image->dDenseSa);
+  g->image->dDenseSa = nullptr;
+  g->image->denseSaBytes = 0;
+  g->image->denseWide = false;
   if (!enable) return AwFmSuccess;
   DenseBuilt built;
   const enum AwFmReturnCode rc = buildDenseSa(g, capped, &built);
-  g->dDenseSa = built.dDenseSa;
-  g->denseWide = built.denseWide;
-  g->denseSaBytes = built.denseSaBytes;
+  g->image->dDenseSa = built.dDenseSa;
+  g->image->denseWide = built.denseWide;
+  g->image->denseSaBytes = built.denseSaBytes;
   return rc;
 }
-/* the construction itself: reads the image (its blocks, its sampled array), writes `g` (what was built) */
-static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *image, bool capped, DenseBuilt *g) {
-  const unsigned long long n = image->dev.bwtLength;
+/* the construction itself: reads the image (its blocks, its sampled array), writes `out` (what was built) */
+static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *g, bool capped, DenseBuilt *out) {
+  const unsigned long long n = g->image->dev.bwtLength;
   /* 32-bit entries for the images that run 32-bit positions, 40-bit ones (DenseSa) for the others */
-  const bool wide = !awfmImageNarrow(image);
+  const bool wide = !awfmImageNarrow(g);
   if (n >= (1ull << 40)) {
     setError("awfmGpuIndexSetDenseSa: 40-bit entries need bwtLength < 2^40");
     return AwFmUnsupportedVersionError;
@@ -284,12 +278,12 @@ static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *image, bool capped, DenseB
         return AwFmSuccess; /* no array: the image locates by walking */
       }
       if (wide) {
-        hipLaunchKernelGGL((packDense40Kernel<unsigned>), dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned *)stash, n, (unsigned *)other);
+        hipLaunchKernelGGL((packDense40Kernel<unsigned>), dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned *)stash, n, (unsigned *)other);
       } else {
         DenseSa from;
         from.words = (const unsigned *)stash;
         from.wide = 1u;
-        hipLaunchKernelGGL(unpackDense40Kernel, dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, from, n, (unsigned *)other);
+        hipLaunchKernelGGL(unpackDense40Kernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, from, n, (unsigned *)other);
       }
       const bool ok = hipGetLastError() == hipSuccess && awfmGpuSetupSync() == hipSuccess;
       (void)hipFree(stash);
@@ -300,12 +294,12 @@ static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *image, bool capped, DenseB
       }
       stash = other;
     }
-    g->dDenseSa = stash;
-    g->denseWide = wide;
-    g->denseSaBytes = awfmDenseSaBytes(n, wide);
+    out->dDenseSa = stash;
+    out->denseWide = wide;
+    out->denseSaBytes = awfmDenseSaBytes(n, wide);
     return AwFmSuccess;
   }
-  if (wide) return buildDenseSaWide(image, capped, g);
+  if (wide) return buildDenseSaWide(g, capped, out);
   unsigned *dense = nullptr;
   unsigned long long *chunkBuf = nullptr, *park = nullptr, *counter = nullptr;
   const unsigned long long chunk = n < (1ull << 28) ? n : (1ull << 28);
@@ -322,7 +316,7 @@ static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *image, bool capped, DenseB
    * runs); `capped` = false now only says what happens when the parked walks cannot be kept: the array that was asked for
    * is then built by walking to the end, the automatic one is dropped */
   const bool explicitBuild = !capped;
-  unsigned stepCap = 32u * image->dev.saRatio;
+  unsigned stepCap = 32u * g->image->dev.saRatio;
   /* the parked walks of the first pass go into a list (narrowParkListKernel) of at most a quarter of the positions, 2^26 at
    * most (0.8 GB; $AWFM_GPU_DIAG park_list = entries, 0 = none: tests): a text that parks more -- one that is mostly runs -- takes
    * the array over all positions and a second pass, as round 4 did for every text that parked anything */
@@ -345,12 +339,12 @@ static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *image, bool capped, DenseB
     for (unsigned long long first = 0; first < n && rc == AwFmSuccess; first += chunk) {
       const unsigned long long count = n - first < chunk ? n - first : chunk;
       hipLaunchKernelGGL(iotaKernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, awfmGpuSetupStream, chunkBuf, first, count);
-      rc = awfmGpuLaunchLocate(image, count, chunkBuf, awfmGpuSetupStream, nullptr, nullptr, stepCap);
+      rc = awfmGpuLaunchLocate(g, count, chunkBuf, awfmGpuSetupStream, nullptr, nullptr, stepCap);
       if (stepCap && listing)
-        hipLaunchKernelGGL(narrowParkListKernel, dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned long long *)chunkBuf,
+        hipLaunchKernelGGL(narrowParkListKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned long long *)chunkBuf,
                            count, first, dense, listAt, listEntry, listCapacity, counter);
       else if (stepCap)
-        hipLaunchKernelGGL(narrowParkKernel, dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned long long *)chunkBuf, count,
+        hipLaunchKernelGGL(narrowParkKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned long long *)chunkBuf, count,
                            dense + first, park ? park + first : (unsigned long long *)nullptr, counter);
       else
         hipLaunchKernelGGL(narrowKernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, awfmGpuSetupStream, chunkBuf, count, dense + first);
@@ -394,10 +388,10 @@ static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *image, bool capped, DenseB
     for (; rc == AwFmSuccess && left != 0 && rounds < 64u; rounds++) {
       if (awfmGpuSetupMemset(counter + 1, 0, 8) != hipSuccess) rc = AwFmGeneralFailure;
       if (listed)
-        hipLaunchKernelGGL(denseSaJumpListKernel, dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, dense, (const unsigned *)listAt, listEntry,
+        hipLaunchKernelGGL(denseSaJumpListKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, dense, (const unsigned *)listAt, listEntry,
                            parked, n, counter + 1);
       else
-        hipLaunchKernelGGL(denseSaJumpKernel, dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, dense, park, n, counter + 1);
+        hipLaunchKernelGGL(denseSaJumpKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, dense, park, n, counter + 1);
       if (hipGetLastError() != hipSuccess || awfmGpuSetupToHost(&left, counter + 1, 8) != hipSuccess) rc = AwFmGeneralFailure;
     }
     if (awfmKnob(AWFM_KNOB_VERBOSE) && parked)
@@ -421,16 +415,16 @@ static enum AwFmReturnCode buildDenseSa(AwFmGpuIndex *image, bool capped, DenseB
     setError("awfmGpuIndexSetDenseSa: construction failed");
     return rc;
   }
-  g->dDenseSa = dense;
-  g->denseSaBytes = n * 4;
+  out->dDenseSa = dense;
+  out->denseSaBytes = n * 4;
   return AwFmSuccess;
 }
 
 /* the construction for images that run 64-bit positions (kernels above): capped walks, the parked ones in a list, pointer
  * jumping, 40-bit entries at the end.  A text that parks more walks than the list holds -- a quarter of its positions, 2^27 at
  * most -- gets no automatic array; one that was asked for is then walked to the end, however long that takes. */
-static enum AwFmReturnCode buildDenseSaWide(AwFmGpuIndex *image, bool capped, DenseBuilt *g) {
-  const unsigned long long n = image->dev.bwtLength;
+static enum AwFmReturnCode buildDenseSaWide(AwFmGpuIndex *g, bool capped, DenseBuilt *out) {
+  const unsigned long long n = g->image->dev.bwtLength;
   const unsigned long long chunk = n < (1ull << 28) ? n : (1ull << 28);
   unsigned long long *dense = nullptr, *chunkBuf = nullptr, *listAt = nullptr;
   ulonglong2 *entry[2] = {nullptr, nullptr};
@@ -454,15 +448,15 @@ static enum AwFmReturnCode buildDenseSaWide(AwFmGpuIndex *image, bool capped, De
   }
   unsigned long long *counter = chunkBuf + chunk; /* two words behind the chunk: parked entries, entries left */
   enum AwFmReturnCode rc = AwFmSuccess;
-  unsigned stepCap = 32u * image->dev.saRatio;
+  unsigned stepCap = 32u * g->image->dev.saRatio;
   auto walkAll = [&]() {
     if (awfmGpuSetupMemset(counter, 0, 16) != hipSuccess) rc = AwFmGeneralFailure;
     for (unsigned long long first = 0; first < n && rc == AwFmSuccess; first += chunk) {
       const unsigned long long count = n - first < chunk ? n - first : chunk;
       hipLaunchKernelGGL(iotaKernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, awfmGpuSetupStream, chunkBuf, first, count);
-      rc = awfmGpuLaunchLocate(image, count, chunkBuf, awfmGpuSetupStream, nullptr, nullptr, stepCap);
+      rc = awfmGpuLaunchLocate(g, count, chunkBuf, awfmGpuSetupStream, nullptr, nullptr, stepCap);
       if (stepCap)
-        hipLaunchKernelGGL(parkWideKernel, dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned long long *)chunkBuf, count, first, dense,
+        hipLaunchKernelGGL(parkWideKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned long long *)chunkBuf, count, first, dense,
                            listAt, entry[0], listCapacity, counter);
       else if (hipMemcpyAsync(dense + first, chunkBuf, count * 8, hipMemcpyDeviceToDevice, awfmGpuSetupStream) != hipSuccess)
         rc = AwFmGeneralFailure;
@@ -486,7 +480,7 @@ static enum AwFmReturnCode buildDenseSaWide(AwFmGpuIndex *image, bool capped, De
   unsigned rounds = 0;
   for (; rc == AwFmSuccess && left != 0 && rounds < 64u; rounds++) {
     if (awfmGpuSetupMemset(counter + 1, 0, 8) != hipSuccess) rc = AwFmGeneralFailure;
-    hipLaunchKernelGGL(denseSaJumpWideKernel, dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, dense, (const unsigned long long *)listAt,
+    hipLaunchKernelGGL(denseSaJumpWideKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, dense, (const unsigned long long *)listAt,
                        (const ulonglong2 *)entry[rounds & 1u], entry[(rounds & 1u) ^ 1u], parked, n, counter + 1);
     if (hipGetLastError() != hipSuccess || awfmGpuSetupToHost(&left, counter + 1, 8) != hipSuccess) rc = AwFmGeneralFailure;
   }
@@ -511,7 +505,7 @@ static enum AwFmReturnCode buildDenseSaWide(AwFmGpuIndex *image, bool capped, De
     return capped ? AwFmSuccess : AwFmAllocationFailure;
   }
   if (rc == AwFmSuccess) {
-    hipLaunchKernelGGL((packDense40Kernel<unsigned long long>), dim3((unsigned)image->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned long long *)dense, n, packed);
+    hipLaunchKernelGGL((packDense40Kernel<unsigned long long>), dim3((unsigned)g->numCUs * 8u), dim3(256), 0, awfmGpuSetupStream, (const unsigned long long *)dense, n, packed);
     if (hipGetLastError() != hipSuccess || awfmGpuSetupSync() != hipSuccess) rc = AwFmGeneralFailure;
   }
   release();
@@ -520,9 +514,9 @@ static enum AwFmReturnCode buildDenseSaWide(AwFmGpuIndex *image, bool capped, De
     setError("awfmGpuIndexSetDenseSa: construction failed");
     return rc;
   }
-  g->dDenseSa = packed;
-  g->denseWide = true;
-  g->denseSaBytes = awfmDenseSaBytes(n, true);
+  out->dDenseSa = packed;
+  out->denseWide = true;
+  out->denseSaBytes = awfmDenseSaBytes(n, true);
   return AwFmSuccess;
 }
 
@@ -543,22 +537,22 @@ enum AwFmReturnCode awfmGpuBuildDenseSaAuto(const AwFmGpuIndex *g, void **arrayO
   bool want = false, automatic = false;
   const char *env = awfmKnob(AWFM_KNOB_DENSE_SA);
   if (env && !strcmp(env, "auto")) { /* the automatic construction whatever the image's size (tests) */
-    want = automatic = g->dev.saRatio > 1u;
+    want = automatic = g->image->dev.saRatio > 1u;
   } else if (env) {
     want = atoi(env) != 0;
-  } else if (g->dev.bwtLength >= (1ull << 26) && g->dev.bwtLength < (1ull << 40) && g->dev.saRatio > 1u) {
+  } else if (g->image->dev.bwtLength >= (1ull << 26) && g->image->dev.bwtLength < (1ull << 40) && g->image->dev.saRatio > 1u) {
     /* (round 5: from 2^26 positions instead of 2^28 -- a Swiss-Prot-sized amino image, 0.8 GB of entries: the LF walk of the
      * few hits of a shard's list was a chain of 130 us, a third of the shard's step) */
     size_t freeBytes = 0, totalBytes = 0;
     DeviceGuard guard(g->device);
     /* (32-bit entries; 40-bit ones, put together in 64-bit entries, for the images that run 64-bit positions: round 6) */
-    const uint64_t entryBytes = awfmImageNarrow(g) ? 4u : (awfmGpuDenseSaStash && awfmGpuDenseSaStashLength == g->dev.bwtLength ? 5u : 8u);
-    if (hipMemGetInfo(&freeBytes, &totalBytes) == hipSuccess) want = freeBytes / (awfmImageNarrow(g) ? 4u : 2u) >= g->dev.bwtLength * entryBytes + (1ull << 31);
+    const uint64_t entryBytes = awfmImageNarrow(g) ? 4u : (awfmGpuDenseSaStash && awfmGpuDenseSaStashLength == g->image->dev.bwtLength ? 5u : 8u);
+    if (hipMemGetInfo(&freeBytes, &totalBytes) == hipSuccess) want = freeBytes / (awfmImageNarrow(g) ? 4u : 2u) >= g->image->dev.bwtLength * entryBytes + (1ull << 31);
     else (void)hipGetLastError();
     if (!want) *notes += "full suffix array: not built (less than 4 x its size free); ";
     automatic = true;
   }
-  if (!want || g->dev.bwtLength >= (1ull << 40)) return AwFmSuccess;
+  if (!want || g->image->dev.bwtLength >= (1ull << 40)) return AwFmSuccess;
   DeviceGuard guard(g->device);
   struct timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
@@ -577,17 +571,17 @@ enum AwFmReturnCode awfmGpuApplyDenseSaAuto(AwFmGpuIndex *g) {
   bool wide = false;
   uint64_t bytes = 0;
   double seconds = 0.0;
-  const enum AwFmReturnCode rc = awfmGpuBuildDenseSaAuto(g, &array, &wide, &bytes, &seconds, &g->accelNotes);
+  const enum AwFmReturnCode rc = awfmGpuBuildDenseSaAuto(g, &array, &wide, &bytes, &seconds, &g->image->accelNotes);
   if (array) {
-    if (g->dDenseSa) (void)hipFree(g->dDenseSa);
-    g->dDenseSa = array;
-    g->denseWide = wide;
-    g->denseSaBytes = bytes;
-    g->denseSaBuildSeconds = seconds;
+    if (g->image->dDenseSa) (void)hipFree(g->image->dDenseSa);
+    g->image->dDenseSa = array;
+    g->image->denseWide = wide;
+    g->image->denseSaBytes = bytes;
+    g->image->denseSaBuildSeconds = seconds;
   }
   return rc;
 }
 extern "C" {
-int awfmGpuIndexHasDenseSa(const AwFmGpuIndex *g) { return g && g->dDenseSa ? 1 : 0; }
-double awfmGpuIndexDenseSaBuildSeconds(const AwFmGpuIndex *g) { return g ? (g->shares ? g->shares : g)->denseSaBuildSeconds : 0.0; }
+int awfmGpuIndexHasDenseSa(const AwFmGpuIndex *g) { return g && g->image->dDenseSa ? 1 : 0; }
+double awfmGpuIndexDenseSaBuildSeconds(const AwFmGpuIndex *g) { return g ? g->image->denseSaBuildSeconds : 0.0; }
 }  // extern "C"

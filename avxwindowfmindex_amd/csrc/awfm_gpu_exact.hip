@@ -14,8 +14,8 @@ hipError_t awfmGpuLaunchExactLookup(const AwFmGpuIndex *g, hipStream_t s, hipEve
                                     bool pairOff, ulonglong2 *rng, unsigned *dCounts, unsigned long long *leftover, unsigned *leftoverCount) {
   /* the superblock bases of the pair image are read from memory, as in mixedLookupSearchKernel: the survivors' slots leave room
    * for 5 workgroups per CU, 12-24 KB of bases in LDS would leave 3 */
-  DevIndex dev = g->dev;
-  dev.lengthBig = (const unsigned long long *)(g->shares ? g->shares : g)->dLengthBig;
+  DevIndex dev = g->image->dev;
+  dev.lengthBig = (const unsigned long long *)g->image->dLengthBig;
   dev.pairSuperInLds = 0u;
   const bool narrow = awfmImageNarrow(g);
   int perCU = 0;

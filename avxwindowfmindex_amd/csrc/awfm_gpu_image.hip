@@ -10,6 +10,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <system_error>
 #include <vector>
 
 #include "awfm_device.h"
@@ -28,13 +29,9 @@ namespace {
 std::mutex tableMutex;
 struct ImageEntry {
   const AwFmIndex *index;
-  int device; /* HIP ordinal the image lives on */
-  int lane;   /* 0 = the image itself; n = the n-th extra handle on it (a device named again in $AWFM_GPU_DEVICES) */
-  AwFmGpuIndex *image;
+  AwFmGpuIndex *handle; /* its device, and its lane: 0 the primary, n the n-th lane on its image (a device named again in $AWFM_GPU_DEVICES) */
 };
 std::vector<ImageEntry> imageTable;
-
-
 
 }  // namespace
 enum AwFmReturnCode awfmGpuEnsureWork(AwFmGpuIndex *g, size_t bytes) {
@@ -51,17 +48,17 @@ enum AwFmReturnCode awfmGpuEnsureWork(AwFmGpuIndex *g, size_t bytes) {
 
 namespace {
 void fillDevIndex(AwFmGpuIndex *g, const struct AwFmIndex *index, unsigned superShift, unsigned long long sentinelPos) {
-  DevIndex &d = g->dev;
-  d.blocks = (const uint4 *)g->dBlocks;
-  d.super = (const unsigned long long *)g->dSuper;
+  DevIndex &d = g->image->dev;
+  d.blocks = (const uint4 *)g->image->dBlocks;
+  d.super = (const unsigned long long *)g->image->dSuper;
   d.numSuper = (unsigned)awfmNumSuper(index->bwtLength, index->config.alphabetType == AwFmAlphabetAmino, superShift);
   d.nucSuperShift = superShift;
-  d.seed = (const ulonglong2 *)g->dSeed;
-  d.sa = (const unsigned long long *)g->dSa;
+  d.seed = (const ulonglong2 *)g->image->dSeed;
+  d.sa = (const unsigned long long *)g->image->dSa;
   d.bwtLength = index->bwtLength;
   d.sentinelPos = sentinelPos;
   d.seedLen = awfmKmerTableLength(index->config.alphabetType, index->config.kmerLengthInSeedTable);
-  d.prefixSums = (const unsigned long long *)g->dPrefix;
+  d.prefixSums = (const unsigned long long *)g->image->dPrefix;
   d.saRatio = index->config.suffixArrayCompressionRatio;
   d.saShift = 0xFFFFFFFFu;
   if ((d.saRatio & (d.saRatio - 1)) == 0) {
@@ -112,34 +109,54 @@ constexpr unsigned kAutoDeepSeedMin = 14, kAutoDeepSeedMax = 16; /* depths of th
 extern "C" {
 static enum AwFmReturnCode applyDeepSeedFromEnv(AwFmGpuIndex *g);
 static enum AwFmReturnCode applyPairFromEnv(AwFmGpuIndex *g);
+static bool startBuilder(AwFmGpuIndex *g);
+}
+
+/* a new image of `index` on `device` and its primary handle; nothing of it is on the device yet */
+static AwFmGpuIndex *newImage(const struct AwFmIndex *index, int device) {
+  AwFmGpuIndex *g = new AwFmGpuIndex();
+  g->image = new AwFmGpuImage();
+  g->image->handles.push_back(g);
+  g->device = device;
+  g->amino = index->config.alphabetType == AwFmAlphabetAmino;
+  g->image->numBlocks = awfmDeviceBlocks(index->bwtLength);
+  return g;
+}
+
+/* The tail of making an image, once its arrays are on the device: the kernels' view, then the optional accelerators -- the pair
+ * image first (the deeper table's next-step bits are computed through it), then the deeper table and the full suffix array, or
+ * (behind) a thread that builds those two behind the first searches.  deepRequired: a deeper table that was asked for and could
+ * not be built fails the image; otherwise it carries on without one, as it does without the others. */
+static enum AwFmReturnCode finishImage(AwFmGpuIndex *g, const struct AwFmIndex *index, unsigned superShift, unsigned long long sentinelPos,
+                                       bool behind, bool deepRequired) {
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, g->device) == hipSuccess && prop.multiProcessorCount > 0)
+    g->numCUs = prop.multiProcessorCount;
+  fillDevIndex(g, index, superShift, sentinelPos);
+  if (const char *env = awfmKnob(AWFM_KNOB_FORCE_WIDE)) g->forceWide = atoi(env) != 0;
+  (void)applyPairFromEnv(g); /* without it (no memory left) searches simply take one step per read */
+  if (behind && startBuilder(g)) return AwFmSuccess;
+  if (applyDeepSeedFromEnv(g) != AwFmSuccess && deepRequired) return AwFmGeneralFailure;
+  (void)awfmGpuApplyDenseSaAuto(g); /* without it (no memory left) a locate walks */
+  return AwFmSuccess;
 }
 
 AwFmGpuIndex *awfmGpuIndexAdopt(const struct AwFmIndex *index, int device, void *dBlocks, void *dSuper, unsigned superShift,
                                 void *dSeed, void *dSa, void *dPrefix, unsigned long long sentinelPos, uint64_t deviceBytes) {
-  AwFmGpuIndex *g = new AwFmGpuIndex();
-  g->device = device;
-  g->amino = index->config.alphabetType == AwFmAlphabetAmino;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-    g->numCUs = prop.multiProcessorCount;
-  g->numBlocks = awfmDeviceBlocks(index->bwtLength);
-  g->dBlocks = dBlocks;
-  g->dSuper = dSuper;
-  g->dSeed = dSeed;
-  g->dSa = dSa;
-  g->dPrefix = dPrefix;
-  g->deviceBytes = deviceBytes;
-  fillDevIndex(g, index, superShift, sentinelPos);
-  if (const char *env = awfmKnob(AWFM_KNOB_FORCE_WIDE)) g->forceWide = atoi(env) != 0;
-  (void)applyPairFromEnv(g);     /* first: the deeper table's next-step bits are computed through the pair image */
-  (void)applyDeepSeedFromEnv(g); /* optional accelerator: on failure the image simply has no deeper table */
-  (void)awfmGpuApplyDenseSaAuto(g);  /* the same: without it a locate walks */
+  AwFmGpuIndex *g = newImage(index, device);
+  g->image->dBlocks = dBlocks;
+  g->image->dSuper = dSuper;
+  g->image->dSeed = dSeed;
+  g->image->dSa = dSa;
+  g->image->dPrefix = dPrefix;
+  g->image->deviceBytes = deviceBytes;
+  (void)finishImage(g, index, superShift, sentinelPos, false, false);
   return g;
 }
 
 void awfmGpuIndexRegister(const struct AwFmIndex *index, AwFmGpuIndex *g) {
   std::lock_guard<std::mutex> lock(tableMutex);
-  imageTable.push_back({index, g->device, 0, g});
+  imageTable.push_back({index, g});
 }
 
 bool awfmGpuRelayout(const void *dRefBlocks, uint64_t bwtLength, bool amino, unsigned superShift, void *dBlocks,
@@ -191,28 +208,51 @@ enum AwFmReturnCode awfmGpuIndexCreate(const struct AwFmIndex *index, int device
 static void accelBuilder(AwFmGpuIndex *g);
 /* images whose builder thread has not been joined yet */
 static std::mutex buildingMutex;
-static std::vector<AwFmGpuIndex *> building;
-static void forgetBuilder(AwFmGpuIndex *g) {
-  std::lock_guard<std::mutex> lock(buildingMutex);
+static std::vector<AwFmGpuImage *> building;
+/* the one place that joins an image's builder thread (it returns when the thread is done) */
+static void joinBuilder(AwFmGpuImage *image) {
+  std::lock_guard<std::mutex> lock(image->joinMutex);
+  if (image->accelThread.joinable()) image->accelThread.join();
+  std::lock_guard<std::mutex> listLock(buildingMutex);
   for (size_t i = 0; i < building.size(); i++)
-    if (building[i] == g) {
+    if (building[i] == image) {
       building[i] = building.back();
       building.pop_back();
       break;
     }
 }
 static void settleBuildersAtExit() {
-  std::vector<AwFmGpuIndex *> left;
-  {
-    std::lock_guard<std::mutex> lock(buildingMutex);
-    left.swap(building);
+  for (;;) {
+    AwFmGpuImage *image = nullptr;
+    {
+      std::lock_guard<std::mutex> lock(buildingMutex);
+      if (building.empty()) return;
+      image = building.back();
+    }
+    joinBuilder(image);
   }
-  for (AwFmGpuIndex *g : left)
-    if (g->accelThread.joinable()) g->accelThread.join();
+}
+/* starts the thread that builds the image's deeper table and full suffix array behind its first searches; false: there is no
+ * thread (the caller builds them itself) */
+static bool startBuilder(AwFmGpuIndex *g) {
+  AwFmGpuImage *image = g->image;
+  image->accelState.store(1);
+  try {
+    image->accelThread = std::thread(accelBuilder, g);
+  } catch (const std::system_error &) {
+    image->accelState.store(0);
+    return false;
+  }
+  /* a program that exits while a builder is at work (no awFmDeallocIndex) must not tear the runtime down under it */
+  std::lock_guard<std::mutex> lock(buildingMutex);
+  static bool hooked = false;
+  if (!hooked) hooked = atexit(settleBuildersAtExit) == 0;
+  building.push_back(image);
+  return true;
 }
 static unsigned chooseDeepSeedK(const AwFmGpuIndex *g, std::string &notes);
-static enum AwFmReturnCode buildDeepSeed(AwFmGpuIndex *g, unsigned deepK, AwFmGpuIndex::PendingAccel *to);
-static void installDeepSeed(AwFmGpuIndex *g, AwFmGpuIndex::PendingAccel *from, const std::vector<AwFmGpuIndex *> &laneList);
+static enum AwFmReturnCode buildDeepSeed(AwFmGpuIndex *g, unsigned deepK, AwFmGpuImage::PendingAccel *to);
+static void installDeepSeed(AwFmGpuImage *image, AwFmGpuImage::PendingAccel *from);
 static enum AwFmReturnCode createImage(const struct AwFmIndex *index, int device, AwFmGpuIndex **out, bool deferAccelerators) {
   if (!index || !out) {
     setError("awfmGpuIndexCreate: null argument");
@@ -247,15 +287,9 @@ static enum AwFmReturnCode createImage(const struct AwFmIndex *index, int device
     return AwFmGeneralFailure;
   }
 
-  AwFmGpuIndex *g = new AwFmGpuIndex();
-  g->device = device;
-  g->amino = amino;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-    g->numCUs = prop.multiProcessorCount;
-  g->numBlocks = awfmDeviceBlocks(index->bwtLength);
+  AwFmGpuIndex *g = newImage(index, device);
   const size_t refBytes = awfmNumBlocks(index->bwtLength) * awfmBlockBytes(index->config.alphabetType);
-  const size_t devBlockBytes = g->numBlocks * awfmDeviceBlockBytes(amino);
+  const size_t devBlockBytes = g->image->numBlocks * awfmDeviceBlockBytes(amino);
   const size_t superBytes = awfmSuperBytes(index->bwtLength, amino, superShift);
   const uint64_t seedLen = awfmKmerTableLength(index->config.alphabetType, index->config.kmerLengthInSeedTable);
   const size_t seedBytes = seedLen * sizeof(struct AwFmSearchRange);
@@ -277,64 +311,48 @@ static enum AwFmReturnCode createImage(const struct AwFmIndex *index, int device
     }                                         \
   } while (0)
 
-  TRY_OR_FAIL(hipMalloc(&g->dBlocks, devBlockBytes), AwFmAllocationFailure);
-  TRY_OR_FAIL(hipMalloc(&g->dSuper, superBytes), AwFmAllocationFailure);
-  TRY_OR_FAIL(hipMalloc(&g->dSeed, seedBytes ? seedBytes : 16), AwFmAllocationFailure);
-  TRY_OR_FAIL(hipMalloc(&g->dSa, saAlloc), AwFmAllocationFailure);
+  TRY_OR_FAIL(hipMalloc(&g->image->dBlocks, devBlockBytes), AwFmAllocationFailure);
+  TRY_OR_FAIL(hipMalloc(&g->image->dSuper, superBytes), AwFmAllocationFailure);
+  TRY_OR_FAIL(hipMalloc(&g->image->dSeed, seedBytes ? seedBytes : 16), AwFmAllocationFailure);
+  TRY_OR_FAIL(hipMalloc(&g->image->dSa, saAlloc), AwFmAllocationFailure);
   TRY_OR_FAIL(hipMalloc(&dRef, refBytes), AwFmAllocationFailure);
-  g->deviceBytes = devBlockBytes + superBytes + seedBytes + saAlloc;
+  g->image->deviceBytes = devBlockBytes + superBytes + seedBytes + saAlloc;
 
   TRY_OR_FAIL(hipMemcpy(dRef, index->bwtBlockList.asNucleotide, refBytes, hipMemcpyHostToDevice), AwFmGeneralFailure);
   unsigned long long sentinelPos = 0;
-  if (!awfmGpuRelayout(dRef, index->bwtLength, amino, superShift, g->dBlocks, g->dSuper, &sentinelPos)) {
+  if (!awfmGpuRelayout(dRef, index->bwtLength, amino, superShift, g->image->dBlocks, g->image->dSuper, &sentinelPos)) {
     (void)hipFree(dRef);
     return fail(AwFmGeneralFailure);
   }
   (void)hipFree(dRef);
   dRef = nullptr;
 
-  TRY_OR_FAIL(hipMemcpy(g->dSeed, index->kmerSeedTable, seedBytes, hipMemcpyHostToDevice), AwFmGeneralFailure);
+  TRY_OR_FAIL(hipMemcpy(g->image->dSeed, index->kmerSeedTable, seedBytes, hipMemcpyHostToDevice), AwFmGeneralFailure);
   {
     unsigned long long prefix[24] = {0};
     memcpy(prefix, index->prefixSums, awfmPrefixSumsLength(index->config.alphabetType) * sizeof(uint64_t));
-    TRY_OR_FAIL(hipMalloc(&g->dPrefix, sizeof prefix), AwFmAllocationFailure);
-    TRY_OR_FAIL(hipMemcpy(g->dPrefix, prefix, sizeof prefix, hipMemcpyHostToDevice), AwFmGeneralFailure);
+    TRY_OR_FAIL(hipMalloc(&g->image->dPrefix, sizeof prefix), AwFmAllocationFailure);
+    TRY_OR_FAIL(hipMemcpy(g->image->dPrefix, prefix, sizeof prefix, hipMemcpyHostToDevice), AwFmGeneralFailure);
   }
 
   /* sampled SA: from memory, or staged from the index file (keepSuffixArrayInMemory == false) */
-  TRY_OR_FAIL(hipMemset(g->dSa, 0, saAlloc), AwFmGeneralFailure);
+  TRY_OR_FAIL(hipMemset(g->image->dSa, 0, saAlloc), AwFmGeneralFailure);
   if (index->suffixArray.values) {
-    TRY_OR_FAIL(hipMemcpy(g->dSa, index->suffixArray.values, saBytes, hipMemcpyHostToDevice), AwFmGeneralFailure);
+    TRY_OR_FAIL(hipMemcpy(g->image->dSa, index->suffixArray.values, saBytes, hipMemcpyHostToDevice), AwFmGeneralFailure);
   } else {
     uint8_t *staged = awfmReadPackedSaFromFile(index);
     if (!staged) {
       setError("awfmGpuIndexCreate: index has no in-memory suffix array and it could not be read from its file");
       return fail(AwFmFileReadFail);
     }
-    hipError_t e = hipMemcpy(g->dSa, staged, saBytes, hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(g->image->dSa, staged, saBytes, hipMemcpyHostToDevice);
     free(staged);
     TRY_OR_FAIL(e, AwFmGeneralFailure);
   }
 #undef TRY_OR_FAIL
 
-  fillDevIndex(g, index, superShift, sentinelPos);
-  if (const char *env = awfmKnob(AWFM_KNOB_FORCE_WIDE)) g->forceWide = atoi(env) != 0;
-  (void)applyPairFromEnv(g); /* without it (no memory left) searches simply take one step per read */
-  if (deferAccelerators) {
-    /* the image is usable now (general kernel from the index's own table, pair steps, LF walk); the deeper table and the full
-     * suffix array are built by a thread of their own, on a stream of their own, and installed between two calls */
-    g->accelState.store(1);
-    g->accelThread = std::thread(accelBuilder, g);
-    { /* a program that exits while a builder is at work (no awFmDeallocIndex) must not tear the runtime down under it */
-      std::lock_guard<std::mutex> lock(buildingMutex);
-      static bool hooked = false;
-      if (!hooked) hooked = atexit(settleBuildersAtExit) == 0;
-      building.push_back(g);
-    }
-  } else {
-    if (applyDeepSeedFromEnv(g) != AwFmSuccess) return fail(AwFmGeneralFailure);
-    (void)awfmGpuApplyDenseSaAuto(g); /* optional accelerator: without it (no memory left) a locate walks */
-  }
+  /* deferAccelerators: usable once the pair image is made (general kernel, pair steps, LF walk), the rest comes behind */
+  if (finishImage(g, index, superShift, sentinelPos, deferAccelerators, true) != AwFmSuccess) return fail(AwFmGeneralFailure);
   *out = g;
   return AwFmSuccess;
 }
@@ -346,7 +364,7 @@ static void accelBuilder(AwFmGpuIndex *g) {
   hipStream_t own = nullptr;
   if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) own = nullptr; /* (the null stream then: correct, not hidden) */
   awfmGpuSetupStream = own;
-  AwFmGpuIndex::PendingAccel &to = g->pendingAccel;
+  AwFmGpuImage::PendingAccel &to = g->image->pendingAccel;
   const unsigned deepK = chooseDeepSeedK(g, to.notes);
   if (deepK != 0 && buildDeepSeed(g, deepK, &to) != AwFmSuccess) to.notes += "deeper table: construction failed; ";
   (void)awfmGpuBuildDenseSaAuto(g, &to.dense, &to.denseWide, &to.denseBytes, &to.denseSeconds, &to.notes);
@@ -354,85 +372,76 @@ static void accelBuilder(AwFmGpuIndex *g) {
   awfmGpuSetupStream = nullptr;
   if (own) (void)hipStreamDestroy(own);
   (void)hipGetLastError();
-  g->accelState.store(2);
+  g->image->accelState.store(2);
 }
 
 }  // extern "C"
-void awfmGpuAdoptAccelerators(AwFmGpuIndex *g, bool wait, const std::vector<AwFmGpuIndex *> *lanesIn) {
-  if (!g || g->shares) return;
-  if (g->accelState.load() == 0) return;
-  if (wait) {
-    if (g->accelThread.joinable()) {
-      g->accelThread.join();
-      forgetBuilder(g);
-    }
-  } else if (g->accelState.load() != 2) {
-    return;
+AwFmGpuExclusive::AwFmGpuExclusive(AwFmGpuImage *image, bool wait) {
+  auto take = [&](std::mutex &m) {
+    if (wait) m.lock();
+    else if (!m.try_lock()) return false;
+    locked.push_back(&m);
+    return true;
+  };
+  if (!take(image->handlesMutex)) return;
+  for (AwFmGpuIndex *h : image->handles)
+    if (!take(h->aosMutex) || !take(h->workMutex) || !take(h->orderMutex)) return;
+  held = true;
+}
+AwFmGpuExclusive::~AwFmGpuExclusive() {
+  while (!locked.empty()) {
+    locked.back()->unlock();
+    locked.pop_back();
   }
-  if (g->accelState.load() != 2) return;
-  std::vector<AwFmGpuIndex *> lanes = lanesIn ? *lanesIn : awfmGpuLanesOf(g);
-  /* nobody is enqueuing a search through the image or one of its lanes while its view changes: all their locks, or (not
-   * waiting) none and another time */
-  std::vector<std::mutex *> want = {&g->aosMutex, &g->workMutex, &g->orderMutex};
-  for (AwFmGpuIndex *lane : lanes) {
-    want.push_back(&lane->aosMutex);
-    want.push_back(&lane->workMutex);
-    want.push_back(&lane->orderMutex);
+}
+
+void awfmGpuAdoptAccelerators(AwFmGpuImage *image, bool wait) {
+  if (image->accelState.load() == 0) return;
+  if (wait) joinBuilder(image);
+  else if (image->accelState.load() != 2) return;
+  AwFmGpuExclusive section(image, wait); /* (not waiting: now or another time) */
+  if (!section.held || image->accelState.load() != 2) return;
+  joinBuilder(image); /* (the thread is done) */
+  AwFmGpuImage::PendingAccel &from = image->pendingAccel;
+  if (from.deepTable) installDeepSeed(image, &from);
+  if (from.dense) {
+    image->dDenseSa = from.dense;
+    image->denseWide = from.denseWide;
+    image->denseSaBytes = from.denseBytes;
+    image->denseSaBuildSeconds = from.denseSeconds;
+    from.dense = nullptr;
   }
-  size_t held = 0;
-  for (; held < want.size(); held++) {
-    if (wait) want[held]->lock();
-    else if (!want[held]->try_lock()) break;
-  }
-  if (held == want.size() && g->accelState.load() == 2) {
-    if (g->accelThread.joinable()) {
-      g->accelThread.join();
-      forgetBuilder(g);
-    }
-    AwFmGpuIndex::PendingAccel &from = g->pendingAccel;
-    if (from.deepTable) installDeepSeed(g, &from, lanes);
-    if (from.dense) {
-      g->dDenseSa = from.dense;
-      g->denseWide = from.denseWide;
-      g->denseSaBytes = from.denseBytes;
-      g->denseSaBuildSeconds = from.denseSeconds;
-      from.dense = nullptr;
-      for (AwFmGpuIndex *lane : lanes) {
-        lane->dDenseSa = g->dDenseSa;
-        lane->denseWide = g->denseWide;
-      }
-    }
-    g->accelNotes += from.notes;
-    from.notes.clear();
-    g->accelState.store(0);
-  }
-  while (held > 0) want[--held]->unlock();
+  image->accelNotes += from.notes;
+  from.notes.clear();
+  image->accelState.store(0);
 }
 extern "C" {
 
+/* a lane's handle goes alone; the primary's takes the image with it (its lanes are gone by then: awfmGpuIndexRelease) */
 void awfmGpuIndexDestroy(AwFmGpuIndex *g) {
   if (!g) return;
-  if (g->accelThread.joinable()) g->accelThread.join();
-  forgetBuilder(g);
+  AwFmGpuImage *image = g->image;
+  if (g->lane) {
+    std::lock_guard<std::mutex> lock(image->handlesMutex);
+    for (size_t i = 0; i < image->handles.size(); i++)
+      if (image->handles[i] == g) {
+        image->handles.erase(image->handles.begin() + (long)i);
+        break;
+      }
+  } else {
+    joinBuilder(image);
+  }
   {
     DeviceGuard guard(g->device);
-    if (g->pendingAccel.deepTable) (void)hipFree(g->pendingAccel.deepTable); /* (built, never installed) */
-    if (g->pendingAccel.deepBig) (void)hipFree(g->pendingAccel.deepBig);
-    if (g->pendingAccel.dense) (void)hipFree(g->pendingAccel.dense);
-    awfmGpuStreamStateFree(g);
-    if (!g->shares) { /* a lane owns only its staging */
-      if (g->dBlocks) (void)hipFree(g->dBlocks);
-      if (g->dSuper) (void)hipFree(g->dSuper);
-      if (g->dSeed) (void)hipFree(g->dSeed);
-      if (g->dSa) (void)hipFree(g->dSa);
-      if (g->dPrefix) (void)hipFree(g->dPrefix);
-      if (g->dDeepSeed) (void)hipFree(g->dDeepSeed);
-      if (g->dDeepBig) (void)hipFree(g->dDeepBig);
-      if (g->dDenseSa) (void)hipFree(g->dDenseSa);
-      if (g->dLengthTable) (void)hipFree(g->dLengthTable);
-      if (g->dLengthBig) (void)hipFree(g->dLengthBig);
-      void *pairOwned[] = {g->dPairBlocks, g->dPairSuper, g->dPairSuper32, g->dPairC};
-      for (void *p : pairOwned)
+    if (!g->lane) {
+      if (image->pendingAccel.deepTable) (void)hipFree(image->pendingAccel.deepTable); /* (built, never installed) */
+      if (image->pendingAccel.deepBig) (void)hipFree(image->pendingAccel.deepBig);
+      if (image->pendingAccel.dense) (void)hipFree(image->pendingAccel.dense);
+      awfmGpuStreamStateFree(image);
+      void *owned[] = {image->dBlocks, image->dSuper, image->dSeed, image->dSa, image->dPrefix, image->dDeepSeed, image->dDeepBig,
+                       image->dDenseSa, image->dLengthTable, image->dLengthBig, image->dPairBlocks, image->dPairSuper,
+                       image->dPairSuper32, image->dPairC};
+      for (void *p : owned)
         if (p) (void)hipFree(p);
     }
     if (g->dWork) (void)hipFree(g->dWork);
@@ -452,6 +461,7 @@ void awfmGpuIndexDestroy(AwFmGpuIndex *g) {
       if (g->pinned[i]) (void)hipHostFree(g->pinned[i]);
     if (g->predict.verdictHost) (void)hipHostFree(g->predict.verdictHost);
   }
+  if (!g->lane) delete image;
   delete g;
 }
 
@@ -478,35 +488,18 @@ static int aosDevices(int *devs, int maxOut) {
   return n;
 }
 
-}  // extern "C"
-/* the lanes of a primary image (call with tableMutex NOT held) */
-std::vector<AwFmGpuIndex *> awfmGpuLanesOf(const AwFmGpuIndex *primary) {
-  std::vector<AwFmGpuIndex *> lanes;
-  std::lock_guard<std::mutex> lock(tableMutex);
-  for (auto &e : imageTable)
-    if (e.image->shares == primary) lanes.push_back(e.image);
-  return lanes;
-}
-
-extern "C" {
-static AwFmGpuIndex *makeLane(AwFmGpuIndex *primary) {
+/* a lane: a new handle on the image of `primary`, with the primary's selections; waits for an exclusive section in progress */
+static AwFmGpuIndex *addLane(AwFmGpuIndex *primary) {
   AwFmGpuIndex *g = new AwFmGpuIndex();
-  g->shares = primary;
+  g->image = primary->image;
   g->device = primary->device;
   g->amino = primary->amino;
-  g->dev = primary->dev;
-  g->dBlocks = primary->dBlocks;
-  g->dSuper = primary->dSuper;
-  g->dSeed = primary->dSeed;
-  g->dSa = primary->dSa;
-  g->dPrefix = primary->dPrefix;
-  g->dDeepSeed = primary->dDeepSeed;
-  g->dDenseSa = primary->dDenseSa;
-  g->denseWide = primary->denseWide;
-  g->numBlocks = primary->numBlocks;
+  g->numCUs = primary->numCUs;
   g->kernel = primary->kernel;
   g->forceWide = primary->forceWide;
-  g->numCUs = primary->numCUs;
+  std::lock_guard<std::mutex> lock(g->image->handlesMutex);
+  g->lane = (int)g->image->handles.size();
+  g->image->handles.push_back(g);
   return g;
 }
 
@@ -523,7 +516,7 @@ int awfmGpuIndexAcquireAll(const struct AwFmIndex *index, AwFmGpuIndex **out, in
   std::lock_guard<std::mutex> lock(tableMutex);
   auto find = [&](int device, int lane) -> AwFmGpuIndex * {
     for (auto &e : imageTable)
-      if (e.index == index && e.device == device && e.lane == lane) return e.image;
+      if (e.index == index && e.handle->device == device && e.handle->lane == lane) return e.handle;
     return nullptr;
   };
   int n = 0;
@@ -535,24 +528,16 @@ int awfmGpuIndexAcquireAll(const struct AwFmIndex *index, AwFmGpuIndex **out, in
       if (lane > 0) { /* a device named again gets a lane on the image it already has */
         AwFmGpuIndex *primary = find(devs[slot], 0);
         if (!primary) return n;
-        g = makeLane(primary);
+        g = addLane(primary);
       } else if (createImage(index, devs[slot], &g, true) != AwFmSuccess) {
         return n;
       }
-      imageTable.push_back({index, devs[slot], lane, g});
+      imageTable.push_back({index, g});
     }
     out[n++] = g;
   }
   /* what the images' builder threads have finished since the last call is installed now, if nobody is inside a search */
-  for (int i = 0; i < n; i++) {
-    AwFmGpuIndex *primary = out[i]->shares ? out[i]->shares : out[i];
-    if (primary->accelState.load() == 2) {
-      std::vector<AwFmGpuIndex *> lanes;
-      for (auto &e : imageTable)
-        if (e.image->shares == primary) lanes.push_back(e.image);
-      awfmGpuAdoptAccelerators(primary, false, &lanes);
-    }
-  }
+  for (int i = 0; i < n; i++) awfmGpuAdoptAccelerators(out[i]->image, false);
   return n;
 }
 
@@ -560,7 +545,7 @@ int awfmGpuIndexAcquireAll(const struct AwFmIndex *index, AwFmGpuIndex **out, in
 AwFmGpuIndex *awfmGpuIndexAcquire(const struct AwFmIndex *index) {
   AwFmGpuIndex *g = nullptr;
   if (awfmGpuIndexAcquireAll(index, &g, 1) != 1) return nullptr;
-  awfmGpuAdoptAccelerators(g->shares ? g->shares : g, true);
+  awfmGpuAdoptAccelerators(g->image, true);
   return g;
 }
 
@@ -570,7 +555,7 @@ void awfmGpuIndexRelease(const struct AwFmIndex *index) {
     std::lock_guard<std::mutex> lock(tableMutex);
     for (size_t i = 0; i < imageTable.size();) {
       if (imageTable[i].index == index) {
-        doomed.push_back(imageTable[i].image);
+        doomed.push_back(imageTable[i].handle);
         imageTable.erase(imageTable.begin() + (long)i);
       } else {
         i++;
@@ -578,9 +563,9 @@ void awfmGpuIndexRelease(const struct AwFmIndex *index) {
     }
   }
   for (AwFmGpuIndex *g : doomed)
-    if (g->shares) awfmGpuIndexDestroy(g); /* lanes first: they point into their primary */
+    if (g->lane) awfmGpuIndexDestroy(g); /* lanes first: their image goes with its primary */
   for (AwFmGpuIndex *g : doomed)
-    if (!g->shares) awfmGpuIndexDestroy(g);
+    if (!g->lane) awfmGpuIndexDestroy(g);
 }
 
 void *awfmGpuPinnedBuffer(AwFmGpuIndex *g, int slot, uint64_t bytes) {
@@ -606,34 +591,33 @@ void awfmGpuAosUnlock(AwFmGpuIndex *g) {
   if (g) g->aosMutex.unlock();
 }
 
-uint64_t awfmGpuIndexDeviceBytes(const AwFmGpuIndex *g) {
-  return g ? g->deviceBytes + g->deepSeedBytes + g->denseSaBytes + g->pairBytes + g->lengthTableBytes : 0;
+static uint64_t imageBytes(const AwFmGpuImage *image) {
+  return image->deviceBytes + image->deepSeedBytes + image->denseSaBytes + image->pairBytes + image->lengthTableBytes;
 }
+uint64_t awfmGpuIndexDeviceBytes(const AwFmGpuIndex *g) { return g && !g->lane ? imageBytes(g->image) : 0; } /* (a lane holds none of it) */
 
-
-/* replaces the deeper table of a primary image and of the given lanes; the caller holds whatever locks the image
- * needs (none for an image nobody else has a pointer to yet) */
-static enum AwFmReturnCode applyDeepSeed(AwFmGpuIndex *g, unsigned deepK, const std::vector<AwFmGpuIndex *> &laneList);
+/* replaces the deeper table of an image; the caller holds whatever locks the image needs (none for an image nobody else has a
+ * pointer to yet) */
+static enum AwFmReturnCode applyDeepSeed(AwFmGpuIndex *g, unsigned deepK);
 
 enum AwFmReturnCode awfmGpuIndexSetDeepSeed(AwFmGpuIndex *g, unsigned deepK) {
   if (!g) {
     setError("awfmGpuIndexSetDeepSeed: null image");
     return AwFmNullPtrError;
   }
-  if (g->shares) {
+  if (g->lane) {
     setError("awfmGpuIndexSetDeepSeed: set it on the primary image, not on a lane");
     return AwFmIllegalPositionError;
   }
-  awfmGpuAdoptAccelerators(g, true);
+  awfmGpuAdoptAccelerators(g->image, true);
   DeviceGuard guard(g->device);
-  AwFmGpuLaneLocks lanes(g); /* nobody searches through a lane while the table is replaced */
-  std::lock_guard<std::mutex> lock(g->workMutex);
-  return applyDeepSeed(g, deepK, lanes.lanes);
+  AwFmGpuExclusive section(g->image); /* nobody searches through the image while the table is replaced */
+  return applyDeepSeed(g, deepK);
 }
 
 /* the deeper table of depth deepK with its next-step bits, built from the image as it is (nothing of the image is written):
  * into `to` */
-static enum AwFmReturnCode buildDeepSeed(AwFmGpuIndex *g, unsigned deepK, AwFmGpuIndex::PendingAccel *to) {
+static enum AwFmReturnCode buildDeepSeed(AwFmGpuIndex *g, unsigned deepK, AwFmGpuImage::PendingAccel *to) {
   void *table = nullptr, *big = nullptr;
   uint64_t bytes = 0, peak = 0;
   unsigned format = 0, numBig = 0;
@@ -653,8 +637,8 @@ static enum AwFmReturnCode buildDeepSeed(AwFmGpuIndex *g, unsigned deepK, AwFmGp
   to->deepBig = big;
   to->deepBytes = bytes;
   to->deepBigBytes = !big ? 0u
-                     : format == 2u ? ((g->dev.bwtLength >> (g->amino ? kAminoWideBigShift : kDeepWideBigShift)) + 2u) * 8u
-                                    : ((g->dev.bwtLength >> (g->amino ? kAminoDeepBigShift : kDeepBigShift)) + 5u) * 4u;
+                     : format == 2u ? ((g->image->dev.bwtLength >> (g->amino ? kAminoWideBigShift : kDeepWideBigShift)) + 2u) * 8u
+                                    : ((g->image->dev.bwtLength >> (g->amino ? kAminoDeepBigShift : kDeepBigShift)) + 5u) * 4u;
   to->deepTransient = peak > bytes ? peak - bytes : 0;
   to->deepK = deepK;
   to->deepFormat = format;
@@ -666,67 +650,57 @@ static enum AwFmReturnCode buildDeepSeed(AwFmGpuIndex *g, unsigned deepK, AwFmGp
             (double)bytes * 1e-9, to->deepSeconds, next > 0 ? "yes" : "no", numBig);
   return AwFmSuccess;
 }
-/* a built table becomes the image's (and its lanes'); the caller holds whatever locks the image needs */
-static void installDeepSeed(AwFmGpuIndex *g, AwFmGpuIndex::PendingAccel *from, const std::vector<AwFmGpuIndex *> &laneList) {
-  g->dDeepSeed = from->deepTable;
-  g->dDeepBig = from->deepBig;
-  g->deepSeedBytes = from->deepBytes + from->deepBigBytes;
-  g->deepSeedBuildSeconds = from->deepSeconds;
-  g->deepSeedAllocSeconds = from->deepAllocSeconds;
-  g->deepSeedTransientBytes = from->deepTransient;
-  g->dev.deepSeed = (const ulonglong2 *)from->deepTable;
-  g->dev.deepNarrow = from->deepFormat;
-  g->dev.deepNext = from->deepNext;
-  g->dev.numDeepBig = from->numDeepBig;
-  g->dev.deepBigBySp = (const unsigned *)from->deepBig;
-  g->dev.deepK = from->deepTable ? from->deepK : 0u;
+/* a built table becomes the image's; the caller holds whatever locks the image needs */
+static void installDeepSeed(AwFmGpuImage *image, AwFmGpuImage::PendingAccel *from) {
+  image->dDeepSeed = from->deepTable;
+  image->dDeepBig = from->deepBig;
+  image->deepSeedBytes = from->deepBytes + from->deepBigBytes;
+  image->deepSeedBuildSeconds = from->deepSeconds;
+  image->deepSeedAllocSeconds = from->deepAllocSeconds;
+  image->deepSeedTransientBytes = from->deepTransient;
+  image->dev.deepSeed = (const ulonglong2 *)from->deepTable;
+  image->dev.deepNarrow = from->deepFormat;
+  image->dev.deepNext = from->deepNext;
+  image->dev.numDeepBig = from->numDeepBig;
+  image->dev.deepBigBySp = (const unsigned *)from->deepBig;
+  image->dev.deepK = from->deepTable ? from->deepK : 0u;
   from->deepTable = from->deepBig = nullptr;
-  for (AwFmGpuIndex *lane : laneList) {
-    lane->dDeepSeed = g->dDeepSeed;
-    lane->dev.deepSeed = g->dev.deepSeed;
-    lane->dev.deepNarrow = g->dev.deepNarrow;
-    lane->dev.deepK = g->dev.deepK;
-    lane->dev.deepNext = g->dev.deepNext;
-    lane->dev.numDeepBig = g->dev.numDeepBig;
-    lane->dev.deepBigBySp = g->dev.deepBigBySp;
-  }
 }
 
-static enum AwFmReturnCode applyDeepSeed(AwFmGpuIndex *g, unsigned deepK, const std::vector<AwFmGpuIndex *> &laneList) {
+static enum AwFmReturnCode applyDeepSeed(AwFmGpuIndex *g, unsigned deepK) {
+  AwFmGpuImage *image = g->image;
   (void)hipDeviceSynchronize();
-  if (g->dDeepSeed) (void)hipFree(g->dDeepSeed);
-  if (g->dDeepBig) (void)hipFree(g->dDeepBig);
+  if (image->dDeepSeed) (void)hipFree(image->dDeepSeed);
+  if (image->dDeepBig) (void)hipFree(image->dDeepBig);
   { /* the tables of the shorter lengths go with the deeper table they complete; the next mixed-length batch builds them again */
-    std::lock_guard<std::mutex> lock(g->lengthMutex);
-    if (g->dLengthTable) (void)hipFree(g->dLengthTable);
-    if (g->dLengthBig) (void)hipFree(g->dLengthBig);
-    g->dLengthTable = nullptr;
-    g->dLengthBig = nullptr;
-    g->lengthDepths = 0;
-    g->lengthTableBytes = 0;
-    g->lengthTried = false;
+    std::lock_guard<std::mutex> lock(image->lengthMutex);
+    if (image->dLengthTable) (void)hipFree(image->dLengthTable);
+    if (image->dLengthBig) (void)hipFree(image->dLengthBig);
+    image->dLengthTable = nullptr;
+    image->dLengthBig = nullptr;
+    image->lengthDepths = 0;
+    image->lengthTableBytes = 0;
+    image->lengthTried = false;
   }
-  AwFmGpuIndex::PendingAccel built; /* (nothing: the image without a deeper table) */
+  AwFmGpuImage::PendingAccel built; /* (nothing: the image without a deeper table) */
   enum AwFmReturnCode rc = AwFmSuccess;
   if (deepK != 0) {
     /* (the construction reads the image's view: without the table that is being replaced) */
-    g->dev.deepSeed = nullptr;
-    g->dev.deepK = 0;
+    image->dev.deepSeed = nullptr;
+    image->dev.deepK = 0;
     rc = buildDeepSeed(g, deepK, &built);
   }
-  installDeepSeed(g, &built, laneList);
+  installDeepSeed(image, &built);
   return rc;
 }
 
-/* $AWFM_GPU_DEEP_SEED_K on an image that was just created or adopted: nobody else holds it and it has no lanes,
- * so no lock is taken -- awfmGpuIndexAcquireAll creates images while it holds the table lock, and the public
- * setter would ask for that lock again through lanesOf() */
+/* $AWFM_GPU_DEEP_SEED_K on an image that was just created or adopted: nobody else holds it, so no lock is taken */
 static unsigned chooseDeepSeedK(const AwFmGpuIndex *g, std::string &notes);
 static enum AwFmReturnCode applyDeepSeedFromEnv(AwFmGpuIndex *g) {
-  const unsigned deepK = chooseDeepSeedK(g, g->accelNotes);
+  const unsigned deepK = chooseDeepSeedK(g, g->image->accelNotes);
   if (deepK == 0) return AwFmSuccess;
   DeviceGuard guard(g->device);
-  return applyDeepSeed(g, deepK, {});
+  return applyDeepSeed(g, deepK);
 }
 /* the depth of the device-only table an image gets by itself ($AWFM_GPU_DEEP_SEED_K / $AWFM_GPU_AMINO_DEEP_SEED_K, else by its size
  * and the memory that is free); 0: none */
@@ -741,17 +715,17 @@ static unsigned chooseDeepSeedK(const AwFmGpuIndex *g, std::string &notes) {
      * 7-mer) and the rest start two steps further on.  Exact: an entry is what the stepping holds after those steps. */
     size_t freeBytes = 0, totalBytes = 0;
     DeviceGuard guard(g->device);
-    if (g->dev.bwtLength >= (1ull << 26) && g->dev.bwtLength < (1ull << kDeepWideMaxBits) && g->dev.seedK >= 2 && hipMemGetInfo(&freeBytes, &totalBytes) == hipSuccess) {
+    if (g->image->dev.bwtLength >= (1ull << 26) && g->image->dev.bwtLength < (1ull << kDeepWideMaxBits) && g->image->dev.seedK >= 2 && hipMemGetInfo(&freeBytes, &totalBytes) == hipSuccess) {
       unsigned long long entries = 1;
       for (unsigned k = 1; k <= 7u; k++) {
         entries *= 20ull;
-        if (k > g->dev.seedK && entries <= 8ull * g->dev.bwtLength && freeBytes / 3u >= entries * 8ull) deepK = (int)k;
-        else if (k > g->dev.seedK && entries <= 8ull * g->dev.bwtLength && k > (unsigned)deepK) notes += "deeper table: depth " + std::to_string(k) + " not built (less than 3 x its size free); ";
+        if (k > g->image->dev.seedK && entries <= 8ull * g->image->dev.bwtLength && freeBytes / 3u >= entries * 8ull) deepK = (int)k;
+        else if (k > g->image->dev.seedK && entries <= 8ull * g->image->dev.bwtLength && k > (unsigned)deepK) notes += "deeper table: depth " + std::to_string(k) + " not built (less than 3 x its size free); ";
       }
     } else {
       (void)hipGetLastError();
     }
-  } else if (g->dev.bwtLength >= (1ull << 28) && g->dev.seedK >= 8 && g->dev.seedK < kAutoDeepSeedMin) {
+  } else if (g->image->dev.bwtLength >= (1ull << 28) && g->image->dev.seedK >= 8 && g->image->dev.seedK < kAutoDeepSeedMin) {
     /* Automatic: an image far beyond the L2s gets the deepest table of 14..16 characters that has no more than two
      * entries per text position, when the device has room to spare (8 B -- 16 B from 2^32 positions -- x 4^K: 2.1 GB
      * at 14, 34 GB at 16; its construction holds the level below beside it; asked for: three times the table).  Every
@@ -762,13 +736,13 @@ static unsigned chooseDeepSeedK(const AwFmGpuIndex *g, std::string &notes) {
     size_t freeBytes = 0, totalBytes = 0;
     DeviceGuard guard(g->device);
     if (hipMemGetInfo(&freeBytes, &totalBytes) == hipSuccess) {
-      const uint64_t entryBytes = g->dev.bwtLength < (1ull << kDeepWideMaxBits) ? 8u : 16u;
+      const uint64_t entryBytes = g->image->dev.bwtLength < (1ull << kDeepWideMaxBits) ? 8u : 16u;
       for (unsigned k = kAutoDeepSeedMax; k >= kAutoDeepSeedMin && deepK == 0; k--)
-        if ((1ull << (2u * k)) <= 2ull * g->dev.bwtLength && freeBytes / 3u >= (entryBytes << (2u * k))) deepK = (int)k;
+        if ((1ull << (2u * k)) <= 2ull * g->image->dev.bwtLength && freeBytes / 3u >= (entryBytes << (2u * k))) deepK = (int)k;
       if (deepK == 0 && freeBytes / 4u >= (16ull << (2u * kAutoDeepSeedMin))) deepK = (int)kAutoDeepSeedMin;
       unsigned wanted = 0; /* the depth the image's size asks for */
       for (unsigned k = kAutoDeepSeedMax; k >= kAutoDeepSeedMin && wanted == 0; k--)
-        if ((1ull << (2u * k)) <= 2ull * g->dev.bwtLength) wanted = k;
+        if ((1ull << (2u * k)) <= 2ull * g->image->dev.bwtLength) wanted = k;
       if ((unsigned)deepK < wanted)
         notes += "deeper table: depth " + std::to_string(wanted) + " not built (less than 3 x its size free)" +
                          (deepK ? ", depth " + std::to_string(deepK) + " instead; " : "; ");
@@ -776,7 +750,7 @@ static unsigned chooseDeepSeedK(const AwFmGpuIndex *g, std::string &notes) {
       (void)hipGetLastError();
     }
   }
-  return deepK <= 0 || (unsigned)deepK <= g->dev.seedK ? 0u : (unsigned)deepK; /* (nothing deeper than the index's own table) */
+  return deepK <= 0 || (unsigned)deepK <= g->image->dev.seedK ? 0u : (unsigned)deepK; /* (nothing deeper than the index's own table) */
 }
 /* Pair image (awfm_pair.h) of a nucleotide image that was just created or adopted (nobody else holds it, no lanes, so
  * no lock): built unless $AWFM_GPU_PAIR=0.  It doubles the block bytes of the image (128 B per 128 positions beside
@@ -789,7 +763,7 @@ static enum AwFmReturnCode applyPairFromEnv(AwFmGpuIndex *g) {
   const enum AwFmReturnCode rc = awfmGpuApplyPairImage(g, true);
   if (rc != AwFmSuccess) {
     (void)awfmGpuApplyPairImage(g, false);
-    g->accelNotes += "pair image: not built (no device memory for 1 byte per position); ";
+    g->image->accelNotes += "pair image: not built (no device memory for 1 byte per position); ";
   }
   return rc;
 }
@@ -799,30 +773,22 @@ enum AwFmReturnCode awfmGpuIndexSetPairImage(AwFmGpuIndex *g, int enable) {
     setError("awfmGpuIndexSetPairImage: null image");
     return AwFmNullPtrError;
   }
-  if (g->shares) {
+  if (g->lane) {
     setError("awfmGpuIndexSetPairImage: set it on the primary image, not on a lane");
     return AwFmIllegalPositionError;
   }
-  awfmGpuAdoptAccelerators(g, true);
+  awfmGpuAdoptAccelerators(g->image, true);
   DeviceGuard guard(g->device);
-  AwFmGpuLaneLocks lanes(g); /* nobody searches through a lane while the image changes */
-  std::lock_guard<std::mutex> lock(g->workMutex);
+  AwFmGpuExclusive section(g->image); /* nobody searches through the image while it changes */
   const enum AwFmReturnCode rc = awfmGpuApplyPairImage(g, enable != 0);
   if (rc != AwFmSuccess) (void)awfmGpuApplyPairImage(g, false);
-  for (AwFmGpuIndex *lane : lanes.lanes) {
-    lane->dev.pairBlocks = g->dev.pairBlocks;
-    lane->dev.pairSuper = g->dev.pairSuper;
-    lane->dev.pairSuper32 = g->dev.pairSuper32;
-    lane->dev.pairC = g->dev.pairC;
-    lane->dev.numPairSuper = g->dev.numPairSuper;
-  }
   return rc;
 }
-int awfmGpuIndexHasPairImage(const AwFmGpuIndex *g) { return g && g->dev.pairBlocks ? 1 : 0; }
-unsigned awfmGpuIndexDeepSeedK(const AwFmGpuIndex *g) { return g ? g->dev.deepK : 0u; }
-double awfmGpuIndexDeepSeedAllocSeconds(const AwFmGpuIndex *g) { return g ? (g->shares ? g->shares : g)->deepSeedAllocSeconds : 0.0; }
-double awfmGpuIndexDeepSeedBuildSeconds(const AwFmGpuIndex *g) { return g ? (g->shares ? g->shares : g)->deepSeedBuildSeconds : 0.0; }
-uint64_t awfmGpuIndexDeepSeedTransientBytes(const AwFmGpuIndex *g) { return g ? (g->shares ? g->shares : g)->deepSeedTransientBytes : 0; }
+int awfmGpuIndexHasPairImage(const AwFmGpuIndex *g) { return g && g->image->dev.pairBlocks ? 1 : 0; }
+unsigned awfmGpuIndexDeepSeedK(const AwFmGpuIndex *g) { return g ? g->image->dev.deepK : 0u; }
+double awfmGpuIndexDeepSeedAllocSeconds(const AwFmGpuIndex *g) { return g ? g->image->deepSeedAllocSeconds : 0.0; }
+double awfmGpuIndexDeepSeedBuildSeconds(const AwFmGpuIndex *g) { return g ? g->image->deepSeedBuildSeconds : 0.0; }
+uint64_t awfmGpuIndexDeepSeedTransientBytes(const AwFmGpuIndex *g) { return g ? g->image->deepSeedTransientBytes : 0; }
 
 int awfmGpuIndexDevice(const AwFmGpuIndex *g) { return g ? g->device : -1; }
 void awfmGpuIndexSetKernel(AwFmGpuIndex *g, enum AwFmGpuKernel kernel) {
@@ -831,23 +797,26 @@ void awfmGpuIndexSetKernel(AwFmGpuIndex *g, enum AwFmGpuKernel kernel) {
 int awfmGpuIndexIsWide(const AwFmGpuIndex *g) { return g && !awfmImageNarrow(g) ? 1 : 0; }
 void awfmGpuIndexSetWide(AwFmGpuIndex *g, int wide) {
   if (!g) return;
-  g->forceWide = wide != 0;
-  if (!g->shares)
-    for (AwFmGpuIndex *lane : awfmGpuLanesOf(g)) lane->forceWide = g->forceWide;
+  if (g->lane) {
+    g->forceWide = wide != 0;
+    return;
+  }
+  std::lock_guard<std::mutex> lock(g->image->handlesMutex); /* the primary's setting reaches its lanes */
+  for (AwFmGpuIndex *h : g->image->handles) h->forceWide = wide != 0;
 }
 
 
 /* see include/awfm_gpu.h */
 int awfmGpuIndexDescribe(const AwFmGpuIndex *g, char *out, int outBytes) {
   if (!g || !out || outBytes <= 0) return 0;
-  const AwFmGpuIndex *p = g->shares ? g->shares : g;
-  std::string text = std::string(p->amino ? "amino" : "nucleotide") + " image of " + std::to_string(p->dev.bwtLength) + " positions, " +
-                     std::to_string(awfmGpuIndexDeviceBytes(p)) + " bytes on device " + std::to_string(p->device) + ": ";
-  if (!p->amino) text += p->dev.pairBlocks ? "pair image yes; " : "pair image no; ";
-  text += p->dev.deepK ? "deeper table depth " + std::to_string(p->dev.deepK) + (p->dev.deepNext ? " with next-step bits; " : "; ") : "deeper table no; ";
-  text += p->dDenseSa ? "full suffix array yes; " : "full suffix array no; ";
-  if (!p->amino) text += p->dLengthTable ? "tables per k-mer length 1.." + std::to_string(p->lengthDepths) + "; " : "tables per k-mer length not built (the first large mixed-length batch builds them); ";
-  if (!p->accelNotes.empty()) text += "notes: " + p->accelNotes;
+  const AwFmGpuImage *image = g->image; /* (a lane reports its image) */
+  std::string text = std::string(g->amino ? "amino" : "nucleotide") + " image of " + std::to_string(image->dev.bwtLength) + " positions, " +
+                     std::to_string(imageBytes(image)) + " bytes on device " + std::to_string(g->device) + ": ";
+  if (!g->amino) text += image->dev.pairBlocks ? "pair image yes; " : "pair image no; ";
+  text += image->dev.deepK ? "deeper table depth " + std::to_string(image->dev.deepK) + (image->dev.deepNext ? " with next-step bits; " : "; ") : "deeper table no; ";
+  text += image->dDenseSa ? "full suffix array yes; " : "full suffix array no; ";
+  if (!g->amino) text += image->dLengthTable ? "tables per k-mer length 1.." + std::to_string(image->lengthDepths) + "; " : "tables per k-mer length not built (the first large mixed-length batch builds them); ";
+  if (!image->accelNotes.empty()) text += "notes: " + image->accelNotes;
   while (!text.empty() && (text.back() == ' ' || text.back() == ';')) text.pop_back();
   const int n = (int)text.size() < outBytes - 1 ? (int)text.size() : outBytes - 1;
   memcpy(out, text.data(), (size_t)n);
@@ -855,7 +824,7 @@ int awfmGpuIndexDescribe(const AwFmGpuIndex *g, char *out, int outBytes) {
   return (int)text.size();
 }
 /* the tables per k-mer length a mixed-length batch builds on first use (awfm_gpu_ordered.hip: ensureLengthTables) */
-uint64_t awfmGpuIndexLengthTableBytes(const AwFmGpuIndex *g) { return g ? (g->shares ? g->shares : g)->lengthTableBytes : 0; }
-double awfmGpuIndexLengthTableBuildSeconds(const AwFmGpuIndex *g) { return g ? (g->shares ? g->shares : g)->lengthTableBuildSeconds : 0.0; }
+uint64_t awfmGpuIndexLengthTableBytes(const AwFmGpuIndex *g) { return g ? g->image->lengthTableBytes : 0; }
+double awfmGpuIndexLengthTableBuildSeconds(const AwFmGpuIndex *g) { return g ? g->image->lengthTableBuildSeconds : 0.0; }
 
 }  // extern "C"

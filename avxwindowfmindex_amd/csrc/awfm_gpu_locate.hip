@@ -538,7 +538,7 @@ enum AwFmReturnCode awfmGpuHitOffsetsFromCounts(AwFmGpuIndex *g, const uint32_t 
     setError("awfmGpuHitOffsetsFromCounts: null argument");
     return AwFmNullPtrError;
   }
-  if (g->dev.bwtLength >= (1ull << 32)) {
+  if (g->image->dev.bwtLength >= (1ull << 32)) {
     setError("awfmGpuHitOffsetsFromCounts: 32-bit counts are exact only for images below 2^32 positions; use awfmGpuHitOffsets");
     return AwFmUnsupportedVersionError;
   }
@@ -613,7 +613,7 @@ enum AwFmReturnCode awfmGpuLocateWindow(AwFmGpuIndex *g, const struct AwFmSearch
   const uint64_t numQueries = queryEnd - queryBegin, totalHits = hitEnd - hitBegin;
   DeviceGuard guard(g->device);
   hipStream_t s = (hipStream_t)stream;
-  if (g->dDenseSa && totalHits < 64ull * numQueries) {
+  if (g->image->dDenseSa && totalHits < 64ull * numQueries) {
     /* the full suffix array: expand and gather in one kernel, straight to where the positions go */
     hipLaunchKernelGGL(expandHitsKernel<true>, dim3(cappedGrid(numQueries)), dim3(256), 0, s,
                        (const ulonglong2 *)dRanges, (const unsigned long long *)dHitOffsets, (unsigned long long)queryBegin,
@@ -622,7 +622,7 @@ enum AwFmReturnCode awfmGpuLocateWindow(AwFmGpuIndex *g, const struct AwFmSearch
     AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
     return AwFmSuccess;
   }
-  if (g->dDenseSa) {
+  if (g->image->dDenseSa) {
     /* long hit lists (64 hits per k-mer and more on average): parallel over the hits (expandLongKernel; the expansion parallel
      * over the k-mers followed by a gather parallel over the hits moved every position three times: 32 against 15 ms for
      * 2 * 10^6 mixed 8..30-mers with 5.5 * 10^9 hits) */
@@ -649,7 +649,7 @@ enum AwFmReturnCode awfmGpuHitOffsetsOnDevice(AwFmGpuIndex *g, const uint32_t *d
     setError("awfmGpuHitOffsetsOnDevice: null argument");
     return AwFmNullPtrError;
   }
-  if (dCounts && g->dev.bwtLength >= (1ull << 32)) {
+  if (dCounts && g->image->dev.bwtLength >= (1ull << 32)) {
     setError("awfmGpuHitOffsetsOnDevice: 32-bit counts are exact only for images below 2^32 positions; pass the ranges");
     return AwFmUnsupportedVersionError;
   }
@@ -670,7 +670,7 @@ enum AwFmReturnCode awfmGpuLocateOnDevice(AwFmGpuIndex *g, const struct AwFmSear
   hipStream_t s = (hipStream_t)stream;
   /* the window [0, capacity) of the hit list: the hits beyond what `dPositions` holds are left out (the caller sees from
    * the total, when it gets to read it, that the buffer was too small) */
-  if (g->dDenseSa) { /* the full suffix array: expand and gather in one kernel */
+  if (g->image->dDenseSa) { /* the full suffix array: expand and gather in one kernel */
     hipLaunchKernelGGL(expandHitsKernel<true>, dim3(cappedGrid(numQueries)), dim3(256), 0, s, (const ulonglong2 *)dRanges,
                        (const unsigned long long *)dHitOffsets, 0ull, (unsigned long long)numQueries, 0ull,
                        (unsigned long long)capacityHits, (unsigned long long *)dPositions, denseSaOf(g));
@@ -728,7 +728,7 @@ enum AwFmReturnCode awfmGpuListLocateOnDevice(AwFmGpuIndex *g, const uint32_t *d
   unsigned grid = capacity / 16u;
   grid = grid < 1u ? 1u : (grid > (unsigned)g->numCUs ? (unsigned)g->numCUs : grid);
   if ((unsigned long long)grid > numQueries) grid = (unsigned)numQueries;
-  if (g->dDenseSa)
+  if (g->image->dDenseSa)
     hipLaunchKernelGGL(listTailKernel<true>, dim3(grid), dim3(kListTailThreads), 0, s, (const unsigned *)dHitKmers, (const ulonglong2 *)dHitRanges,
                        (const unsigned *)dNumHits, (unsigned)capacity, (unsigned long long)numQueries, (unsigned *)dSortedKmers,
                        (ulonglong2 *)dSortedRanges, (unsigned long long *)dHitOffsets, (unsigned long long)capacityHits,
@@ -739,7 +739,7 @@ enum AwFmReturnCode awfmGpuListLocateOnDevice(AwFmGpuIndex *g, const uint32_t *d
                        (ulonglong2 *)dSortedRanges, (unsigned long long *)dHitOffsets, (unsigned long long)capacityHits,
                        (unsigned long long *)dPositions, DenseSa());
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
-  if (g->dDenseSa || capacityHits == 0) return AwFmSuccess;
+  if (g->image->dDenseSa || capacityHits == 0) return AwFmSuccess;
   /* no full suffix array: the kernel left the BWT positions; the LF walk and the sample reads take them from there */
   return awfmGpuLaunchLocate(g, capacityHits, (unsigned long long *)dPositions, s, (unsigned long long *)dPositions,
                       (const unsigned long long *)dHitOffsets + capacity);
@@ -758,18 +758,18 @@ enum AwFmReturnCode awfmGpuLaunchLocate(AwFmGpuIndex *g, unsigned long long tota
     if (g->amino && lanes < 2) lanes = 2;
     unsigned long long *pos = dPositions;
     const unsigned long long th = totalHits;
-    if (g->dev.bwtLength / g->dev.saRatio >= (1ull << 40)) {
+    if (g->image->dev.bwtLength / g->image->dev.saRatio >= (1ull << 40)) {
       setError("awfmGpuLocate: more than 2^40 suffix-array samples are not supported");
       return AwFmUnsupportedVersionError;
     }
-    const bool pow2 = g->dev.saShift != 0xFFFFFFFFu;
+    const bool pow2 = g->image->dev.saShift != 0xFFFFFFFFu;
     const bool narrow = awfmImageNarrow(g);
     /* two LF steps per block read where the image has its pair blocks (awfm_pair.h); their 32-bit superblock bases are
      * dynamic LDS */
-    const bool pair = !g->amino && lanes == 4 && g->dev.pairBlocks;
+    const bool pair = !g->amino && lanes == 4 && g->image->dev.pairBlocks;
     const bool superInLds = pair && narrow && awfmPairSuperInLds(g);
-    const size_t pairLds = superInLds ? (size_t)g->dev.numPairSuper * (kPairSuperStride * 4u) : 0u;
-    DevIndex pairDev = g->dev;
+    const size_t pairLds = superInLds ? (size_t)g->image->dev.numPairSuper * (kPairSuperStride * 4u) : 0u;
+    DevIndex pairDev = g->image->dev;
     pairDev.pairSuperInLds = superInLds ? 1u : 0u;
     /* steps after which an uncapped walk is parked for finishKernel to walk on (the hand-over holds 23 bits of steps);
      * $AWFM_GPU_DIAG walk_give_up: a small number, so that the tests reach that path on ordinary texts */
@@ -789,7 +789,7 @@ enum AwFmReturnCode awfmGpuLaunchLocate(AwFmGpuIndex *g, unsigned long long tota
   } while (0)
 #define AWFM_LOC3(AM, GG, P2, NR)                                                                                  \
   hipLaunchKernelGGL((walkKernel<AM, GG, P2, NR>), dim3(gridFor(th, g, walkKernel<AM, GG, P2, NR>, kThreads / GG)), \
-                     dim3(kThreads), 0, s, g->dev, th, pos, totalOnDevice, stepCap, giveUp)
+                     dim3(kThreads), 0, s, g->image->dev, th, pos, totalOnDevice, stepCap, giveUp)
 #define AWFM_LOC(AM, GG)                                      \
   do {                                                        \
     if (pow2 && narrow) AWFM_LOC3(AM, GG, true, true);        \
@@ -817,7 +817,7 @@ enum AwFmReturnCode awfmGpuLaunchLocate(AwFmGpuIndex *g, unsigned long long tota
     /* out-of-place: the final positions go to `out` (page-locked host memory in the pipeline): a smaller grid, so that
      * a kernel paced by the PCIe writes leaves the chip to whatever runs beside it */
     const unsigned finishGrid = out && out != pos ? (unsigned)g->numCUs * 2u : (unsigned)g->numCUs * 8u;
-    hipLaunchKernelGGL(finishKernel, dim3(finishGrid), dim3(256), 0, s, g->dev, th, (const unsigned long long *)pos, out ? out : pos, totalOnDevice,
+    hipLaunchKernelGGL(finishKernel, dim3(finishGrid), dim3(256), 0, s, g->image->dev, th, (const unsigned long long *)pos, out ? out : pos, totalOnDevice,
                        stepCap ? 0u : (g->amino ? 2u : 1u), giveUp);
   }
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);

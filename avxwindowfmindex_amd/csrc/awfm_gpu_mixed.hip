@@ -13,10 +13,10 @@
 
 namespace {
 /* the image view of a launch: the tables per k-mer length of an image in the wide format come with their long lengths
- * (DevIndex::lengthBig: owned by the primary, set before the table's pointer is published under its mutex) */
+ * (DevIndex::lengthBig: the image's, set before the table's pointer is published under its mutex) */
 DevIndex viewOf(const AwFmGpuIndex *g) {
-  DevIndex dev = g->dev;
-  dev.lengthBig = (const unsigned long long *)(g->shares ? g->shares : g)->dLengthBig;
+  DevIndex dev = g->image->dev;
+  dev.lengthBig = (const unsigned long long *)g->image->dLengthBig;
   return dev;
 }
 }  // namespace
@@ -39,7 +39,7 @@ hipError_t awfmGpuLaunchMixedLookup(const AwFmGpuIndex *g, hipStream_t s, hipEve
   if (!narrow) superInLds = false; /* (the 32-bit copy of the bases is the narrow kernels') */
   DevIndex dev = viewOf(g);
   dev.pairSuperInLds = superInLds ? 1u : 0u;
-  const size_t lds = superInLds ? (size_t)g->dev.numPairSuper * 64u : 0u;
+  const size_t lds = superInLds ? (size_t)g->image->dev.numPairSuper * 64u : 0u;
   SparseOut out;
   out.count = sparseCount;
   out.cap = sparseCap;

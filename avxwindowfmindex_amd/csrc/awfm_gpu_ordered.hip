@@ -53,7 +53,7 @@ unsigned residentGrid(const AwFmGpuIndex *g, Kernel kernel, size_t dynamicLds = 
 }
 
 /* does the image step two characters per block read?  ($AWFM_GPU_PAIR=0 leaves the pair image out altogether) */
-inline bool pairSteps(const AwFmGpuIndex *g) { return g->dev.pairBlocks != nullptr; }
+inline bool pairSteps(const AwFmGpuIndex *g) { return g->image->dev.pairBlocks != nullptr; }
 
 template <bool NARROW, bool VARLEN, bool PAIR = false, bool TOUCH = false, bool BUCKET = false, bool LIST = false>
 enum AwFmReturnCode launchOrderedKernel(AwFmGpuIndex *g, hipStream_t s, uint32_t len, unsigned depth, const ulonglong2 *table,
@@ -64,8 +64,8 @@ enum AwFmReturnCode launchOrderedKernel(AwFmGpuIndex *g, hipStream_t s, uint32_t
   constexpr int G = 4;
   /* dynamic LDS: the 32-bit superblock bases of the pair image (images below 2^32 positions) */
   const bool superInLds = PAIR && NARROW && awfmPairSuperInLds(g);
-  const size_t lds = superInLds ? (size_t)g->dev.numPairSuper * 64u : 0u; /* the 16 pair bases of every superblock */
-  DevIndex dev = g->dev;
+  const size_t lds = superInLds ? (size_t)g->image->dev.numPairSuper * 64u : 0u; /* the 16 pair bases of every superblock */
+  DevIndex dev = g->image->dev;
   dev.pairSuperInLds = superInLds ? 1u : 0u;
   constexpr int threads = orderedThreads(PAIR);
   unsigned grid = residentGrid(g, orderedSearchKernel<G, NARROW, VARLEN, PAIR, TOUCH, BUCKET, LIST>, lds, threads);
@@ -105,7 +105,7 @@ enum AwFmReturnCode launchLeftover(AwFmGpuIndex *g, hipStream_t s, const uint8_t
                                    unsigned indexAt, const unsigned *leftCount, const SparseOut *sparse, bool last = true) {
   const unsigned grid = residentGrid(g, searchKernel<false, 4, CSR, false, NARROW, true>);
   AWFM_LAUNCH_WITH_EVENTS((searchKernel<false, 4, CSR, false, NARROW, true>), dim3(grid), dim3(kThreads), 0u, s, nullptr, last ? g->orderDoneEvent : nullptr,
-                          g->dev, dChars, off, len, nq, rng, dCounts, (unsigned long long *)nullptr, (const unsigned char *)recs, recordBytes,
+                          g->image->dev, dChars, off, len, nq, rng, dCounts, (unsigned long long *)nullptr, (const unsigned char *)recs, recordBytes,
                           indexAt, nq, leftCount, sparse ? *sparse : SparseOut(), (const unsigned *)nullptr, 0u);
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
   if (last) g->orderDoneArmed = g->orderDoneEvent != nullptr;
@@ -162,15 +162,15 @@ enum AwFmReturnCode launchBucketed(AwFmGpuIndex *g, hipStream_t s, const uint8_t
  * depth/table: where the search of a fixed-length batch starts */
 static bool orderedApplies(const AwFmGpuIndex *g, bool hasOffsets, uint32_t fixedLength, unsigned long long nq,
                            unsigned *depthOut, const ulonglong2 **tableOut) {
-  if (g->amino || nq >= 0xFFFFFFFFull || g->dev.seedK == 0 || g->dev.seedK >= 32 || g->dev.deepK >= 32) return false;
+  if (g->amino || nq >= 0xFFFFFFFFull || g->image->dev.seedK == 0 || g->image->dev.seedK >= 32 || g->image->dev.deepK >= 32) return false;
   if (!hasOffsets) {
     if (fixedLength == 0 || fixedLength > 32) return false;
     /* the table the search starts from: the deeper device-only one when it is built and the k-mers reach it */
-    const bool deep = g->dev.deepK != 0 && fixedLength >= g->dev.deepK;
-    const unsigned depth = deep ? g->dev.deepK : g->dev.seedK;
+    const bool deep = g->image->dev.deepK != 0 && fixedLength >= g->image->dev.deepK;
+    const unsigned depth = deep ? g->image->dev.deepK : g->image->dev.seedK;
     if (fixedLength < depth) return false; /* shorter than the seed: the general kernel */
     if (depthOut) *depthOut = depth;
-    if (tableOut) *tableOut = deep ? g->dev.deepSeed : g->dev.seed;
+    if (tableOut) *tableOut = deep ? g->image->dev.deepSeed : g->image->dev.seed;
   }
   int mode = g->orderMode; /* -1 auto, 0 off, 1 on */
   if (mode < 0) {
@@ -181,7 +181,7 @@ static bool orderedApplies(const AwFmGpuIndex *g, bool hasOffsets, uint32_t fixe
      * the general kernel with pair steps, 3.1 Gbp index, random / planted 21-mers (scripts/threshold_probe.sh): 4 M
      * k-mers 0.52 against 0.42 ms / 0.81 against 0.63 ms, 8 M 0.85 against 0.88 / 1.39 against 1.31, 16 M 1.45 against
      * 1.68 / 2.35 against 2.51, 64 M 4.44 against 6.34 / 7.93 against 9.85 */
-    mode = nq >= (1ull << 23) && g->dev.bwtLength >= (1ull << 28);
+    mode = nq >= (1ull << 23) && g->image->dev.bwtLength >= (1ull << 28);
   }
   return mode != 0;
 }
@@ -193,7 +193,7 @@ static bool orderedApplies(const AwFmGpuIndex *g, bool hasOffsets, uint32_t fixe
 int awfmGpuDeepSeedAddNext(AwFmGpuIndex *g, void *table, unsigned deepK, unsigned format, void **bigOut, unsigned *numBigOut) {
   *numBigOut = 0;
   if (!g || !table || format == 0u || deepK == 0) return 0;
-  if (g->amino ? deepK > 7u : (!g->dev.pairBlocks || deepK > 16u)) return 0;
+  if (g->amino ? deepK > 7u : (!g->image->dev.pairBlocks || deepK > 16u)) return 0;
   if (awfmKnob(AWFM_KNOB_DEEP_NEXT) && atoi(awfmKnob(AWFM_KNOB_DEEP_NEXT)) == 0) return 0; /* comparison runs */
   DeviceGuard guard(g->device);
   if (format == 2u) { /* (awfmGpuBuildDeepSeedTable) the table is complete but for its bits; *bigOut holds the long lengths */
@@ -205,7 +205,7 @@ int awfmGpuDeepSeedAddNext(AwFmGpuIndex *g, void *table, unsigned deepK, unsigne
     unsigned numBig = 0;
     bool ok = awfmGpuSetupMemset(dCount, 0, 16) == hipSuccess;
     if (ok) {
-      DevIndex dev = g->dev;
+      DevIndex dev = g->image->dev;
       dev.deepNarrow = 2u;
       dev.deepBigBySp = (const unsigned *)*bigOut;
       dev.pairSuperInLds = 0u;
@@ -231,11 +231,11 @@ int awfmGpuDeepSeedAddNext(AwFmGpuIndex *g, void *table, unsigned deepK, unsigne
     return 1;
   }
   *bigOut = nullptr;
-  if (g->dev.bwtLength >= (1ull << 32)) return 0;
+  if (g->image->dev.bwtLength >= (1ull << 32)) return 0;
   if (g->amino) { /* {sp, length12 | next20 << 12}, the long lengths by sp >> 11 (awfm_device.h) */
     unsigned long long numEntries = 1;
     for (unsigned k = 0; k < deepK; k++) numEntries *= 20ull;
-    const size_t bigWords = (size_t)(g->dev.bwtLength >> kAminoDeepBigShift) + 1u;
+    const size_t bigWords = (size_t)(g->image->dev.bwtLength >> kAminoDeepBigShift) + 1u;
     unsigned *dBig = nullptr;
     if (hipMalloc((void **)&dBig, (bigWords + 4u) * 4u) != hipSuccess) {
       (void)hipGetLastError();
@@ -245,7 +245,7 @@ int awfmGpuDeepSeedAddNext(AwFmGpuIndex *g, void *table, unsigned deepK, unsigne
     bool ok = awfmGpuSetupMemset(dBig, 0, (bigWords + 4u) * 4u) == hipSuccess;
     if (ok) {
       const unsigned grid = residentGrid(g, aminoDeepNextKernel<true>, 0, kThreads);
-      hipLaunchKernelGGL(aminoDeepNextKernel<true>, dim3(grid ? grid : 1u), dim3(kThreads), 0, awfmGpuSetupStream, g->dev, (uint2 *)table, numEntries, dBig, dBig + bigWords);
+      hipLaunchKernelGGL(aminoDeepNextKernel<true>, dim3(grid ? grid : 1u), dim3(kThreads), 0, awfmGpuSetupStream, g->image->dev, (uint2 *)table, numEntries, dBig, dBig + bigWords);
       ok = hipGetLastError() == hipSuccess && awfmGpuSetupSync() == hipSuccess &&
            awfmGpuSetupToHost(&numBig, dBig + bigWords, 4) == hipSuccess;
     }
@@ -262,7 +262,7 @@ int awfmGpuDeepSeedAddNext(AwFmGpuIndex *g, void *table, unsigned deepK, unsigne
   const unsigned long long numEntries = 1ull << (2u * deepK);
   /* the lengths that do not fit the entries' 16 bits, by where their ranges begin (awfm_device.h: deepBigLength), allocated
    * before the in-place rewrite so that it cannot fail half-way; + the word that counts them */
-  const size_t bigWords = (size_t)(g->dev.bwtLength >> kDeepBigShift) + 1u;
+  const size_t bigWords = (size_t)(g->image->dev.bwtLength >> kDeepBigShift) + 1u;
   unsigned *dBig = nullptr;
   if (hipMalloc((void **)&dBig, (bigWords + 4u) * 4u) != hipSuccess) {
     (void)hipGetLastError();
@@ -272,8 +272,8 @@ int awfmGpuDeepSeedAddNext(AwFmGpuIndex *g, void *table, unsigned deepK, unsigne
   unsigned numBig = 0;
   if (ok) {
     const bool superInLds = awfmPairSuperInLds(g);
-    const size_t lds = superInLds ? (size_t)g->dev.numPairSuper * 64u : 0u;
-    DevIndex dev = g->dev;
+    const size_t lds = superInLds ? (size_t)g->image->dev.numPairSuper * 64u : 0u;
+    DevIndex dev = g->image->dev;
     dev.pairSuperInLds = superInLds ? 1u : 0u;
     constexpr int threads = orderedThreads(true);
     unsigned grid = residentGrid(g, deepNextKernel<true>, lds, threads);
@@ -672,7 +672,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
    * hits (results in search order owe an entry to every k-mer).  Its k-mer numbers: 4 bytes per k-mer behind the records;
    * share counts and the sample's count: in the counter block, beyond the ticket counters. */
   const bool narrow = awfmImageNarrow(g);
-  const bool lookupCapable = !packed && !touch && table == g->dev.deepSeed && g->dev.deepNarrow != 0u &&
+  const bool lookupCapable = !packed && !touch && table == g->image->dev.deepSeed && g->image->dev.deepNarrow != 0u &&
                              !(sparse && sparse->kmers && !sparse->count);
   const char *lookupEnv = awfmKnob(AWFM_KNOB_LOOKUP_FIRST); /* 0: never, 1: whenever it applies; unset: by a sample of the batch */
   const bool lookupWanted = lookupCapable && (lookupEnv ? atoi(lookupEnv) != 0 : nq >= (1ull << 20));
@@ -714,7 +714,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
   unsigned encodeGrid = (unsigned)(perShare256 * kShares < (unsigned long long)g->numCUs * 8u ? perShare256 * kShares : (unsigned long long)g->numCUs * 8u);
   encodeGrid = (encodeGrid + kShares - 1u) / kShares * kShares;
   unsigned *shareCount = (unsigned *)(w + kShareCountAt), *numbers = (unsigned *)(w + numbersAt);
-  const unsigned useNext = g->dev.deepNext != 0u && pairSteps(g) && fixedLength >= depth + 2u ? 1u : 0u;
+  const unsigned useNext = g->image->dev.deepNext != 0u && pairSteps(g) && fixedLength >= depth + 2u ? 1u : 0u;
   /* lookup first: forced ($AWFM_GPU_LOOKUP_FIRST=1), or left to a sample of the batch -- 16384 k-mers at a fixed stride; the
    * pass pays when fewer than a quarter of them are alive after the table.  The sample's count stays on the device: both
    * front ends are launched and the one it does not choose returns at once (lookupChosen), so the search never waits
@@ -760,7 +760,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
     static_assert(kSamples == kPredictSamples, "the verdict is judged against the sample's size");
     const unsigned number = predictTag(g, front, fixedLength);
     const unsigned prepGrid = front == kFrontLookupOnly && !(sparse && sparse->count) ? kSamples / 256u : 2u * (kSamples / 256u);
-    hipLaunchKernelGGL(lookupPrepKernel<false>, dim3(prepGrid), dim3(256), 0, s, g->dev, dChars, fixedLength, depth, useNext, nq, kSamples, aliveOut,
+    hipLaunchKernelGGL(lookupPrepKernel<false>, dim3(prepGrid), dim3(256), 0, s, g->image->dev, dChars, fixedLength, depth, useNext, nq, kSamples, aliveOut,
                        aliveNext, zeroA, vecsA, zeroB, vecsB, sparse && sparse->count ? *sparse : SparseOut(), predict.verdictHost, number);
     BUCKET_TRY(hipGetLastError());
     g->orderSlot[g->orderCur].prepParity = 1 - parity;
@@ -799,9 +799,9 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
     {
       const bool pairOff = !pairSteps(g);
       const bool superInLds = !pairOff && narrow && awfmPairSuperInLds(g);
-      DevIndex dev = g->dev;
+      DevIndex dev = g->image->dev;
       dev.pairSuperInLds = superInLds ? 1u : 0u;
-      const size_t lds = superInLds ? (size_t)g->dev.numPairSuper * 64u : 0u;
+      const size_t lds = superInLds ? (size_t)g->image->dev.numPairSuper * 64u : 0u;
       /* persistent grid: what is resident (7 workgroups per CU; the 64-bit instantiation: 80 registers, 6), a multiple of the 8 shares */
       const unsigned perCU = narrow ? 7u : 6u;
       unsigned fusedGrid = (unsigned)(perShare256 * kShares < (unsigned long long)g->numCUs * perCU ? perShare256 * kShares : (unsigned long long)g->numCUs * perCU);
@@ -908,16 +908,16 @@ int awfmGpuOrderedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, 
   return orderedSearch(g, s, dChars, off, fixedLength, nq, rng, dCounts, packed, rangesOfHitsOnly, nullptr, nullptr, nullptr);
 }
 
-/* the tables of the k-mer lengths below the deeper table's, built by the first search that can use them (on the primary
- * image, for its lanes too); nullptr: there are none (no memory, or the image is not one for them) */
+/* the tables of the k-mer lengths below the deeper table's, built by the first search that can use them (for all handles
+ * of the image); nullptr: there are none (no memory, or the image is not one for them) */
 static const uint2 *ensureLengthTables(AwFmGpuIndex *g) {
-  AwFmGpuIndex *p = g->shares ? g->shares : g;
-  const unsigned need = g->dev.deepK - 1u;
-  std::lock_guard<std::mutex> lock(p->lengthMutex);
-  if (p->dLengthTable && p->lengthDepths >= need) return (const uint2 *)p->dLengthTable;
+  AwFmGpuImage *im = g->image;
+  const unsigned need = im->dev.deepK - 1u;
+  std::lock_guard<std::mutex> lock(im->lengthMutex);
+  if (im->dLengthTable && im->lengthDepths >= need) return (const uint2 *)im->dLengthTable;
   /* after a failed attempt the next ones wait: every 64th call tries again (memory may have been freed since) */
-  if (p->lengthTried && (++p->lengthRetryIn & 63u) != 0u) return nullptr;
-  p->lengthTried = true;
+  if (im->lengthTried && (++im->lengthRetryIn & 63u) != 0u) return nullptr;
+  im->lengthTried = true;
   { /* the same headroom rule as the other automatic tables: three times the table free on the device */
     const uint64_t tableBytes = awfmLengthTableAt(need + 1u) * 8ull;
     size_t freeBytes = 0, totalBytes = 0;
@@ -931,19 +931,19 @@ static const uint2 *ensureLengthTables(AwFmGpuIndex *g) {
   void *table = nullptr;
   uint64_t bytes = 0;
   void *big = nullptr;
-  if (!awfmGpuBuildLengthTables(p, need, &table, &bytes, &big)) {
+  if (!awfmGpuBuildLengthTables(g, need, &table, &bytes, &big)) {
     (void)hipGetLastError();
     return nullptr;
   }
   clock_gettime(CLOCK_MONOTONIC, &t1);
-  if (p->dLengthBig) (void)hipFree(p->dLengthBig);
-  p->dLengthBig = big; /* (before the table: whoever finds the table under this mutex finds its long lengths) */
-  p->dLengthTable = table;
-  p->lengthDepths = need;
-  p->lengthTableBytes = bytes;
-  p->lengthTableBuildSeconds = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+  if (im->dLengthBig) (void)hipFree(im->dLengthBig);
+  im->dLengthBig = big; /* (before the table: whoever finds the table under this mutex finds its long lengths) */
+  im->dLengthTable = table;
+  im->lengthDepths = need;
+  im->lengthTableBytes = bytes;
+  im->lengthTableBuildSeconds = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
   if (awfmKnob(AWFM_KNOB_VERBOSE))
-    fprintf(stderr, "[awfm length tables] lengths 1..%u: %.2f GB in %.3f s\n", need, (double)bytes * 1e-9, p->lengthTableBuildSeconds);
+    fprintf(stderr, "[awfm length tables] lengths 1..%u: %.2f GB in %.3f s\n", need, (double)bytes * 1e-9, im->lengthTableBuildSeconds);
   return (const uint2 *)table;
 }
 
@@ -968,8 +968,8 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
    * 18..30-mers: 9.1 against 10.7 ms) */
   constexpr unsigned kSamples = 16384, kChooseOf = 3u * kSamples;
   const char *mixedEnv = awfmKnob(AWFM_KNOB_MIXED_LOOKUP);
-  const bool mixedCapable = off && !touch && !g->amino && g->dev.deepSeed && g->dev.deepNarrow != 0u &&
-                            g->dev.deepK >= 2u && g->dev.deepK <= 16u && g->dev.seedK < g->dev.deepK &&
+  const bool mixedCapable = off && !touch && !g->amino && g->image->dev.deepSeed && g->image->dev.deepNarrow != 0u &&
+                            g->image->dev.deepK >= 2u && g->image->dev.deepK <= 16u && g->image->dev.seedK < g->image->dev.deepK &&
                             !(sparse && sparse->kmers && !sparse->count) /* results in search order owe an entry to every k-mer */;
   const bool mixedForced = mixedCapable && (lookupAlways || (mixedEnv && atoi(mixedEnv) == 1));
   const bool mixedWanted = mixedCapable && (mixedEnv ? atoi(mixedEnv) != 0 : nq >= (1ull << 20)) && (mixedForced || nq >= kSamples);
@@ -1030,7 +1030,7 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
   const unsigned *sampleAlive = nullptr;
   if (bySample) { /* the sample: always taken (the next searches' prediction), consulted on the device when both front ends run */
     const bool pairOff = !pairSteps(g);
-    const unsigned useNext = (g->dev.deepNext != 0u && !pairOff ? 1u : 0u) | (pairOff ? 2u : 0u);
+    const unsigned useNext = (g->image->dev.deepNext != 0u && !pairOff ? 1u : 0u) | (pairOff ? 2u : 0u);
     unsigned *sampleWord = (unsigned *)(w + kSampleAt);
     static_assert(kSamples == kPredictSamples, "the verdict is judged against the sample's size");
     const unsigned number = predictTag(g, front, 0u);
@@ -1039,7 +1039,7 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
   }
   if (lookupRuns) {
     const bool pairOff = !pairSteps(g);
-    unsigned useNext = (g->dev.deepNext != 0u && !pairOff ? 1u : 0u) | (pairOff ? 2u : 0u);
+    unsigned useNext = (g->image->dev.deepNext != 0u && !pairOff ? 1u : 0u) | (pairOff ? 2u : 0u);
     if (wholeCounts) useNext |= 16u;
     /* the superblock bases of the pair image are read from memory: 24 KB of them in LDS (a 3.1 Gbp image) would leave room
      * for 3 workgroups per CU where the survivors' slots alone allow 6 (10^8 8..30-mers: 6.36 against 6.74 ms) */
@@ -1075,7 +1075,7 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
   }
   const unsigned long long encodeTiles = (nq + 255ull) / 256ull;
   const unsigned encodeGrid = (unsigned)(encodeTiles < (unsigned long long)g->numCUs * 8u ? encodeTiles : (unsigned long long)g->numCUs * 8u);
-  const unsigned seedK = g->dev.seedK, deepK = g->dev.deepK;
+  const unsigned seedK = g->image->dev.seedK, deepK = g->image->dev.deepK;
   if (off)
     hipLaunchKernelGGL((encodeRecordsKernel<true>), dim3(encodeGrid), dim3(256), 0, s, dChars, off, fixedLength, depth, seedK, deepK, nq,
                        recsIn, hist, sampleAlive, kChooseOf);
@@ -1133,8 +1133,8 @@ static int orderedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, 
     if (mode < 0)
       if (const char *env = awfmKnob(AWFM_KNOB_ORDERED)) mode = atoi(env) != 0;
     const char *mixedEnv = awfmKnob(AWFM_KNOB_MIXED_LOOKUP);
-    lookupAlways = off && !touch && mode != 0 && !g->amino && nq < 0xFFFFFFFFull && g->dev.deepSeed &&
-                   g->dev.deepNarrow != 0u && g->dev.deepK >= 2u && g->dev.deepK <= 16u && g->dev.seedK < g->dev.deepK &&
+    lookupAlways = off && !touch && mode != 0 && !g->amino && nq < 0xFFFFFFFFull && g->image->dev.deepSeed &&
+                   g->image->dev.deepNarrow != 0u && g->image->dev.deepK >= 2u && g->image->dev.deepK <= 16u && g->image->dev.seedK < g->image->dev.deepK &&
                    !(sparse && sparse->kmers && !sparse->count) && (mixedEnv ? atoi(mixedEnv) != 0 : nq >= (1ull << 20));
     if (!lookupAlways) return 0;
   }
@@ -1198,8 +1198,8 @@ static int aminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
                              ulonglong2 *rng, uint32_t *dCounts, bool rangesOfHitsOnly, const SparseOut *sparse) {
   constexpr unsigned kMaxLength = 19; /* the table's 7 characters + 12 in front of them (5 bits each in one word) */
   const bool narrow = awfmImageNarrow(g);
-  if (!g->amino || g->dev.deepK == 0u || g->dev.deepNarrow != (narrow ? 1u : 2u) || g->dev.deepSeed == nullptr) return 0;
-  if (fixedLength < g->dev.deepK || fixedLength > kMaxLength || fixedLength - g->dev.deepK > 12u || nq >= 0xFFFFFFFFull) return 0;
+  if (!g->amino || g->image->dev.deepK == 0u || g->image->dev.deepNarrow != (narrow ? 1u : 2u) || g->image->dev.deepSeed == nullptr) return 0;
+  if (fixedLength < g->image->dev.deepK || fixedLength > kMaxLength || fixedLength - g->image->dev.deepK > 12u || nq >= 0xFFFFFFFFull) return 0;
   if (!(g->kernel == AWFM_GPU_KERNEL_AUTO || g->kernel == AWFM_GPU_KERNEL_GROUP2)) return 0;
   const char *env = awfmKnob(AWFM_KNOB_AMINO_LOOKUP);
   if (env ? atoi(env) == 0 : nq < (1ull << 20)) return 0;
@@ -1256,8 +1256,8 @@ static int aminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
     unsigned long long *aliveNext = (unsigned long long *)(w + 128u * (unsigned)(1 - parity));
     static_assert(kSamples == kPredictSamples, "the verdict is judged against the sample's size");
     const unsigned number = predictTag(g, front, fixedLength);
-    hipLaunchKernelGGL(lookupPrepKernel<true>, dim3(sparse && sparse->count ? 2u * (kSamples / 256u) : kSamples / 256u), dim3(256), 0, s, g->dev, dChars,
-                       fixedLength, g->dev.deepK, 0u, nq, kSamples, aliveOut, aliveNext, (uint4 *)(w + 64), 64u / 16u, (uint4 *)(w + 256),
+    hipLaunchKernelGGL(lookupPrepKernel<true>, dim3(sparse && sparse->count ? 2u * (kSamples / 256u) : kSamples / 256u), dim3(256), 0, s, g->image->dev, dChars,
+                       fixedLength, g->image->dev.deepK, 0u, nq, kSamples, aliveOut, aliveNext, (uint4 *)(w + 64), 64u / 16u, (uint4 *)(w + 256),
                        (unsigned)(kFusedCounters * 64u / 16u), sparse && sparse->count ? *sparse : SparseOut(), predict.verdictHost, number);
     AMINO_TRY(hipGetLastError());
     g->orderSlot[g->orderCur].prepParity = 1 - parity;
@@ -1284,15 +1284,15 @@ static int aminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
     const unsigned long long rounds = (nq + 1023ull) / 1024ull; /* a workgroup takes 1024 k-mers a round */
     unsigned grid = narrow ? residentGrid(g, aminoLookupSearchKernel<10u, true>) : residentGrid(g, aminoLookupSearchKernel<10u, false>);
     if (rounds < grid) grid = (unsigned)rounds;
-    if (narrow) launchAminoLookupAt<kMaxLength, true>(fixedLength, grid ? grid : 1u, s, g->dev, dChars, nq, sampleAlive, chooseOf, rng, dCounts, out, leftover, leftoverCount, kept);
-    else launchAminoLookupAt<kMaxLength, false>(fixedLength, grid ? grid : 1u, s, g->dev, dChars, nq, sampleAlive, chooseOf, rng, dCounts, out, leftover, leftoverCount, kept);
+    if (narrow) launchAminoLookupAt<kMaxLength, true>(fixedLength, grid ? grid : 1u, s, g->image->dev, dChars, nq, sampleAlive, chooseOf, rng, dCounts, out, leftover, leftoverCount, kept);
+    else launchAminoLookupAt<kMaxLength, false>(fixedLength, grid ? grid : 1u, s, g->image->dev, dChars, nq, sampleAlive, chooseOf, rng, dCounts, out, leftover, leftoverCount, kept);
     AMINO_TRY(hipGetLastError());
   }
   if (generalRuns) { /* the whole batch through the general kernel when the sample says so (it returns at once otherwise) */
 #define AMINO_GENERAL(NR, ...)                                                                                                     \
   do {                                                                                                                             \
     const unsigned grid__ = residentGrid(g, searchKernel<true, 2, false, false, NR, __VA_ARGS__>);                                 \
-    hipLaunchKernelGGL((searchKernel<true, 2, false, false, NR, __VA_ARGS__>), dim3(grid__), dim3(kThreads), 0, s, g->dev, dChars, \
+    hipLaunchKernelGGL((searchKernel<true, 2, false, false, NR, __VA_ARGS__>), dim3(grid__), dim3(kThreads), 0, s, g->image->dev, dChars, \
                        (const unsigned long long *)nullptr, fixedLength, nq, rng, dCounts, (unsigned long long *)nullptr, AMINO_GENERAL_ARGS); \
   } while (0)
 #define AMINO_GENERAL_ARGS (const unsigned char *)nullptr, 0u, 0u, 0ull, (const unsigned *)nullptr, out, sampleAlive, chooseOf
@@ -1328,8 +1328,8 @@ int awfmGpuAminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
  * general kernel's, and the short k-mers of a CSR batch go to it through the list. */
 int awfmGpuExactLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, const unsigned long long *off, uint32_t fixedLength,
                              unsigned long long nq, ulonglong2 *rng, uint32_t *dCounts) {
-  if (g->amino || !g->dev.deepSeed || g->dev.deepNarrow == 0u || g->dev.deepK < 2u || g->dev.deepK > 16u ||
-      g->dev.seedK >= g->dev.deepK || nq >= 0xFFFFFFFFull)
+  if (g->amino || !g->image->dev.deepSeed || g->image->dev.deepNarrow == 0u || g->image->dev.deepK < 2u || g->image->dev.deepK > 16u ||
+      g->image->dev.seedK >= g->image->dev.deepK || nq >= 0xFFFFFFFFull)
     return 0;
   if (!(g->kernel == AWFM_GPU_KERNEL_AUTO || g->kernel == AWFM_GPU_KERNEL_GROUP4)) return 0;
   if (!off && (fixedLength == 0u || fixedLength > 32u)) return 0;
@@ -1337,11 +1337,10 @@ int awfmGpuExactLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
   if (env ? atoi(env) == 0 : nq < (1ull << 18)) return 0;
   const bool forced = env && atoi(env) == 1;
   const uint2 *lengthTable = nullptr;
-  if (off || fixedLength < g->dev.deepK) {
-    AwFmGpuIndex *p = g->shares ? g->shares : g;
+  if (off || fixedLength < g->image->dev.deepK) {
     {
-      std::lock_guard<std::mutex> lock(p->lengthMutex);
-      if (p->dLengthTable && p->lengthDepths >= g->dev.deepK - 1u) lengthTable = (const uint2 *)p->dLengthTable;
+      std::lock_guard<std::mutex> lock(g->image->lengthMutex);
+      if (g->image->dLengthTable && g->image->lengthDepths >= g->image->dev.deepK - 1u) lengthTable = (const uint2 *)g->image->dLengthTable;
     }
     const char *mixedEnv = awfmKnob(AWFM_KNOB_MIXED_LOOKUP);
     /* (awfmGpuSearch allocates nothing by itself: the tables are used when a hits-only mixed-length batch has built them,
@@ -1407,17 +1406,17 @@ extern "C" enum AwFmReturnCode awfmGpuMixedLookupLineTally(AwFmGpuIndex *g, cons
     return AwFmNullPtrError;
   }
   for (int i = 0; i < 8; i++) tallyOut[i] = 0;
-  const bool capable = !g->amino && g->dev.deepSeed && g->dev.deepNarrow == (awfmImageNarrow(g) ? 1u : 2u) && g->dev.deepK >= 2u &&
-                       g->dev.deepK <= 16u && g->dev.seedK < g->dev.deepK;
+  const bool capable = !g->amino && g->image->dev.deepSeed && g->image->dev.deepNarrow == (awfmImageNarrow(g) ? 1u : 2u) && g->image->dev.deepK >= 2u &&
+                       g->image->dev.deepK <= 16u && g->image->dev.seedK < g->image->dev.deepK;
   DeviceGuard guard(g->device);
   const uint2 *lengthTable = capable ? ensureLengthTables(g) : nullptr;
   if (!lengthTable) {
     setError("awfmGpuMixedLookupLineTally: this image has no tables per k-mer length (a nucleotide image with its deeper table in 8-byte entries)");
     return AwFmUnsupportedVersionError;
   }
-  const uint64_t lengthWords = (awfmLengthTableAt(g->dev.deepK) * 8u / 128u + 64u) / 64u;
-  const uint64_t deepWords = ((1ull << (2u * g->dev.deepK)) * 8u / 128u + 64u) / 64u;
-  const uint64_t pairWords = (g->numBlocks + 64u) / 64u, nucWords = (g->numBlocks / 2u + 64u) / 64u;
+  const uint64_t lengthWords = (awfmLengthTableAt(g->image->dev.deepK) * 8u / 128u + 64u) / 64u;
+  const uint64_t deepWords = ((1ull << (2u * g->image->dev.deepK)) * 8u / 128u + 64u) / 64u;
+  const uint64_t pairWords = (g->image->numBlocks + 64u) / 64u, nucWords = (g->image->numBlocks / 2u + 64u) / 64u;
   const unsigned levels = awfmGpuMixedTouchLevels();
   const uint64_t words = lengthWords + deepWords + (uint64_t)levels * (pairWords + nucWords) + 8u;
   unsigned long long *bits = nullptr;
@@ -1430,7 +1429,7 @@ extern "C" enum AwFmReturnCode awfmGpuMixedLookupLineTally(AwFmGpuIndex *g, cons
   unsigned long long *pairLines = bits + lengthWords + deepWords, *nucLines = pairLines + (uint64_t)levels * pairWords;
   unsigned long long *sums = nucLines + (uint64_t)levels * nucWords; /* [0..2] the kernel's counts, [3..6] the four line totals */
   const bool pairOff = !pairSteps(g);
-  const unsigned useNext = (g->dev.deepNext != 0u && !pairOff ? 1u : 0u) | (pairOff ? 2u : 0u);
+  const unsigned useNext = (g->image->dev.deepNext != 0u && !pairOff ? 1u : 0u) | (pairOff ? 2u : 0u);
   hipError_t e = hipMemsetAsync(bits, 0, words * 8u, s);
   unsigned long long host[8] = {0};
   if (e == hipSuccess)
@@ -1475,9 +1474,9 @@ extern "C" enum AwFmReturnCode awfmGpuSearchHitsLineTally(AwFmGpuIndex *g, const
     return AwFmUnsupportedVersionError;
   }
   DeviceGuard guard(g->device);
-  const uint64_t seedWords = (g->dev.seedLen * 16u / 128u + 64u) / 64u;
-  const uint64_t deepWords = g->dev.deepK ? ((1ull << (2u * g->dev.deepK)) * (g->dev.deepNarrow ? 8u : 16u) / 128u + 64u) / 64u : 1u;
-  const uint64_t pairWords = (g->numBlocks + 64u) / 64u, nucWords = (g->numBlocks / 2u + 64u) / 64u;
+  const uint64_t seedWords = (g->image->dev.seedLen * 16u / 128u + 64u) / 64u;
+  const uint64_t deepWords = g->image->dev.deepK ? ((1ull << (2u * g->image->dev.deepK)) * (g->image->dev.deepNarrow ? 8u : 16u) / 128u + 64u) / 64u : 1u;
+  const uint64_t pairWords = (g->image->numBlocks + 64u) / 64u, nucWords = (g->image->numBlocks / 2u + 64u) / 64u;
   const uint64_t words = seedWords + deepWords + (uint64_t)kTouchLevels * (pairWords + nucWords) + 8u;
   unsigned long long *bits = nullptr;
   if (hipMalloc((void **)&bits, words * 8u) != hipSuccess) {
@@ -1630,15 +1629,15 @@ extern "C" enum AwFmReturnCode awfmGpuSearchHitsInOrderCounts(AwFmGpuIndex *g, c
 static bool shardedFormat(const AwFmGpuIndex *g, uint32_t fixedLength, uint64_t totalQueries, unsigned *depthOut, const ulonglong2 **tableOut,
                           BucketFormat *fmtOut) {
   if (g->amino || !(g->kernel == AWFM_GPU_KERNEL_AUTO || g->kernel == AWFM_GPU_KERNEL_GROUP4)) return false;
-  if (totalQueries == 0 || totalQueries >= 0xFFFFFFFFull || g->dev.seedK == 0 || g->dev.seedK >= 32 || g->dev.deepK >= 32) return false;
+  if (totalQueries == 0 || totalQueries >= 0xFFFFFFFFull || g->image->dev.seedK == 0 || g->image->dev.seedK >= 32 || g->image->dev.deepK >= 32) return false;
   if (fixedLength == 0 || fixedLength > 32) return false;
-  const bool deep = g->dev.deepK != 0 && fixedLength >= g->dev.deepK;
-  const unsigned depth = deep ? g->dev.deepK : g->dev.seedK;
+  const bool deep = g->image->dev.deepK != 0 && fixedLength >= g->image->dev.deepK;
+  const unsigned depth = deep ? g->image->dev.deepK : g->image->dev.seedK;
   if (fixedLength < depth) return false;
   const BucketFormat fmt = bucketFormat(depth, totalQueries);
   if (!bucketFits(fixedLength, fmt)) return false;
   *depthOut = depth;
-  *tableOut = deep ? g->dev.deepSeed : g->dev.seed;
+  *tableOut = deep ? g->image->dev.deepSeed : g->image->dev.seed;
   *fmtOut = fmt;
   return true;
 }
@@ -1861,11 +1860,11 @@ extern "C" enum AwFmReturnCode awfmGpuSearchGeneralRecords(AwFmGpuIndex *g, cons
   const bool narrow = awfmImageNarrow(g);
   const unsigned grid = narrow ? residentGrid(g, searchKernel<false, 4, false, false, true, true>) : residentGrid(g, searchKernel<false, 4, false, false, false, true>);
   if (narrow)
-    hipLaunchKernelGGL((searchKernel<false, 4, false, false, true, true>), dim3(grid), dim3(kThreads), 0, s, g->dev, base, (const unsigned long long *)nullptr, fixedLength,
+    hipLaunchKernelGGL((searchKernel<false, 4, false, false, true, true>), dim3(grid), dim3(kThreads), 0, s, g->image->dev, base, (const unsigned long long *)nullptr, fixedLength,
                        (unsigned long long)(firstNumber + numQueries), (ulonglong2 *)nullptr, (unsigned *)nullptr, (unsigned long long *)nullptr,
                        (const unsigned char *)dRecords, 8u, 0u, (unsigned long long)numQueries, leftCount, out, (const unsigned *)nullptr, 0u);
   else
-    hipLaunchKernelGGL((searchKernel<false, 4, false, false, false, true>), dim3(grid), dim3(kThreads), 0, s, g->dev, base, (const unsigned long long *)nullptr, fixedLength,
+    hipLaunchKernelGGL((searchKernel<false, 4, false, false, false, true>), dim3(grid), dim3(kThreads), 0, s, g->image->dev, base, (const unsigned long long *)nullptr, fixedLength,
                        (unsigned long long)(firstNumber + numQueries), (ulonglong2 *)nullptr, (unsigned *)nullptr, (unsigned long long *)nullptr,
                        (const unsigned char *)dRecords, 8u, 0u, (unsigned long long)numQueries, leftCount, out, (const unsigned *)nullptr, 0u);
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);

@@ -165,20 +165,20 @@ __global__ void pairStartKernel(const DevIndex ix, u64 *__restrict__ pairC) {
 
 enum AwFmReturnCode awfmGpuApplyPairImage(AwFmGpuIndex *g, bool enable) {
   (void)hipDeviceSynchronize();
-  void **owned[] = {&g->dPairBlocks, &g->dPairSuper, &g->dPairSuper32, &g->dPairC};
+  void **owned[] = {&g->image->dPairBlocks, &g->image->dPairSuper, &g->image->dPairSuper32, &g->image->dPairC};
   /* pairSuper / pairSuper32: kPairSuperStride = 20 words per superblock (16 pairs, then the 4 letters) */
   for (void **p : owned) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  g->pairBytes = 0;
-  g->dev.pairBlocks = nullptr;
-  g->dev.pairSuper = nullptr;
-  g->dev.pairSuper32 = nullptr;
-  g->dev.pairC = nullptr;
-  g->dev.numPairSuper = 0;
+  g->image->pairBytes = 0;
+  g->image->dev.pairBlocks = nullptr;
+  g->image->dev.pairSuper = nullptr;
+  g->image->dev.pairSuper32 = nullptr;
+  g->image->dev.pairC = nullptr;
+  g->image->dev.numPairSuper = 0;
   if (!enable || g->amino) return AwFmSuccess;
-  const u64 n = g->dev.bwtLength;
+  const u64 n = g->image->dev.bwtLength;
   const u64 numBlocks = (n + kBlockMask) >> kBlockShift;
   const u64 numSuper = ((n - 1ull) >> kPairSuperShift) + 1ull;
   if (numSuper > (1ull << 20)) {
@@ -204,10 +204,10 @@ enum AwFmReturnCode awfmGpuApplyPairImage(AwFmGpuIndex *g, bool enable) {
   if ((e = hipMalloc((void **)&pairC, 128)) != hipSuccess) return fail("pair image: starts", e);
   const u64 halves = numBlocks * 2ull;
   const unsigned codesGrid = (unsigned)((halves + 3ull) / 4ull < (u64)g->numCUs * 32ull ? (halves + 3ull) / 4ull : (u64)g->numCUs * 32ull);
-  hipLaunchKernelGGL(pairCodesKernel, dim3(codesGrid ? codesGrid : 1u), dim3(256), 0, 0, g->dev, blocks, hist);
+  hipLaunchKernelGGL(pairCodesKernel, dim3(codesGrid ? codesGrid : 1u), dim3(256), 0, 0, g->image->dev, blocks, hist);
   /* (the letters' counts include the positions of flagged blocks: they are counted from L itself) */
   hipLaunchKernelGGL(pairCountsKernel, dim3((unsigned)numSuper), dim3(256), 0, 0, (const uint4 *)hist, numBlocks, blocks, totals);
-  hipLaunchKernelGGL(pairStartKernel, dim3(1), dim3(64), 0, 0, g->dev, pairC);
+  hipLaunchKernelGGL(pairStartKernel, dim3(1), dim3(64), 0, 0, g->image->dev, pairC);
   if ((e = hipGetLastError()) != hipSuccess) return fail("pair image: launch", e);
   const u64 words = numSuper * kPairSuperStride;
   std::vector<u64> host(words), bases(words);
@@ -225,15 +225,15 @@ enum AwFmReturnCode awfmGpuApplyPairImage(AwFmGpuIndex *g, bool enable) {
   if ((e = hipMemcpy(super32, bases32.data(), words * 4ull, hipMemcpyHostToDevice)) != hipSuccess) return fail("pair image: bases", e);
   (void)hipFree(hist);
   (void)hipFree(totals);
-  g->dPairBlocks = blocks;
-  g->dPairSuper = super;
-  g->dPairSuper32 = super32;
-  g->dPairC = pairC;
-  g->pairBytes = numBlocks * 128ull + numSuper * kPairSuperStride * 12ull + 128ull;
-  g->dev.pairBlocks = blocks;
-  g->dev.pairSuper = super;
-  g->dev.pairSuper32 = super32;
-  g->dev.pairC = pairC;
-  g->dev.numPairSuper = (unsigned)numSuper;
+  g->image->dPairBlocks = blocks;
+  g->image->dPairSuper = super;
+  g->image->dPairSuper32 = super32;
+  g->image->dPairC = pairC;
+  g->image->pairBytes = numBlocks * 128ull + numSuper * kPairSuperStride * 12ull + 128ull;
+  g->image->dev.pairBlocks = blocks;
+  g->image->dev.pairSuper = super;
+  g->image->dev.pairSuper32 = super32;
+  g->image->dev.pairC = pairC;
+  g->image->dev.numPairSuper = (unsigned)numSuper;
   return AwFmSuccess;
 }

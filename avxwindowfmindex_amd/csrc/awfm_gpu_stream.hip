@@ -293,18 +293,18 @@ bool isPinned(const void *p) {
 
 }  // namespace
 
-void awfmGpuStreamStateFree(AwFmGpuIndex *g) {
-  if (!g || !g->streamState) return;
-  AwFmGpuStreamState &state = *g->streamState;
+void awfmGpuStreamStateFree(AwFmGpuImage *image) {
+  if (!image->streamState) return;
+  AwFmGpuStreamState &state = *image->streamState;
   hipStream_t streams[] = {state.slotStream[0], state.slotStream[1], state.slotStream[2]};
   for (hipStream_t s : streams)
     if (s) {
       (void)hipStreamSynchronize(s);
       (void)hipStreamDestroy(s);
     }
-  for (StreamSlot &s : g->streamState->slot) freeSlot(s);
-  delete g->streamState;
-  g->streamState = nullptr;
+  for (StreamSlot &s : state.slot) freeSlot(s);
+  delete image->streamState;
+  image->streamState = nullptr;
 }
 
 extern "C" {
@@ -451,15 +451,18 @@ static enum AwFmReturnCode streamBatch(AwFmGpuIndex *g, const void *input, int p
     return AwFmIllegalPositionError;
   }
   if (numKmers == 0) return AwFmSuccess;
-  if (g->shares) g = g->shares; /* lanes have no pipeline of their own */
+  { /* the pipeline is the image's, run on its primary handle */
+    std::lock_guard<std::mutex> lock(g->image->handlesMutex);
+    g = g->image->handles[0];
+  }
   if (chunkKmers == 0) chunkKmers = 1ull << 24;
   if (chunkKmers > numKmers) chunkKmers = numKmers;
   if (chunkKmers >= 0xFFFFFFFFull) chunkKmers = 0xFFFFFFFEull;
   if (hostThreads == 0) hostThreads = 4;
   DeviceGuard guard(g->device);
-  std::lock_guard<std::mutex> lock(g->streamMutex);
-  if (!g->streamState) g->streamState = new AwFmGpuStreamState();
-  AwFmGpuStreamState &st = *g->streamState;
+  std::lock_guard<std::mutex> lock(g->image->streamMutex);
+  if (!g->image->streamState) g->image->streamState = new AwFmGpuStreamState();
+  AwFmGpuStreamState &st = *g->image->streamState;
   StreamSlot *slots = st.slot;
   if (!st.streamsReady) {
     /* all three streams or none: a later failure must not leave a guard satisfied with null streams behind it */
@@ -482,7 +485,7 @@ static enum AwFmReturnCode streamBatch(AwFmGpuIndex *g, const void *input, int p
    * 23-25; retired in round 6) */
   const size_t inBytesPerKmer = packed ? 8 : kmerLength;
   const bool stage = !isPinned(input);
-  const bool narrowCounts = g->dev.bwtLength < (1ull << 32);
+  const bool narrowCounts = g->image->dev.bwtLength < (1ull << 32);
   const u64 hitBudget = awfmGpuHitBudget(g);
   bool denseList = false; /* sparse results: a chunk's list overflowed, so the batch is not sparse: lists out of dense results from now on */
   const u64 numChunks = (numKmers + chunkKmers - 1) / chunkKmers;

@@ -310,3 +310,78 @@ def test_accelerators_built_behind_the_first_searches(oracle, awfm, require_gpu,
     for job in jobs:
         job["list"].dealloc()
     ix.dealloc()
+
+
+def test_searches_acquires_and_setters_race_on_a_fresh_image(oracle, awfm, require_gpu, monkeypatch):
+    """Drop-in searches, explicit acquires and the setters, all started at once on an index that has no device image yet: the
+    image's builder thread is joined by whoever comes first (awfm_gpu_image.hip: joinBuilder, one place), and every change of
+    the image's view -- installing what the builder made, replacing the deeper table, dropping and making the full suffix
+    array -- holds the locks of all its handles in one order (AwFmGpuExclusive) while three lanes search.  Every round of
+    every search must give the oracle's counts and positions, every thread must come back, and the image must end with what
+    the setters set last."""
+    monkeypatch.setenv("AWFM_GPU_DEVICES", "0,0,0")
+    monkeypatch.setenv("AWFM_GPU_DEEP_SEED_K", "11")
+    monkeypatch.setenv("AWFM_GPU_DENSE_SA", "auto")
+    txt = synth.text(481, 900_000).copy()
+    txt[2000:2100] = ord("n")
+    ix = awfm.create_index(txt, awfm.AwFmAlphabetDna, 8, 8)  # no device image yet
+    oi = oracle.Index.wrap(oracle.DNA, 8, 8, ix.bwt_length, ix.blocks(), ix.prefix_sums(), ix.seed_table(), ix.packed_sa())
+    n, rounds = 30011, 8
+    searches = []
+    for t in range(3):
+        q = np.concatenate([synth.random_queries(490 + t, n // 2, 19), synth.planted_queries(495 + t, n - n // 2, 19, txt)])
+        kmers = [bytes(r) for r in q]
+        sp, ep, cnt, _ = oi.search_list(kmers)
+        hit_off, pos, _ = oi.batch_locate(sp, ep)
+        lst = awfm.KmerSearchList(n)
+        lst.fill(kmers)
+        searches.append({"cnt": cnt, "hit_off": hit_off, "pos": pos, "list": lst})
+    start = threading.Barrier(7)
+    errors, done = [], []
+
+    def search(job):
+        for r in range(rounds):
+            rc = awfm.parallel_search_locate(ix, job["list"], 2)
+            if rc != awfm.AwFmSuccess:
+                raise AssertionError(f"round {r}: awFmParallelSearchLocate returned {rc}")
+            if not np.array_equal(job["list"].counts(), job["cnt"]):
+                raise AssertionError(f"round {r}: counts differ from the oracle")
+            for i in range(0, n, 37):
+                if not np.array_equal(job["list"].positions(i), job["pos"][int(job["hit_off"][i]):int(job["hit_off"][i + 1])]):
+                    raise AssertionError(f"round {r}: positions of k-mer {i} differ from the oracle")
+
+    def acquire():
+        for _ in range(3):
+            awfm.GpuIndex(ix, acquire=True).handle = None
+
+    def toggle(setter, first, last):
+        g = awfm.GpuIndex(ix, acquire=True)
+        for _ in range(3):
+            getattr(g, setter)(first)
+            getattr(g, setter)(last)
+        g.handle = None
+
+    def run(name, fn, *args):
+        try:
+            start.wait(120)
+            fn(*args)
+            done.append(name)
+        except Exception as e:  # noqa: BLE001  (reported by the main thread)
+            errors.append(f"{name}: {e!r}")
+
+    work = [(f"search {t}", search, searches[t]) for t in range(3)] + [(f"acquire {a}", acquire) for a in range(2)]
+    work += [("set_deep_seed", toggle, "set_deep_seed", 0, 11), ("set_dense_sa", toggle, "set_dense_sa", False, True)]
+    threads = [threading.Thread(target=run, args=w, daemon=True) for w in work]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(600)
+    assert not any(t.is_alive() for t in threads), f"a caller did not come back (done: {done})"
+    assert not errors, errors
+    assert len(done) == len(work)
+    g = awfm.GpuIndex(ix, acquire=True)
+    assert g.deep_seed_k == 11 and g.has_dense_sa, g.describe()
+    g.handle = None
+    for job in searches:
+        job["list"].dealloc()
+    ix.dealloc()
