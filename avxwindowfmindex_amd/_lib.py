@@ -11,6 +11,7 @@ AwFmAlphabetAmino, AwFmAlphabetDna, AwFmAlphabetRna = 1, 2, 3
 AwFmSuccess, AwFmFileReadOkay, AwFmFileWriteOkay = 1, 2, 3
 AwFmGeneralFailure = -1
 AwFmIllegalPositionError = -6
+AwFmUnsupportedVersionError = -2
 AwFmFileReadFail = -11
 
 # every symbol the two public headers declare
@@ -38,6 +39,7 @@ GPU_SYMBOLS = [
     "awfmGpuStreamPackedSparse", "awfmGpuStreamCharsSparse", "awfmGpuSearchHitsInOrder", "awfmGpuSearchHitsInOrderCounts",
     "awfmGpuSortHitsOnDevice", "awfmGpuHitOffsetsOnDevice", "awfmGpuLocateOnDevice", "awfmGpuLastOrderedSearchKernelMs", "awfmGpuOrderedKernelLog", "awfmGpuIndexDeepSeedBuildSeconds", "awfmGpuIndexDeepSeedTransientBytes", "awfmGpuIndexHasDenseSa", "awfmGpuIndexDenseSaBuildSeconds", "awfmGpuIndexLengthTableBytes", "awfmGpuIndexLengthTableBuildSeconds", "awfmGpuMixedLookupLineTally",
     "awfmGpuListLocateOnDevice", "awfmGpuLastLookupFront", "awfmGpuLastSearchWasExactLookup", "awfmGpuSynthPlantedQueriesUnique", "awfmGpuStreamRetire", "awfmGpuIndexDescribe", "awfmGpuIndexDeepSeedAllocSeconds", "awfmGpuAosLastStages", "awfmHostCopyGBs",
+    "awfmLocalPositions", "awfmGpuIndexSetRecordTable", "awfmGpuIndexNumRecords", "awfmGpuLocalPositions", "awfmGpuLocateHostLocal",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -201,6 +203,12 @@ def lib():
         "awfmGpuLocateHostWindows": (C.c_int, [vp, vp, vp, C.c_uint32, u64, vp, vp, HIT_WINDOW_SINK, vp]),
         "awfmGpuCountHost": (C.c_int, [vp, vp, vp, C.c_uint32, u64, vp, vp]),
         "awfmGpuLocateHost": (C.c_int, [vp, vp, vp, C.c_uint32, u64, vp, vp, C.POINTER(C.POINTER(u64))]),
+        "awfmLocalPositions": (C.c_int, [IP, vp, u64, vp, vp, C.POINTER(u64), C.c_uint]),
+        "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),
+        "awfmGpuIndexNumRecords": (C.c_uint32, [vp]),
+        "awfmGpuLocalPositions": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),
+        "awfmGpuLocateHostLocal": (C.c_int, [vp, vp, vp, C.c_uint32, u64, vp, vp, C.POINTER(C.POINTER(C.c_uint32)),
+                                             C.POINTER(C.POINTER(u64)), C.POINTER(u64)]),
         "awfmGpuCreateIndex": (C.c_int, [C.POINTER(IP), C.POINTER(AwFmIndexConfiguration), vp, u64, C.c_int,
                                          C.c_char_p, C.c_int]),
         "awfmGpuSearchTally": (C.c_int, [vp, vp, vp, C.c_uint32, u64, C.POINTER(u64 * 4)]),

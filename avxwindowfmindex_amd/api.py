@@ -12,7 +12,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import (AwFmAlphabetAmino, AwFmAlphabetDna, AwFmAlphabetRna, AwFmFileReadOkay, AwFmFileWriteOkay,  # noqa: F401
-                   AwFmIllegalPositionError, AwFmSuccess)
+                   AwFmIllegalPositionError, AwFmSuccess, AwFmUnsupportedVersionError)
+
+ILLEGAL_SEQUENCE = 0xFFFFFFFF  # the sequence number of an illegal position in the batch mappings (include/awfm_gpu.h)
 
 
 class AwFmError(RuntimeError):
@@ -236,6 +238,22 @@ def pack_kmers(kmers, alphabet=AwFmAlphabetDna):
     return out
 
 
+def local_positions_host(index, positions, threads=4, out_sequence=None, out_local=None):
+    """awfmLocalPositions: global text positions (uint64[n]) -> (sequence numbers uint32[n], local positions uint64[n],
+    how many are illegal); an illegal position gets ILLEGAL_SEQUENCE and keeps its global position.  out_local may be
+    `positions` itself (in place).  Raises AwFmError (rc AwFmUnsupportedVersionError) on an index without a record table."""
+    positions = np.ascontiguousarray(positions, dtype=np.uint64)
+    n = positions.size
+    seq = np.zeros(n, np.uint32) if out_sequence is None else out_sequence
+    local = np.zeros(n, np.uint64) if out_local is None else out_local
+    assert seq.dtype == np.uint32 and local.dtype == np.uint64 and seq.size >= n and local.size >= n
+    illegal = C.c_uint64(0)
+    rc = _lib.lib().awfmLocalPositions(index.ptr, positions.ctypes.data if n else None, n, seq.ctypes.data if n else None,
+                                       local.ctypes.data if n else None, C.byref(illegal), threads)
+    _check("awfmLocalPositions", rc)
+    return seq, local, int(illegal.value)
+
+
 # enum AwFmGpuKernel (include/awfm_gpu.h)
 AWFM_GPU_KERNEL_AUTO, AWFM_GPU_KERNEL_GROUP8, AWFM_GPU_KERNEL_GROUP4, AWFM_GPU_KERNEL_GROUP2, AWFM_GPU_KERNEL_GROUP1 = range(5)
 
@@ -260,6 +278,22 @@ class GpuIndex:
             _check("awfmGpuIndexCreate", L.awfmGpuIndexCreate(index.ptr, device, C.byref(h)))
             self.handle = h
         self.index = index
+
+    @classmethod
+    def acquire_all(cls, index, max_handles=8):
+        """awfmGpuIndexAcquireAll: the handles awFmParallelSearch* deal their chunks to ($AWFM_GPU_DEVICES; unset: three
+        lanes on one image of the default device), owned by the index"""
+        L = _lib.lib()
+        if L.awfmGpuDeviceCount() <= 0:
+            raise RuntimeError("no HIP device: the search path is GPU only (no CPU fallback)")
+        handles = (C.c_void_p * max_handles)()
+        n = L.awfmGpuIndexAcquireAll(index.ptr, handles, max_handles)
+        out = []
+        for h in handles[:n]:
+            g = cls.__new__(cls)
+            g.owned, g.handle, g.index = False, C.c_void_p(h), index
+            out.append(g)
+        return out
 
     @property
     def device_bytes(self):
@@ -331,6 +365,46 @@ class GpuIndex:
     @property
     def is_wide(self):
         return bool(_lib.lib().awfmGpuIndexIsWide(self.handle))
+
+    # sequence coordinates (include/awfm_gpu.h) ---------------------------
+    def set_record_table(self, ends):
+        """awfmGpuIndexSetRecordTable: installs or replaces the image's record table from the records' ends in the concatenated
+        text (terminators excluded); an empty array drops it"""
+        ends = np.ascontiguousarray(ends, dtype=np.uint64)
+        _check("awfmGpuIndexSetRecordTable", _lib.lib().awfmGpuIndexSetRecordTable(self.handle, ends.ctypes.data if ends.size else None,
+                                                                                   ends.size))
+
+    @property
+    def num_records(self):
+        """records of the image's record table (0: none)"""
+        return int(_lib.lib().awfmGpuIndexNumRecords(self.handle))
+
+    def local_positions(self, d_positions, capacity, d_seq, d_local, d_num_positions=0, d_num_illegal=0, stream=0):
+        """awfmGpuLocalPositions: the first min(*d_num_positions, capacity) positions (capacity without a count) to
+        (sequence number, local position) on the device; d_local may be d_positions; *d_num_illegal is added to"""
+        _check("awfmGpuLocalPositions", _lib.lib().awfmGpuLocalPositions(self.handle, d_positions or None, capacity, d_num_positions or None,
+                                                                         d_seq or None, d_local or None, d_num_illegal or None, stream or None))
+
+    def locate_host_local(self, chars, offsets=None, fixed_length=0):
+        """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],
+        number of illegal positions)"""
+        L = _lib.lib()
+        chars = np.ascontiguousarray(chars, dtype=np.uint8)
+        n = (len(offsets) - 1) if offsets is not None else chars.size // fixed_length
+        ranges = np.zeros((n, 2), np.uint64)
+        hit_off = np.zeros(n + 1, np.uint64)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        holder = chars if chars.size else np.zeros(1, np.uint8)
+        seq_ptr, loc_ptr, illegal = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.c_uint64(0)
+        rc = L.awfmGpuLocateHostLocal(self.handle, holder.ctypes.data, off.ctypes.data if off is not None else None, fixed_length, n,
+                                      ranges.ctypes.data, hit_off.ctypes.data, C.byref(seq_ptr), C.byref(loc_ptr), C.byref(illegal))
+        _check("awfmGpuLocateHostLocal", rc)
+        total = int(hit_off[n])
+        seq = np.ctypeslib.as_array(seq_ptr, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
+        loc = np.ctypeslib.as_array(loc_ptr, shape=(total,)).copy() if total else np.zeros(0, np.uint64)
+        L.free(C.cast(seq_ptr, C.c_void_p))
+        L.free(C.cast(loc_ptr, C.c_void_p))
+        return ranges, hit_off, seq, loc, int(illegal.value)
 
     # host-buffer calls -------------------------------------------------
     def count_host(self, chars, offsets=None, fixed_length=0):

@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <shared_mutex>
 #include <thread>
 #include <vector>
 #include <string>
@@ -231,6 +232,19 @@ struct QueryRec {
   unsigned long long codes; /* 2-bit letter codes of the k-mer, last character in bits 1..0 */
   unsigned int index;       /* query number in the batch */
   unsigned int length;      /* characters (1..32), or 0xFFFFFFFF: left to the general kernel */
+};
+
+/* kernel-argument view of an image's record table (awfm_records_kernel.h): the records' ends in the concatenated text
+ * (terminator excluded; record r begins at ends[r - 1] + 1, record 0 at 0) and a directory over the positions:
+ * dir[b] = first record whose end lies beyond position b << shift, dir[numBuckets] = numRecords, so that the record of a
+ * position p < lastEnd is one of dir[p >> shift] .. dir[(p >> shift) + 1] */
+struct DevRecords {
+  const unsigned long long *ends;
+  const unsigned *dir;
+  unsigned long long lastEnd; /* ends[numRecords - 1]: every position from here on is illegal */
+  unsigned numRecords;
+  unsigned numBuckets;
+  unsigned shift;
 };
 
 constexpr int kThreads = 256;
@@ -844,7 +858,7 @@ __global__ void relayoutAminoKernel(const unsigned long long *__restrict__ ref, 
 struct AwFmGpuIndex;
 /* Locks of an image and its handles, in the one order they are taken:
  *   awfm_gpu_image.hip's tableMutex (the registry) -> streamMutex -> handlesMutex -> for each handle in handle order: aosMutex ->
- *   workMutex -> orderMutex -> lengthMutex -> joinMutex.
+ *   workMutex -> orderMutex -> lengthMutex -> joinMutex -> recordMutex (a leaf: nothing is taken and nothing waited for under it).
  * A search takes one handle's locks in that order (AoS lane -> host-buffer call -> ordered search).  AwFmGpuExclusive is the only
  * holder of the locks of more than one handle: every change of an image's view (DevIndex and the arrays behind it) happens inside
  * it.  Nobody takes tableMutex while holding a handle's lock. */
@@ -914,6 +928,18 @@ struct AwFmGpuImage {
    * overlap their pack/scatter with each other's transfers and kernels without a second copy of the index */
   std::mutex handlesMutex;
   std::vector<AwFmGpuIndex *> handles;
+  /* The record table of a multi-record index (awfm_gpu_records.hip): global text position -> (record, position in it).  One
+   * allocation (ends, then the directory), uploaded with the image or installed by awfmGpuIndexSetRecordTable.  A mapping call
+   * holds recordMutex shared while it reads the view and enqueues its kernel (no wait under it); whoever replaces the table
+   * publishes the new view under the lock held exclusively and frees the old arrays after it (hipFree waits for the kernels
+   * that were enqueued with them). */
+  std::shared_mutex recordMutex;
+  DevRecords records{};
+  void *dRecords = nullptr;
+  uint64_t recordBytes = 0;
+  bool recordsInLds = false;   /* the lookup the table got when it was installed: ends and directory staged into LDS, or read from memory */
+  unsigned recordLdsBytes = 0; /* dynamic LDS of the LDS lookup */
+  unsigned recordGrid = 0;     /* resident workgroups of the table's kernel on this device (persistent grid) */
 };
 
 /* one caller's handle on an image: its staging, its scratch, its locks and its selections */
@@ -1173,6 +1199,18 @@ int awfmGpuAminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
 AwFmGpuIndex *awfmGpuIndexAdopt(const struct AwFmIndex *index, int device, void *dBlocks, void *dSuper, unsigned superShift,
                                 void *dSeed, void *dSa, void *dPrefix, unsigned long long sentinelPos, uint64_t deviceBytes);
 void awfmGpuIndexRegister(const struct AwFmIndex *index, AwFmGpuIndex *g);
+/* awfm_gpu_records.hip: installs (numRecords == 0: drops) the image's record table from a host array of record ends; validates,
+ * uploads, publishes, then frees the table it replaces.  The caller holds AwFmGpuExclusive on an image somebody else may be using. */
+enum AwFmReturnCode awfmGpuInstallRecordTable(AwFmGpuIndex *g, const uint64_t *ends, uint64_t numRecords);
+/* ... from the record table of a host index (nothing to do, AwFmSuccess, when it has none) */
+enum AwFmReturnCode awfmGpuInstallRecordTableOf(AwFmGpuIndex *g, const struct AwFmIndex *index);
+/* one line for awfmGpuIndexDescribe ("" without a table) */
+std::string awfmGpuDescribeRecordTable(const AwFmGpuImage *image);
+/* awfm_gpu.hip: awfmGpuLocateHostWindows with every window mapped to sequence coordinates on the device before its download
+ * (seqOfWindow != NULL: the sink's positions are then the local ones and *seqOfWindow the window's sequence numbers) */
+enum AwFmReturnCode awfmGpuLocateHostWindowsMapped(AwFmGpuIndex *g, const uint8_t *chars, const uint64_t *offsets, uint32_t fixedLength,
+                                                   uint64_t numQueries, struct AwFmSearchRange *ranges, uint64_t *hitOffsets,
+                                                   AwFmGpuHitWindowSink sink, void *user, const uint32_t **seqOfWindow, uint64_t *numIllegal);
 /* awfm_gpu_pair.hip: builds (enable) or drops the pair image of a nucleotide image; the caller holds whatever locks the image
  * needs */
 enum AwFmReturnCode awfmGpuApplyPairImage(AwFmGpuIndex *g, bool enable);

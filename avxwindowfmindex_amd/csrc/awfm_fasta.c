@@ -160,6 +160,58 @@ enum AwFmReturnCode awFmGetLocalSequencePositionFromIndexPosition(const struct A
   return AwFmSuccess;
 }
 
+/* the batch form of the function above (include/awfm_gpu.h: awfmLocalPositions): the same search per position, over the
+ * thread pool; an illegal position gets sequence 0xFFFFFFFF and keeps its global position */
+struct awfmLocalCtx {
+  const struct AwfmFastaRecord *records;
+  size_t numRecords;
+  const uint64_t *positions;
+  uint32_t *sequenceNumbers;
+  uint64_t *localPositions;
+  uint64_t illegal[64]; /* per thread of the loop */
+};
+
+static void awfmLocalRange(void *p, uint64_t begin, uint64_t end, unsigned tid) {
+  struct awfmLocalCtx *c = p;
+  uint64_t illegal = 0;
+  for (uint64_t i = begin; i < end; i++) {
+    const uint64_t position = c->positions[i];
+    size_t lo = 0, hi = c->numRecords; /* first record whose end is beyond the position */
+    while (lo < hi) {
+      const size_t mid = lo + (hi - lo) / 2;
+      if (c->records[mid].sequenceEndPosition > position)
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    const uint64_t start = lo == 0 ? 0 : (uint64_t)c->records[lo - 1].sequenceEndPosition + 1;
+    if (lo == c->numRecords || position < start) {
+      c->sequenceNumbers[i] = 0xFFFFFFFFu;
+      c->localPositions[i] = position;
+      illegal++;
+    } else {
+      c->sequenceNumbers[i] = (uint32_t)lo;
+      c->localPositions[i] = position - start;
+    }
+  }
+  c->illegal[tid & 63u] += illegal;
+}
+
+enum AwFmReturnCode awfmLocalPositions(const struct AwFmIndex *index, const uint64_t *positions, uint64_t numPositions,
+                                       uint32_t *sequenceNumbers, uint64_t *localPositions, uint64_t *numIllegalOut,
+                                       unsigned threads) {
+  if (!index) return AwFmNullPtrError;
+  const struct FastaVector *fv = index->fastaVector;
+  if (!fv) return AwFmUnsupportedVersionError;
+  if (numPositions != 0 && (!positions || !sequenceNumbers || !localPositions)) return AwFmNullPtrError;
+  struct awfmLocalCtx ctx = {fv->records, fv->numRecords, positions, sequenceNumbers, localPositions, {0}};
+  if (numPositions != 0) awfmParallelFor(threads ? threads : 1, numPositions, awfmLocalRange, &ctx);
+  uint64_t illegal = 0;
+  for (unsigned t = 0; t < 64; t++) illegal += ctx.illegal[t];
+  if (numIllegalOut) *numIllegalOut = illegal;
+  return AwFmSuccess;
+}
+
 /* ref src/AwFmSearch.c:303-315: *headerBuffer points into the index (not NUL terminated) */
 enum AwFmReturnCode awFmGetHeaderStringFromSequenceNumber(const struct AwFmIndex *_RESTRICT_ const index,
                                                           size_t sequenceNumber, char **headerBuffer,

@@ -333,6 +333,18 @@ static uint64_t queryOfHit(const uint64_t *offsets, uint64_t n, uint64_t h) {
 enum AwFmReturnCode awfmGpuLocateHostWindows(AwFmGpuIndex *g, const uint8_t *chars, const uint64_t *offsets,
                                              uint32_t fixedLength, uint64_t numQueries, struct AwFmSearchRange *ranges,
                                              uint64_t *hitOffsets, AwFmGpuHitWindowSink sink, void *user) {
+  return awfmGpuLocateHostWindowsMapped(g, chars, offsets, fixedLength, numQueries, ranges, hitOffsets, sink, user, nullptr, nullptr);
+}
+
+}  // extern "C"
+
+/* seqOfWindow != NULL (awfmGpuLocateHostLocal): every window is mapped to sequence coordinates where it was located
+ * (awfmGpuLocalPositions, in place) before it is downloaded -- the sink's positions are the local ones, *seqOfWindow the
+ * window's sequence numbers (4 bytes per hit more in the device buffer and in the staging), *numIllegal the batch's count */
+enum AwFmReturnCode awfmGpuLocateHostWindowsMapped(AwFmGpuIndex *g, const uint8_t *chars, const uint64_t *offsets, uint32_t fixedLength,
+                                                   uint64_t numQueries, struct AwFmSearchRange *ranges, uint64_t *hitOffsets,
+                                                   AwFmGpuHitWindowSink sink, void *user, const uint32_t **seqOfWindow, uint64_t *numIllegal) {
+  const bool mapped = seqOfWindow != nullptr;
   if (!g || !chars || !hitOffsets || !sink) {
     setError("awfmGpuLocateHost: null argument");
     return AwFmNullPtrError;
@@ -370,11 +382,14 @@ enum AwFmReturnCode awfmGpuLocateHostWindows(AwFmGpuIndex *g, const uint8_t *cha
   const uint64_t budget = awfmGpuHitBudget(g);
   const uint64_t window = totalHits <= budget ? totalHits : (budget / 2 > 0 ? budget / 2 : 1);
   const unsigned buffers = totalHits <= budget ? 1u : 2u;
-  if (window * buffers * 8 > g->hitsBytes) { /* grow-only, so that a steady stream of batches never allocates */
+  /* mapped: the windows' sequence numbers and the counter of illegal positions behind the positions */
+  const size_t seqAt = alignUp(window * buffers * 8, 16), illegalAt = seqAt + alignUp(window * buffers * 4, 16);
+  const size_t hitsNeed = mapped ? illegalAt + 16 : window * buffers * 8;
+  if (hitsNeed > g->hitsBytes) { /* grow-only, so that a steady stream of batches never allocates */
     if (g->dHits) (void)hipFree(g->dHits);
     g->dHits = nullptr;
     g->hitsBytes = 0;
-    const size_t want = window * buffers * 8 + (buffers == 1 ? window * 2 : 0) + 4096;
+    const size_t want = hitsNeed + (buffers == 1 ? window * 2 : 0) + 4096;
     if (hipMalloc(&g->dHits, want) != hipSuccess) {
       (void)hipGetLastError();
       setError("awfmGpuLocateHost: no device memory for the positions of one window of hits ($AWFM_GPU_HIT_BUDGET_BYTES)");
@@ -382,11 +397,14 @@ enum AwFmReturnCode awfmGpuLocateHostWindows(AwFmGpuIndex *g, const uint8_t *cha
     }
     g->hitsBytes = want;
   }
-  uint64_t *staging = (uint64_t *)awfmGpuPinnedBuffer(g, 3, window * buffers * 8);
+  uint64_t *staging = (uint64_t *)awfmGpuPinnedBuffer(g, 3, mapped ? illegalAt + 16 : window * buffers * 8);
   if (!staging) {
     setError("awfmGpuLocateHost: host allocation failed");
     return AwFmAllocationFailure;
   }
+  uint32_t *dSeq = (uint32_t *)((uint8_t *)g->dHits + seqAt), *stagingSeq = (uint32_t *)((uint8_t *)staging + seqAt);
+  uint64_t *dIllegal = (uint64_t *)((uint8_t *)g->dHits + illegalAt), *stagingIllegal = (uint64_t *)((uint8_t *)staging + illegalAt);
+  if (mapped) AWFM_HIP_TRY(hipMemsetAsync(dIllegal, 0, 8, s), AwFmGeneralFailure);
   if (!g->windowEvent[0]) {
     for (int i = 0; i < 2; i++)
       if (hipEventCreateWithFlags(&g->windowEvent[i], hipEventDisableTiming) != hipSuccess) {
@@ -407,6 +425,13 @@ enum AwFmReturnCode awfmGpuLocateHostWindows(AwFmGpuIndex *g, const uint8_t *cha
     uint64_t *dPos = (uint64_t *)g->dHits + (wi % buffers) * window;
     const enum AwFmReturnCode r = awfmGpuLocateWindow(g, dRanges, dHitOffsets, p.qb, p.qe, p.hb, p.he, dPos, dPos, s);
     if (r != AwFmSuccess) return r;
+    if (mapped) {
+      const enum AwFmReturnCode m = awfmGpuLocalPositions(g, dPos, p.he - p.hb, nullptr, dSeq + (wi % buffers) * window, dPos, dIllegal, s);
+      if (m != AwFmSuccess) return m;
+      AWFM_HIP_TRY(hipMemcpyAsync(stagingSeq + (wi % buffers) * window, dSeq + (wi % buffers) * window, (p.he - p.hb) * 4, hipMemcpyDeviceToHost, s),
+                   AwFmGeneralFailure);
+      if (wi + 1 == numWindows) AWFM_HIP_TRY(hipMemcpyAsync(stagingIllegal, dIllegal, 8, hipMemcpyDeviceToHost, s), AwFmGeneralFailure);
+    }
     AWFM_HIP_TRY(hipMemcpyAsync(staging + (wi % buffers) * window, dPos, (p.he - p.hb) * 8, hipMemcpyDeviceToHost, s), AwFmGeneralFailure);
     AWFM_HIP_TRY(hipEventRecord(g->windowEvent[wi % buffers], s), AwFmGeneralFailure);
     return AwFmSuccess;
@@ -421,6 +446,10 @@ enum AwFmReturnCode awfmGpuLocateHostWindows(AwFmGpuIndex *g, const uint8_t *cha
       break;
     }
     const Pending &p = pending[wi % buffers];
+    if (mapped) {
+      *seqOfWindow = stagingSeq + (wi % buffers) * window;
+      if (wi + 1 == numWindows && numIllegal) *numIllegal = *stagingIllegal;
+    }
     if (sink(user, p.qb, p.qe, p.hb, p.he, staging + (wi % buffers) * window) != 0) {
       setError("awfmGpuLocateHost: the sink asked to stop");
       rc = AwFmGeneralFailure;
@@ -429,6 +458,8 @@ enum AwFmReturnCode awfmGpuLocateHostWindows(AwFmGpuIndex *g, const uint8_t *cha
   (void)hipStreamSynchronize(s); /* nothing of this batch is in flight when the work buffers are released */
   return rc;
 }
+
+extern "C" {
 
 namespace {
 struct FlatSinkCtx {

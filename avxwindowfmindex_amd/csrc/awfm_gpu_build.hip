@@ -1202,6 +1202,9 @@ extern "C" enum AwFmReturnCode awfmGpuCreateIndexWithFasta(struct AwFmIndex **in
 
   enum AwFmReturnCode rc = AwFmFileWriteOkay;
   ix->fastaVector = fastaVector; /* the trailer of the file is written from it */
+  /* the image was made before the records were attached: it gets their table now, so that a FASTA index built here maps its
+   * hits to sequence coordinates without a second image */
+  if (fastaVector && awfmGpuInstallRecordTableOf(g, ix) != AwFmSuccess) g->image->accelNotes += "record table: not installed (" + std::string(awfmGpuLastError()) + "); ";
   if (fileSrc) {
     if (config->storeOriginalSequence && sequenceOnDevice) {
       std::vector<uint8_t> hostSeq(sequenceLength ? sequenceLength : 1);

@@ -134,6 +134,8 @@ static enum AwFmReturnCode finishImage(AwFmGpuIndex *g, const struct AwFmIndex *
     g->numCUs = prop.multiProcessorCount;
   fillDevIndex(g, index, superShift, sentinelPos);
   if (const char *env = awfmKnob(AWFM_KNOB_FORCE_WIDE)) g->forceWide = atoi(env) != 0;
+  /* the record table of a multi-record index: small and needed by the first mapping call, so it is not left to the builder thread */
+  if (awfmGpuInstallRecordTableOf(g, index) != AwFmSuccess) return AwFmGeneralFailure;
   (void)applyPairFromEnv(g); /* without it (no memory left) searches simply take one step per read */
   if (behind && startBuilder(g)) return AwFmSuccess;
   if (applyDeepSeedFromEnv(g) != AwFmSuccess && deepRequired) return AwFmGeneralFailure;
@@ -440,7 +442,7 @@ void awfmGpuIndexDestroy(AwFmGpuIndex *g) {
       awfmGpuStreamStateFree(image);
       void *owned[] = {image->dBlocks, image->dSuper, image->dSeed, image->dSa, image->dPrefix, image->dDeepSeed, image->dDeepBig,
                        image->dDenseSa, image->dLengthTable, image->dLengthBig, image->dPairBlocks, image->dPairSuper,
-                       image->dPairSuper32, image->dPairC};
+                       image->dPairSuper32, image->dPairC, image->dRecords};
       for (void *p : owned)
         if (p) (void)hipFree(p);
     }
@@ -592,7 +594,7 @@ void awfmGpuAosUnlock(AwFmGpuIndex *g) {
 }
 
 static uint64_t imageBytes(const AwFmGpuImage *image) {
-  return image->deviceBytes + image->deepSeedBytes + image->denseSaBytes + image->pairBytes + image->lengthTableBytes;
+  return image->deviceBytes + image->deepSeedBytes + image->denseSaBytes + image->pairBytes + image->lengthTableBytes + image->recordBytes;
 }
 uint64_t awfmGpuIndexDeviceBytes(const AwFmGpuIndex *g) { return g && !g->lane ? imageBytes(g->image) : 0; } /* (a lane holds none of it) */
 
@@ -816,6 +818,7 @@ int awfmGpuIndexDescribe(const AwFmGpuIndex *g, char *out, int outBytes) {
   text += image->dev.deepK ? "deeper table depth " + std::to_string(image->dev.deepK) + (image->dev.deepNext ? " with next-step bits; " : "; ") : "deeper table no; ";
   text += image->dDenseSa ? "full suffix array yes; " : "full suffix array no; ";
   if (!g->amino) text += image->dLengthTable ? "tables per k-mer length 1.." + std::to_string(image->lengthDepths) + "; " : "tables per k-mer length not built (the first large mixed-length batch builds them); ";
+  text += awfmGpuDescribeRecordTable(image);
   if (!image->accelNotes.empty()) text += "notes: " + image->accelNotes;
   while (!text.empty() && (text.back() == ' ' || text.back() == ';')) text.pop_back();
   const int n = (int)text.size() < outBytes - 1 ? (int)text.size() : outBytes - 1;

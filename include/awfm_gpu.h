@@ -70,6 +70,7 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   tally_with_deep=1   awfmGpuSearchTally starts from the deeper table (default: the index's own, the reference's bytes)
  *   nuc_super_shift=13..31|auto   nucleotide superblocks of 2^shift positions: the arithmetic of images of 2^32 positions
  *                       and more on small ones
+ *   record_lookup=lds|dir   which lookup a record table gets when it is installed (default: by its size; lds only where it fits)
  *   stream_trace=1, aos_trace=1   host timelines of the chunked pipelines / the AoS lanes on stderr */
 
 /* ---- device image ---- */
@@ -149,6 +150,33 @@ double awfmGpuIndexLengthTableBuildSeconds(const AwFmGpuIndex *g);
  * 1 byte per BWT position of device memory; the host index and the .awfmi file are untouched. */
 enum AwFmReturnCode awfmGpuIndexSetPairImage(AwFmGpuIndex *g, int enable);
 int awfmGpuIndexHasPairImage(const AwFmGpuIndex *g);
+/* ---- sequence coordinates: global text position -> (sequence number, position in that sequence) ----
+ * The batch forms of awFmGetLocalSequencePositionFromIndexPosition (ref src/AwFmSearch.c:284-301), one definition on both
+ * sides: with the records' ends E[0..R) (sequenceEndPosition: terminator excluded) and starts S[0] = 0, S[r] = E[r-1] + 1, a
+ * position p belongs to the first record r with E[r] > p, provided p >= S[r]; its local position is p - S[r].  Any other p -- a
+ * record's terminator, or anything from E[R-1] on, the sentinel included -- is ILLEGAL: it gets sequence number 0xFFFFFFFF,
+ * keeps its global position, is counted, and the batch carries on (ordinary searches reach such positions: terminators are
+ * stored as the ambiguity letter, so a query of ambiguity letters hits them).  Empty records own no position.  Only a hit's
+ * start is mapped, as in the reference: a k-mer's length plays no part.
+ *
+ * awfmLocalPositions: on the host, over `threads` threads of the library's pool (a binary search per position: 10^8 positions
+ * take 0.16-0.17 s against 640 records and 0.7-0.8 s against 5.7 * 10^5 on 16 threads); what callers of the AoS entry points run on a positionList, and the checker of the
+ * device calls.  localPositions may be `positions`.  AwFmUnsupportedVersionError, nothing written, when the index has no
+ * record table (it was not made from a FASTA file). */
+enum AwFmReturnCode awfmLocalPositions(const struct AwFmIndex *index, const uint64_t *positions, uint64_t numPositions,
+                                       uint32_t *sequenceNumbers, uint64_t *localPositions, uint64_t *numIllegalOut,
+                                       unsigned threads);
+/* The record table of a device image: the records' ends (8 bytes each) and a directory over the positions (4 bytes per bucket;
+ * about as many buckets as records, at most 4096 for a table small enough to be looked up from LDS), counted in
+ * awfmGpuIndexDeviceBytes and named by awfmGpuIndexDescribe.  An image made from an index that has records (awFmCreateIndexFromFasta
+ * on either builder, awFmReadIndexFromFile of such a file) gets it with its blocks.  awfmGpuIndexSetRecordTable installs or
+ * replaces it from the caller's array of ends (host; numRecords == 0 drops it) -- for an index made by awFmCreateIndex /
+ * awfmGpuCreateIndex from a text the caller concatenated with its own terminators.  The ends must increase (E[r] > E[r-1]) and
+ * may lie at and beyond 2^32 whatever the image's width.  Cost: one upload of the table; it waits for the searches on the image
+ * like every other change of it, and mapping calls already enqueued finish on the table they were enqueued with.  Refused
+ * (AwFmIllegalPositionError) tables leave the old one in place. */
+enum AwFmReturnCode awfmGpuIndexSetRecordTable(AwFmGpuIndex *g, const uint64_t *sequenceEndPositions, uint64_t numRecords);
+uint32_t awfmGpuIndexNumRecords(const AwFmGpuIndex *g); /* 0: the image has no record table */
 /* Selects the search kernel variant for this image (default AUTO). */
 void awfmGpuIndexSetKernel(AwFmGpuIndex *g, enum AwFmGpuKernel kernel);
 /* The kernels keep BWT positions in 32 bits whenever bwtLength < 2^32 and in 64 bits otherwise (the reference is
@@ -265,6 +293,18 @@ enum AwFmReturnCode awfmGpuListLocateOnDevice(AwFmGpuIndex *g, const uint32_t *d
                                               uint32_t capacity, const uint32_t *dNumHits, uint64_t numQueries, uint32_t *dSortedKmers,
                                               struct AwFmSearchRange *dSortedRanges, uint64_t *dHitOffsets, uint64_t capacityHits,
                                               uint64_t *dPositions, void *stream);
+
+/* The stage after a locate on the device: dSequenceNumbers[i], dLocalPositions[i] = the sequence coordinates of dPositions[i]
+ * (definition: "sequence coordinates" above; dLocalPositions may be dPositions) for the first n entries, n = capacity when
+ * dNumPositions is NULL and min(*dNumPositions, capacity) otherwise, the count being read ON THE DEVICE: after
+ * awfmGpuLocateOnDevice pass &dHitOffsets[numQueries], after awfmGpuListLocateOnDevice &dHitOffsets[capacity of the list].
+ * Entries past the count stay as they were.  *dNumIllegal (device, may be NULL) is ADDED to: zero it first.  One launch,
+ * asynchronous on `stream`: no host wait, no allocation; the grid is sized from `capacity` and trimmed by the count.  It reads 8
+ * and writes 12 bytes per position and looks the record up in LDS (tables of up to 4096 records: 10^8 positions in 0.35-0.36 ms,
+ * the rate of a device-to-device copy of the same bytes) or in a directory in memory (any table; 5.7 * 10^5 records: 2.3 ms).
+ * AwFmUnsupportedVersionError when the image has no record table. */
+enum AwFmReturnCode awfmGpuLocalPositions(AwFmGpuIndex *g, const uint64_t *dPositions, uint64_t capacity, const uint64_t *dNumPositions,
+                                          uint32_t *dSequenceNumbers, uint64_t *dLocalPositions, uint64_t *dNumIllegal, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
@@ -410,6 +450,15 @@ enum AwFmReturnCode awfmGpuCountHost(AwFmGpuIndex *g, const uint8_t *chars, cons
 enum AwFmReturnCode awfmGpuLocateHost(AwFmGpuIndex *g, const uint8_t *chars, const uint64_t *offsets,
                                       uint32_t fixedLength, uint64_t numQueries, struct AwFmSearchRange *ranges,
                                       uint64_t *hitOffsets, uint64_t **positions);
+
+/* awfmGpuLocateHost with the hits in sequence coordinates: (*sequenceNumbers)[h], (*localPositions)[h] for hit number h of the
+ * flat hit list (both malloc'ed, hitOffsets[numQueries] entries, the caller frees them), *numIllegal (may be NULL) = how many of
+ * them are illegal positions (sequence 0xFFFFFFFF, global position kept).  The mapping runs on the device on every window of
+ * hits before it is downloaded (12 instead of 8 bytes per hit come back; the windows are those of awfmGpuLocateHost:
+ * $AWFM_GPU_HIT_BUDGET_BYTES).  AwFmUnsupportedVersionError when the image has no record table. */
+enum AwFmReturnCode awfmGpuLocateHostLocal(AwFmGpuIndex *g, const uint8_t *chars, const uint64_t *offsets, uint32_t fixedLength,
+                                           uint64_t numQueries, struct AwFmSearchRange *ranges, uint64_t *hitOffsets,
+                                           uint32_t **sequenceNumbers, uint64_t **localPositions, uint64_t *numIllegal);
 
 /* The same with the hit list delivered in windows, for batches whose hits exceed what may be resident on the device
  * ($AWFM_GPU_HIT_BUDGET_BYTES; default a quarter of the free device memory, at most 2^31 hits): hitOffsets[0..numQueries]
