@@ -254,6 +254,36 @@ def local_positions_host(index, positions, threads=4, out_sequence=None, out_loc
     return seq, local, int(illegal.value)
 
 
+def longest_suffix_matches_host(index, chars, starts=None, ends=None, fixed_length=0, min_length=0, threads=4):
+    """awfmLongestSuffixMatches: for query i = chars[starts[i]:ends[i]] (both None: fixed_length characters per query, chars
+    then holds a whole number of them) the length of its longest suffix that occurs in the text, the BWT range of that suffix
+    and its size -> (match lengths uint32[n], ranges uint64[n, 2], counts uint32[n]).  A query whose match is shorter than
+    max(min_length, 1) gets the range (1, 0) and count 0; the length is the true one either way."""
+    chars = np.ascontiguousarray(np.frombuffer(chars, np.uint8) if isinstance(chars, (bytes, bytearray)) else chars, dtype=np.uint8)
+    if (starts is None) != (ends is None):
+        raise ValueError("starts and ends come together")
+    if starts is not None:
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        ends = np.ascontiguousarray(ends, dtype=np.uint64)
+        if starts.shape != ends.shape:
+            raise ValueError("starts and ends differ in length")
+        n = starts.size
+    else:
+        if fixed_length <= 0:
+            raise ValueError("queries need starts and ends or a fixed length")
+        n = chars.size // fixed_length
+    lengths = np.zeros(n, np.uint32)
+    ranges = np.zeros((n, 2), np.uint64)
+    counts = np.zeros(n, np.uint32)
+    holder = chars if chars.size else np.zeros(1, np.uint8)
+    rc = _lib.lib().awfmLongestSuffixMatches(index.ptr, holder.ctypes.data, starts.ctypes.data if starts is not None and n else None,
+                                             ends.ctypes.data if ends is not None and n else None, fixed_length, n, min_length,
+                                             lengths.ctypes.data if n else None, ranges.ctypes.data if n else None,
+                                             counts.ctypes.data if n else None, threads)
+    _check("awfmLongestSuffixMatches", rc)
+    return lengths, ranges, counts
+
+
 # enum AwFmGpuKernel (include/awfm_gpu.h)
 AWFM_GPU_KERNEL_AUTO, AWFM_GPU_KERNEL_GROUP8, AWFM_GPU_KERNEL_GROUP4, AWFM_GPU_KERNEL_GROUP2, AWFM_GPU_KERNEL_GROUP1 = range(5)
 
@@ -542,6 +572,13 @@ class GpuIndex:
     def search(self, d_chars, d_offsets, fixed_length, n, d_ranges, d_counts, stream=0):
         _check("awfmGpuSearch", _lib.lib().awfmGpuSearch(self.handle, d_chars, d_offsets or None, fixed_length, n,
                                                          d_ranges or None, d_counts or None, stream or None))
+
+    def longest_suffix_matches(self, d_chars, d_starts, d_ends, fixed_length, n, min_length, d_lengths, d_ranges, d_counts, stream=0):
+        """awfmGpuLongestSuffixMatches: per query chars[starts[i]:ends[i]] (d_starts = d_ends = 0: fixed_length characters each)
+        the length of its longest suffix that occurs, that suffix's range and count; each output may be 0"""
+        _check("awfmGpuLongestSuffixMatches", _lib.lib().awfmGpuLongestSuffixMatches(
+            self.handle, d_chars, d_starts or None, d_ends or None, fixed_length, n, min_length, d_lengths or None, d_ranges or None,
+            d_counts or None, stream or None))
 
     def search_hits(self, d_chars, d_offsets, fixed_length, n, d_ranges, d_counts, stream=0):
         """awfmGpuSearchHits: like search(), but a query without hits only gets count 0 and some empty range"""

@@ -183,3 +183,55 @@ uint64_t *awFmFindDatabaseHitPositions(const struct AwFmIndex *_RESTRICT_ const 
   *fileAccessResult = AwFmFileReadOkay;
   return positions;
 }
+
+/* ---- longest suffix match (include/awfm_gpu.h: awfmLongestSuffixMatches) ----
+ * The definition, letter by letter with the step above: no table enters it. */
+struct awfmMatchCtx {
+  const struct AwFmIndex *index;
+  const uint8_t *chars;
+  const uint64_t *starts, *ends;
+  uint32_t fixedLength, minLength;
+  uint32_t *matchLengths;
+  struct AwFmSearchRange *ranges;
+  uint32_t *counts;
+};
+
+static void awfmMatchRange(void *p, uint64_t begin, uint64_t end, unsigned tid) {
+  (void)tid;
+  const struct awfmMatchCtx *c = p;
+  const struct AwFmIndex *ix = c->index;
+  const uint32_t threshold = c->minLength > 1u ? c->minLength : 1u;
+  for (uint64_t i = begin; i < end; i++) {
+    const uint64_t first = c->starts ? c->starts[i] : i * c->fixedLength;
+    const uint64_t last = c->starts ? c->ends[i] : first + c->fixedLength;
+    uint64_t m = last > first ? last - first : 0;
+    if (m > 0xFFFFFFFFull) m = 0xFFFFFFFFull; /* the match length is 32-bit: the last 2^32 - 1 characters */
+    struct AwFmSearchRange kept = {1, 0};
+    uint32_t length = 0;
+    if (m != 0) {
+      struct AwFmSearchRange r = awFmCreateInitialQueryRangeFromChar(ix, (char)c->chars[last - 1]);
+      while (r.startPtr <= r.endPtr) {
+        kept = r;
+        length++;
+        if (length == m) break;
+        hostStep(ix, &r, letterIndexOf(ix, (char)c->chars[last - 1 - length]));
+      }
+    }
+    if (length < threshold) kept = (struct AwFmSearchRange){1, 0};
+    if (c->matchLengths) c->matchLengths[i] = length;
+    if (c->ranges) c->ranges[i] = kept;
+    if (c->counts) c->counts[i] = kept.startPtr <= kept.endPtr ? (uint32_t)(kept.endPtr - kept.startPtr + 1) : 0u;
+  }
+}
+
+enum AwFmReturnCode awfmLongestSuffixMatches(const struct AwFmIndex *index, const uint8_t *chars, const uint64_t *starts,
+                                             const uint64_t *ends, uint32_t fixedLength, uint64_t numQueries, uint32_t minLength,
+                                             uint32_t *matchLengths, struct AwFmSearchRange *ranges, uint32_t *counts,
+                                             unsigned threads) {
+  if (!index) return AwFmNullPtrError;
+  if (numQueries == 0) return AwFmSuccess;
+  if (!chars || (starts == NULL) != (ends == NULL) || (!starts && fixedLength == 0)) return AwFmNullPtrError;
+  struct awfmMatchCtx ctx = {index, chars, starts, ends, fixedLength, minLength, matchLengths, ranges, counts};
+  awfmParallelFor(threads ? threads : 1, numQueries, awfmMatchRange, &ctx);
+  return AwFmSuccess;
+}

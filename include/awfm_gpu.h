@@ -14,6 +14,10 @@
  *                          the rank primitives (ref src/AwFmOccurrence.c:8-135,
  *                          src/AwFmSimdConfig.c:89-114, src/AwFmSearch.c:42-159,
  *                          :485-520, src/AwFmKmerTable.c:4-51)
+ *   awfmGpuLongestSuffixMatches   the loop a seed-and-extend caller writes around
+ *                          awFmCreateInitialQueryRangeFromChar and the iterative step
+ *                          functions (ref src/AwFmSearch.c:27-159): step until the range
+ *                          empties, keep the last range that had hits and its depth
  *   awfmGpuHitOffsets      the per-query sizing of setPositionListCount
  *                          (ref src/AwFmParallelSearch.c:327-328, :367-387) as
  *                          one exclusive scan
@@ -210,6 +214,37 @@ enum AwFmReturnCode awfmGpuCreateIndex(struct AwFmIndex **index, const struct Aw
 enum AwFmReturnCode awfmGpuSearch(AwFmGpuIndex *g, const uint8_t *dChars, const uint64_t *dOffsets,
                                   uint32_t fixedLength, uint64_t numQueries, struct AwFmSearchRange *dRanges,
                                   uint32_t *dCounts, void *stream);
+
+/* ---- longest suffix match: how much of a query matches, and where ----
+ * The batch form of the walk a caller of the reference's step functions writes by hand (ref src/AwFmIndex.h:477-512): with the
+ * library's own letter mapping, r_1 = awFmCreateInitialQueryRangeFromChar(q[m-1]) and r_(l+1) = one backward step of r_l with the
+ * letter of q[m-1-l].  The MATCH LENGTH of q[0..m) is the largest l <= m for which r_1 .. r_l are all non-empty (0 when m = 0 or
+ * r_1 is empty), the MATCH RANGE is r_l, or {1, 0} when l = 0: the longest suffix of the query that occurs in the text and the
+ * BWT interval of its occurrences.  No table, pair image or position width changes an answer.
+ *
+ * Query i is chars[starts[i] .. ends[i]) (ends[i] <= starts[i]: empty): two arrays, so that queries may overlap -- "the match
+ * ending at every 4th position of this read, at most 64 characters long" is a list of (start, end) into the read buffer.  A CSR
+ * caller passes offsets and offsets + 1; both NULL: fixedLength characters per query.  Of a query longer than 2^32 - 1
+ * characters the last 2^32 - 1 are walked.  minLength (0: none): a query whose match is shorter than max(minLength, 1) gets
+ * count 0 and the range {1, 0}, so that awfmGpuHitOffsets / awfmGpuHitOffsetsFromCounts / awfmGpuLocate* skip it; the match
+ * length written is the true one either way.  Each output may be NULL; counts[i] = range length truncated to u32.
+ *
+ * awfmLongestSuffixMatches: the definition, letter by letter on the host over `threads` threads of the library's pool; the
+ * checker of the device call.
+ * awfmGpuLongestSuffixMatches: one asynchronous kernel on `stream`, no host wait, no allocation and no scratch (csrc/
+ * awfm_match_kernel.h).  It starts from the deeper table or the index's own where the entry of the query's last letters is
+ * non-empty (an empty entry says only that the match is shorter: the walk then starts from r_1), takes two letters per block
+ * read through the pair image, and re-fills its 32-character register window as the walk moves left.  It reads dChars only in
+ * aligned 4-byte words that hold at least one byte of the query they are read for: nothing outside an allocation that holds
+ * the queries.  numQueries == 0 succeeds and touches nothing. */
+enum AwFmReturnCode awfmLongestSuffixMatches(const struct AwFmIndex *index, const uint8_t *chars, const uint64_t *starts,
+                                             const uint64_t *ends, uint32_t fixedLength, uint64_t numQueries, uint32_t minLength,
+                                             uint32_t *matchLengths, struct AwFmSearchRange *ranges, uint32_t *counts,
+                                             unsigned threads);
+enum AwFmReturnCode awfmGpuLongestSuffixMatches(AwFmGpuIndex *g, const uint8_t *dChars, const uint64_t *dStarts,
+                                                const uint64_t *dEnds, uint32_t fixedLength, uint64_t numQueries,
+                                                uint32_t minLength, uint32_t *dMatchLengths, struct AwFmSearchRange *dRanges,
+                                                uint32_t *dCounts, void *stream);
 
 /* Hits-only variant of awfmGpuSearch, for callers that go on to count or locate (what
  * awFmParallelSearchCount/Locate report: ref src/AwFmParallelSearch.c:159-220, :315-365): queries with hits get
