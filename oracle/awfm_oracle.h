@@ -5,10 +5,10 @@
  * may include, link or call this file; only tests/, __graft_entry__.smoke() and
  * bench.py's cpu_baseline leg use it, and only as the checker.
  *
- * PARITY PINNING: the reference cannot be compiled in the authoring container
- * (src/AwFmIndex.h:8 includes FastaVector.h and src/AwFmCreate.c:99 calls
- * divsufsort64, both from git submodules that are empty in the mount; stand-ins
- * are not allowed).  The oracle is therefore pinned against
+ * PARITY PINNING: where the reference's sources are present the oracle is
+ * compared with the reference itself, compiled behind oracle/ref_shim into
+ * _ref/libawfm_ref.so (tests/test_reference_parity.py).  Independently of that
+ * it is pinned against
  *   - the known answers of test/occurrenceTests/occurrenceTests.c:48-113,
  *   - the brute-force properties of test/searchTest, test/parallelSearch,
  *     test/backtraceTest, test/bwtTest, test/createTests,

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generates tests/golden/*.npz: seeded inputs -> index-array digests, {sp,ep,count} and hit positions.
 
-The vectors come from the CPU oracle after it has been pinned (tests/test_oracle_pin.py): the reference
-itself cannot be built in the authoring container (empty FastaVector / libdivsufsort submodules).
+The vectors come from the CPU oracle after it has been pinned (tests/test_oracle_pin.py); that they are what the
+reference itself computes is checked by tests/test_reference_parity.py::test_goldens_are_what_the_reference_computes.
 Re-run after an intentional change of the generators only; the fixtures are data, the script is the
 provenance.  Usage: python scripts/make_golden.py
 """

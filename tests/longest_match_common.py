@@ -122,9 +122,14 @@ class BruteForce:
 
 # ---- checker 2: the public step functions, one call per letter ----
 def step_walk(lib, index, query):
+    """lib / index: the product's (_lib.lib(), api.Index) or the reference's own (oracle.reference.lib(), its Index) -- the
+    same walk over either library's range and step functions"""
     from avxwindowfmindex_amd import _lib
     amino = index.is_amino
-    to_index = lib.awfmAminoAsciiToIndex if amino else lib.awfmNucAsciiToIndex
+    if hasattr(lib, "awfmNucAsciiToIndex"):
+        to_index = lib.awfmAminoAsciiToIndex if amino else lib.awfmNucAsciiToIndex
+    else:  # the reference's names (src/AwFmLetter.h)
+        to_index = lib.awFmAsciiAminoAcidToLetterIndex if amino else lib.awFmAsciiNucleotideToLetterIndex
     to_index.restype, to_index.argtypes = C.c_uint8, [C.c_uint8]
     step = lib.awFmAminoIterativeStepBackwardSearch if amino else lib.awFmNucleotideIterativeStepBackwardSearch
     m = len(query)

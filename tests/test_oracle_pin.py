@@ -1,7 +1,7 @@
 """Pins the CPU oracle (oracle/awfm_oracle.c) before anything is compared with it.
 
-The reference cannot be compiled here (its FastaVector / libdivsufsort submodules are empty), so the
-oracle is pinned against (a) the known answers the reference's own tests hold and (b) the brute-force
+The oracle is also compared with the compiled reference itself (tests/test_reference_parity.py), where the reference's
+sources are present; these pins need nothing but this repository.  The oracle is pinned against (a) the known answers the reference's own tests hold and (b) the brute-force
 properties those tests check, restated with seeded inputs:
   test/occurrenceTests/occurrenceTests.c:48-113   masked popcount known answers + random vectors
   test/letterTest/AwFmLetterTest.c:16-324         letter tables
