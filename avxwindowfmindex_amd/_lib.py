@@ -40,7 +40,7 @@ GPU_SYMBOLS = [
     "awfmGpuSortHitsOnDevice", "awfmGpuHitOffsetsOnDevice", "awfmGpuLocateOnDevice", "awfmGpuLastOrderedSearchKernelMs", "awfmGpuOrderedKernelLog", "awfmGpuIndexDeepSeedBuildSeconds", "awfmGpuIndexDeepSeedTransientBytes", "awfmGpuIndexHasDenseSa", "awfmGpuIndexDenseSaBuildSeconds", "awfmGpuIndexLengthTableBytes", "awfmGpuIndexLengthTableBuildSeconds", "awfmGpuMixedLookupLineTally",
     "awfmGpuListLocateOnDevice", "awfmGpuLastLookupFront", "awfmGpuLastSearchWasExactLookup", "awfmGpuSynthPlantedQueriesUnique", "awfmGpuStreamRetire", "awfmGpuIndexDescribe", "awfmGpuIndexDeepSeedAllocSeconds", "awfmGpuAosLastStages", "awfmHostCopyGBs",
     "awfmLocalPositions", "awfmGpuIndexSetRecordTable", "awfmGpuIndexNumRecords", "awfmGpuLocalPositions", "awfmGpuLocateHostLocal",
-    "awfmLongestSuffixMatches", "awfmGpuLongestSuffixMatches",
+    "awfmLongestSuffixMatches", "awfmGpuLongestSuffixMatches", "awfmOneSubstitutionSearch", "awfmGpuOneSubstitutionSearch",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -207,6 +207,8 @@ def lib():
         "awfmLocalPositions": (C.c_int, [IP, vp, u64, vp, vp, C.POINTER(u64), C.c_uint]),
         "awfmLongestSuffixMatches": (C.c_int, [IP, vp, vp, vp, C.c_uint32, u64, C.c_uint32, vp, vp, vp, C.c_uint]),
         "awfmGpuLongestSuffixMatches": (C.c_int, [vp, vp, vp, vp, C.c_uint32, u64, C.c_uint32, vp, vp, vp, vp]),
+        "awfmOneSubstitutionSearch": (C.c_int, [IP, vp, vp, C.c_uint32, u64, C.c_int, vp, vp, vp, u64, vp, vp, vp, C.c_uint]),
+        "awfmGpuOneSubstitutionSearch": (C.c_int, [vp, vp, vp, C.c_uint32, u64, C.c_int, vp, vp, vp, u64, vp, vp, vp, vp]),
         "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),
         "awfmGpuIndexNumRecords": (C.c_uint32, [vp]),
         "awfmGpuLocalPositions": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),

@@ -284,6 +284,47 @@ def longest_suffix_matches_host(index, chars, starts=None, ends=None, fixed_leng
     return lengths, ranges, counts
 
 
+AWFM_EDIT_NONE = 0xFFFFFFFF  # the edit of a record of the unedited query (include/awfm_gpu.h)
+
+
+def one_substitution_search_host(index, chars, offsets=None, fixed_length=0, include_exact=True, capacity=None, threads=4):
+    """awfmOneSubstitutionSearch: for query i = chars[offsets[i]:offsets[i + 1]] (offsets None: fixed_length characters per
+    query) one record per string at Hamming distance 1 that occurs in the text (edit = position * 32 + letter index), and with
+    include_exact one for the query itself (edit AWFM_EDIT_NONE) -> (queries uint32[k], edits uint32[k], ranges uint64[k, 2],
+    num_hits, variants uint32[n], occurrences uint64[n]), sorted by (query, edit).  capacity None: counts first, then fills
+    (k = num_hits); otherwise k = min(capacity, num_hits), num_hits stays the true number, the per-query arrays are complete."""
+    chars = np.ascontiguousarray(np.frombuffer(chars, np.uint8) if isinstance(chars, (bytes, bytearray)) else chars, dtype=np.uint8)
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.size - 1, 0)
+    else:
+        if fixed_length <= 0:
+            raise ValueError("queries need offsets or a fixed length")
+        n = chars.size // fixed_length
+    variants = np.zeros(n, np.uint32)
+    occurrences = np.zeros(n, np.uint64)
+    holder = chars if chars.size else np.zeros(1, np.uint8)
+    total = C.c_uint64(0)
+
+    def call(queries, edits, ranges, cap):
+        rc = _lib.lib().awfmOneSubstitutionSearch(index.ptr, holder.ctypes.data, offsets.ctypes.data if offsets is not None and n else None,
+                                                  fixed_length, n, 1 if include_exact else 0,
+                                                  queries.ctypes.data if cap else None, edits.ctypes.data if cap else None,
+                                                  ranges.ctypes.data if cap else None, cap, C.byref(total),
+                                                  variants.ctypes.data if n else None, occurrences.ctypes.data if n else None, threads)
+        _check("awfmOneSubstitutionSearch", rc)
+
+    if capacity is None:
+        call(None, None, None, 0)
+        capacity = int(total.value)
+    queries = np.zeros(capacity, np.uint32)
+    edits = np.zeros(capacity, np.uint32)
+    ranges = np.zeros((capacity, 2), np.uint64)
+    call(queries, edits, ranges, capacity)
+    k = min(capacity, int(total.value))
+    return queries[:k], edits[:k], ranges[:k], int(total.value), variants, occurrences
+
+
 # enum AwFmGpuKernel (include/awfm_gpu.h)
 AWFM_GPU_KERNEL_AUTO, AWFM_GPU_KERNEL_GROUP8, AWFM_GPU_KERNEL_GROUP4, AWFM_GPU_KERNEL_GROUP2, AWFM_GPU_KERNEL_GROUP1 = range(5)
 
@@ -579,6 +620,17 @@ class GpuIndex:
         _check("awfmGpuLongestSuffixMatches", _lib.lib().awfmGpuLongestSuffixMatches(
             self.handle, d_chars, d_starts or None, d_ends or None, fixed_length, n, min_length, d_lengths or None, d_ranges or None,
             d_counts or None, stream or None))
+
+    def one_substitution_search(self, d_chars, d_offsets, fixed_length, n, include_exact, d_hit_queries, d_hit_edits, d_hit_ranges,
+                                capacity, d_num_hits, d_variants, d_occurrences, stream=0):
+        """awfmGpuOneSubstitutionSearch on device addresses (0: NULL): the records {query, edit, range} of every string at
+        Hamming distance 1 of query i = chars[offsets[i]:offsets[i + 1]] (d_offsets = 0: fixed_length characters each) appended
+        to lists of `capacity` entries that were first filled with "no record"; *d_num_hits (uint64) = the true number of
+        records, d_variants (uint32[n]) / d_occurrences (uint64[n]) = records and summed range lengths per query.
+        Asynchronous on `stream`."""
+        _check("awfmGpuOneSubstitutionSearch", _lib.lib().awfmGpuOneSubstitutionSearch(
+            self.handle, d_chars, d_offsets, fixed_length, n, 1 if include_exact else 0, d_hit_queries, d_hit_edits, d_hit_ranges,
+            capacity, d_num_hits, d_variants, d_occurrences, stream))
 
     def search_hits(self, d_chars, d_offsets, fixed_length, n, d_ranges, d_counts, stream=0):
         """awfmGpuSearchHits: like search(), but a query without hits only gets count 0 and some empty range"""

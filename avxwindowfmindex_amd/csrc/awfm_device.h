@@ -618,6 +618,49 @@ __device__ __forceinline__ void nucStepAny(const DevIndex &ix, const unsigned lo
   nucStepAnyRank<G, NARROW>(ix, sC, sSuper, firstSlice, letter, p0, p1, sp, ep);
 }
 
+/* One backward step of a range with ALL four letters a,c,g,t at once, by the 4 lanes of a group (lane `slice` holds that slice
+ * of a block): each lane counts every letter on its slice of the two blocks, one groupSum per letter gives the four ranks, and
+ * lane k -- whose piece carries the count word of letter k -- leaves with the range of letter k.  One pair of block reads
+ * where four nucFastStep calls make four.  sp/ep themselves are not changed. */
+template <bool NARROW>
+__device__ __forceinline__ void nucStepAllLetters(const DevIndex &ix, const unsigned long long *sC, const unsigned long long *sSuper,
+                                                  const unsigned *sMask, unsigned slice, typename PositionType<NARROW>::type sp,
+                                                  typename PositionType<NARROW>::type ep, typename PositionType<NARROW>::type &spOfMine,
+                                                  typename PositionType<NARROW>::type &epOfMine) {
+  typedef typename PositionType<NARROW>::type pos_t;
+  const pos_t q0 = sp - 1, q1 = ep;
+  const unsigned long long blk0 = q0 >> kBlockShift, blk1 = q1 >> kBlockShift;
+  const bool same = blk0 == blk1;
+  Piece p0 = *(const Piece *)(ix.blocks + (blk0 * kSlices + slice)), p1;
+  asm volatile("" : "=v"(p1));
+  if (!same) p1 = *(const Piece *)(ix.blocks + (blk1 * kSlices + slice));
+  const unsigned mask0 = sMask[((unsigned)q0 & kBlockMask) * kSlices + slice];
+  const unsigned mask1 = sMask[((unsigned)q1 & kBlockMask) * kSlices + slice];
+  pos_t cLetter = (pos_t)sC[slice];
+  pos_t super1 = 0;
+  if (!NARROW) {
+    const unsigned long long s0 = sSuper[(unsigned)((unsigned long long)q0 >> ix.nucSuperShift) * 4u + slice];
+    const unsigned long long s1 = sSuper[(unsigned)((unsigned long long)q1 >> ix.nucSuperShift) * 4u + slice];
+    cLetter += (pos_t)s0;
+    super1 = (pos_t)(s1 - s0);
+  }
+  const unsigned sameMask = same ? ~0u : 0u;
+  unsigned mine = 0;
+#pragma unroll
+  for (unsigned letter = 0; letter < 4u; letter++) {
+    const unsigned c0m = 0u - (letter & 1u), c1m = 0u - (letter >> 1);
+    const unsigned occ0 = nucOccFast(p0, c0m, c1m), occ1 = nucOccFast(p1, c0m, c1m);
+    const unsigned n0 = __popc(occ0 & mask0);
+    const unsigned n1 = __popc(__builtin_amdgcn_bitop3_b32(occ0, occ1, sameMask, 0xE4) & mask1);
+    const unsigned packed = groupSum<4>(n0 | (n1 << 16));
+    mine = slice == letter ? packed : mine;
+  }
+  asm volatile("" ::"v"(p0), "v"(p1));
+  const unsigned base0 = p0.w, base1 = same ? p0.w : p1.w;
+  spOfMine = cLetter + (pos_t)base0 + (pos_t)(mine & 0xFFFFu);
+  epOfMine = cLetter + super1 + (pos_t)base1 + (pos_t)(mine >> 16) - (pos_t)1;
+}
+
 /* ------------------------------------------------------------------ amino */
 
 struct AminoTables {

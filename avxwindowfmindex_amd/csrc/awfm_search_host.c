@@ -235,3 +235,128 @@ enum AwFmReturnCode awfmLongestSuffixMatches(const struct AwFmIndex *index, cons
   awfmParallelFor(threads ? threads : 1, numQueries, awfmMatchRange, &ctx);
   return AwFmSuccess;
 }
+
+/* ---- one-substitution search (include/awfm_gpu.h: awfmOneSubstitutionSearch) ----
+ * The definition, letter by letter with the step above: no table enters it.  Per query the ranges S_j = R(q[j..m)) of the
+ * exact walk are kept; the variant (p, c) starts from one step of S_(p+1) with c (the initial range of c when p = m - 1) and
+ * walks on over q[p-1] .. q[0].  Two passes over the batch: the first counts, the second -- after a prefix sum over the
+ * counts -- stores the records of query i from slot first[i] on, which is the order by (query, edit). */
+struct awfmSubstCtx {
+  const struct AwFmIndex *index;
+  const uint8_t *chars;
+  const uint64_t *offsets;
+  uint32_t fixedLength;
+  int includeExact;
+  uint32_t *hitQueries, *hitEdits;
+  struct AwFmSearchRange *hitRanges;
+  uint64_t capacity;
+  uint64_t *first; /* numQueries + 1 words: pass 1 leaves the records of query i in first[i + 1] */
+  uint32_t *variants;
+  uint64_t *occurrences;
+  int store;
+  int failed;
+};
+
+static inline void awfmSubstEmit(const struct awfmSubstCtx *c, uint64_t slot, uint64_t query, uint32_t edit, struct AwFmSearchRange r) {
+  if (!c->store || slot >= c->capacity) return;
+  if (c->hitQueries) c->hitQueries[slot] = (uint32_t)query;
+  if (c->hitEdits) c->hitEdits[slot] = edit;
+  if (c->hitRanges) c->hitRanges[slot] = r;
+}
+
+static void awfmSubstRange(void *p, uint64_t begin, uint64_t end, unsigned tid) {
+  (void)tid;
+  struct awfmSubstCtx *c = p;
+  const struct AwFmIndex *ix = c->index;
+  const unsigned sigma = awfmIsAmino(ix) ? 20u : 4u;
+  struct AwFmSearchRange *suffix = NULL; /* suffix[j] = S_j, j = live .. m - 1 */
+  uint64_t room = 0;
+  for (uint64_t i = begin; i < end; i++) {
+    const uint64_t from = c->offsets ? c->offsets[i] : i * c->fixedLength;
+    const uint64_t to = c->offsets ? c->offsets[i + 1] : from + c->fixedLength;
+    uint64_t m = to > from ? to - from : 0;
+    if (m > 0xFFFFFFFFull) m = 0; /* such a query has no records */
+    const uint8_t *q = c->chars + from;
+    uint64_t slot = c->store ? c->first[i] : 0, records = 0, occurrences = 0;
+    if (m != 0) {
+      if (m > room) {
+        struct AwFmSearchRange *grown = realloc(suffix, m * sizeof *suffix);
+        if (!grown) {
+          __atomic_store_n(&c->failed, 1, __ATOMIC_RELAXED);
+          break;
+        }
+        suffix = grown;
+        room = m;
+      }
+      /* the exact walk: S_j for j = m - 1 down to `live`, the leftmost j with a non-empty S_j (m: none) */
+      uint64_t live = m;
+      struct AwFmSearchRange r = awFmCreateInitialQueryRangeFromChar(ix, (char)q[m - 1]);
+      for (uint64_t j = m; j-- != 0;) {
+        if (j != m - 1) hostStep(ix, &r, letterIndexOf(ix, (char)q[j]));
+        if (r.startPtr > r.endPtr) break;
+        suffix[j] = r;
+        live = j;
+      }
+      /* variants in the order of their edits: p ascending, then c; S_(p+1) must be non-empty */
+      const uint64_t firstP = live == m ? m - 1 : (live == 0 ? 0 : live - 1);
+      for (uint64_t at = firstP; at < m && at < (1ull << 27); at++) {
+        const uint8_t own = letterIndexOf(ix, (char)q[at]);
+        for (unsigned letter = 0; letter < sigma; letter++) {
+          if (letter == own) continue;
+          struct AwFmSearchRange v;
+          if (at == m - 1) {
+            v = (struct AwFmSearchRange){ix->prefixSums[letter], ix->prefixSums[letter + 1] - 1};
+          } else {
+            v = suffix[at + 1];
+            hostStep(ix, &v, (uint8_t)letter);
+          }
+          for (uint64_t j = at; v.startPtr <= v.endPtr && j-- != 0;) hostStep(ix, &v, letterIndexOf(ix, (char)q[j]));
+          if (v.startPtr > v.endPtr) continue;
+          awfmSubstEmit(c, slot + records, i, (uint32_t)(at * 32u + letter), v);
+          records++;
+          occurrences += v.endPtr - v.startPtr + 1;
+        }
+      }
+      if (c->includeExact && live == 0) {
+        awfmSubstEmit(c, slot + records, i, AWFM_EDIT_NONE, suffix[0]);
+        records++;
+        occurrences += suffix[0].endPtr - suffix[0].startPtr + 1;
+      }
+    }
+    if (!c->store) {
+      c->first[i + 1] = records;
+      if (c->variants) c->variants[i] = (uint32_t)records;
+      if (c->occurrences) c->occurrences[i] = occurrences;
+    }
+  }
+  free(suffix);
+}
+
+enum AwFmReturnCode awfmOneSubstitutionSearch(const struct AwFmIndex *index, const uint8_t *chars, const uint64_t *offsets,
+                                              uint32_t fixedLength, uint64_t numQueries, int includeExact, uint32_t *hitQueries,
+                                              uint32_t *hitEdits, struct AwFmSearchRange *hitRanges, uint64_t capacity,
+                                              uint64_t *numHits, uint32_t *variantsPerQuery, uint64_t *occurrencesPerQuery,
+                                              unsigned threads) {
+  if (!index) return AwFmNullPtrError;
+  if (numQueries == 0) return AwFmSuccess;
+  if (numQueries >= (1ull << 32)) return AwFmIllegalPositionError; /* query numbers are 32-bit */
+  if (!chars || (!offsets && fixedLength == 0)) return AwFmNullPtrError;
+  uint64_t *first = malloc((numQueries + 1) * sizeof *first);
+  if (!first) return AwFmAllocationFailure;
+  struct awfmSubstCtx ctx = {index, chars, offsets, fixedLength, includeExact, hitQueries, hitEdits, hitRanges, capacity,
+                             first, variantsPerQuery, occurrencesPerQuery, 0, 0};
+  awfmParallelFor(threads ? threads : 1, numQueries, awfmSubstRange, &ctx);
+  if (__atomic_load_n(&ctx.failed, __ATOMIC_RELAXED)) { /* a worker ran out of memory: its counts are incomplete, nothing is reported */
+    free(first);
+    return AwFmAllocationFailure;
+  }
+  first[0] = 0;
+  for (uint64_t i = 0; i < numQueries; i++) first[i + 1] += first[i];
+  if (numHits) *numHits = first[numQueries];
+  if (capacity != 0 && (hitQueries || hitEdits || hitRanges)) {
+    ctx.store = 1;
+    awfmParallelFor(threads ? threads : 1, numQueries, awfmSubstRange, &ctx);
+  }
+  free(first);
+  return __atomic_load_n(&ctx.failed, __ATOMIC_RELAXED) ? AwFmAllocationFailure : AwFmSuccess;
+}

@@ -18,6 +18,9 @@
  *                          awFmCreateInitialQueryRangeFromChar and the iterative step
  *                          functions (ref src/AwFmSearch.c:27-159): step until the range
  *                          empties, keep the last range that had hits and its depth
+ *   awfmGpuOneSubstitutionSearch  the same caller's next loop: the ranges of every string at Hamming
+ *                          distance 1 of a k-mer, from the same two functions (ref src/AwFmSearch.c:27-159,
+ *                          :317-358), without enumerating the 3m + 1 strings
  *   awfmGpuHitOffsets      the per-query sizing of setPositionListCount
  *                          (ref src/AwFmParallelSearch.c:327-328, :367-387) as
  *                          one exclusive scan
@@ -245,6 +248,51 @@ enum AwFmReturnCode awfmGpuLongestSuffixMatches(AwFmGpuIndex *g, const uint8_t *
                                                 const uint64_t *dEnds, uint32_t fixedLength, uint64_t numQueries,
                                                 uint32_t minLength, uint32_t *dMatchLengths, struct AwFmSearchRange *dRanges,
                                                 uint32_t *dCounts, void *stream);
+
+/* ---- one substitution: every string at Hamming distance 1 of a query that occurs, and where ----
+ * PROPER LETTERS are the letter indices 0 .. sigma-1 of the library's mapping (awfmNucAsciiToIndex / awfmAminoAsciiToIndex):
+ * sigma = 4 for nucleotide, 20 for amino.  For a query q[0..m) the VARIANT (p, c) is q with position p replaced by the proper
+ * letter c, where c differs from the letter index of q[p] (q[p] an ambiguity letter: all sigma letters qualify).  The RANGE of a
+ * string s, R(s), is what awFmFindSearchRangeForString computes: awFmCreateInitialQueryRangeFromChar of its last character,
+ * then one backward step per character leftwards until the range is empty.  A non-empty R(s) is unique: no table, pair image
+ * or position width changes a result.  A RECORD {query number, edit, range} exists for every variant with a non-empty R, and,
+ * with includeExact != 0, for q itself when R(q) is non-empty.  edit = p * 32 + c for a variant and AWFM_EDIT_NONE for the
+ * unedited query.  Positions p >= 2^27 are NOT substituted (the edit has 27 bits for p); ambiguity letters elsewhere in q step
+ * like any letter, as in awfmGpuSearch; m = 0 gives no records, and so does a query of more than 2^32 - 1 characters.
+ *
+ * Queries as awfmGpuSearch takes them: offsets[numQueries + 1] into chars, or, offsets NULL, fixedLength characters each.  The
+ * records are three parallel arrays (hitQueries, hitEdits, hitRanges) of `capacity` entries; *numHits is the TRUE number of
+ * records and may exceed capacity.  variantsPerQuery[i] = the records of query i, occurrencesPerQuery[i] = the sum of their
+ * range lengths: both complete whatever the capacity.  Every output may be NULL (capacity 0 with NULL lists: counts only).
+ * numQueries == 0 succeeds and touches nothing; numQueries >= 2^32 is refused (AwFmIllegalPositionError: query numbers are
+ * 32-bit); missing chars, or neither offsets nor a fixedLength: AwFmNullPtrError.
+ *
+ * awfmOneSubstitutionSearch: the definition, letter by letter on the host over `threads` threads of the library's pool, no
+ * table.  Records sorted by (query, edit) -- the unedited query last among its own --; beyond capacity the first `capacity`
+ * records of that order are stored.
+ * awfmGpuOneSubstitutionSearch (csrc/awfm_subst_kernel.h): asynchronous on `stream`, no host wait, no allocation, none of the
+ * handle's scratch slots: two streams may run it on one image at the same time.  Before the kernel runs the lists are filled up
+ * to capacity with {0xFFFFFFFF, 0xFFFFFFFF, {1, 0}} and *dNumHits is zeroed, so that the list AT ITS CAPACITY goes straight into
+ * awfmGpuHitOffsetsOnDevice(g, NULL, dHitRanges, capacity, ...) and awfmGpuLocateOnDevice: positions per record, dHitQueries /
+ * dHitEdits say whose.  The order of the list is whatever order the waves append in; beyond capacity SOME capacity distinct
+ * records of the true set are stored.  WHERE THE DEVICE CALL DIFFERS FROM THE HOST'S: the host fills any one list alone, numHits
+ * NULL or not; the device appends through the counter *dNumHits (it allocates nothing, so it has no counter of its own), and a
+ * call with a non-zero capacity and any list but without dNumHits is refused (AwFmNullPtrError).  Every other output may be NULL
+ * on both sides.  One branch step gives the ranges of all sigma letters from one pair of block reads; a substitution
+ * inside the span of the deeper table (or the index's own) costs one gather of the variant's entry.  With awfmGpuIndexSetKernel
+ * set to anything but AUTO or GROUP4 the kernel runs letter by letter and reads no table.  dChars is read only in aligned
+ * 4-byte words that hold at least one byte of the query they are read for. */
+#define AWFM_EDIT_NONE 0xFFFFFFFFu
+enum AwFmReturnCode awfmOneSubstitutionSearch(const struct AwFmIndex *index, const uint8_t *chars, const uint64_t *offsets,
+                                              uint32_t fixedLength, uint64_t numQueries, int includeExact, uint32_t *hitQueries,
+                                              uint32_t *hitEdits, struct AwFmSearchRange *hitRanges, uint64_t capacity,
+                                              uint64_t *numHits, uint32_t *variantsPerQuery, uint64_t *occurrencesPerQuery,
+                                              unsigned threads);
+enum AwFmReturnCode awfmGpuOneSubstitutionSearch(AwFmGpuIndex *g, const uint8_t *dChars, const uint64_t *dOffsets,
+                                                 uint32_t fixedLength, uint64_t numQueries, int includeExact,
+                                                 uint32_t *dHitQueries, uint32_t *dHitEdits, struct AwFmSearchRange *dHitRanges,
+                                                 uint64_t capacity, uint64_t *dNumHits, uint32_t *dVariantsPerQuery,
+                                                 uint64_t *dOccurrencesPerQuery, void *stream);
 
 /* Hits-only variant of awfmGpuSearch, for callers that go on to count or locate (what
  * awFmParallelSearchCount/Locate report: ref src/AwFmParallelSearch.c:159-220, :315-365): queries with hits get
