@@ -41,6 +41,7 @@ GPU_SYMBOLS = [
     "awfmGpuListLocateOnDevice", "awfmGpuLastLookupFront", "awfmGpuLastSearchWasExactLookup", "awfmGpuSynthPlantedQueriesUnique", "awfmGpuStreamRetire", "awfmGpuIndexDescribe", "awfmGpuIndexDeepSeedAllocSeconds", "awfmGpuAosLastStages", "awfmHostCopyGBs",
     "awfmLocalPositions", "awfmGpuIndexSetRecordTable", "awfmGpuIndexNumRecords", "awfmGpuLocalPositions", "awfmGpuLocateHostLocal",
     "awfmLongestSuffixMatches", "awfmGpuLongestSuffixMatches", "awfmOneSubstitutionSearch", "awfmGpuOneSubstitutionSearch",
+    "awfmReadCandidates", "awfmGpuReadCandidates", "awfmGpuReadCandidatesScratchBytes",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -66,6 +67,20 @@ class AwFmCompressedSuffixArray(C.Structure):
 
 class AwFmSearchRange(C.Structure):
     _fields_ = [("startPtr", C.c_uint64), ("endPtr", C.c_uint64)]
+
+
+class AwFmCandidateInputs(C.Structure):
+    """struct AwFmCandidateInputs (include/awfm_gpu.h): host or device addresses"""
+    _fields_ = [("readSeedOffsets", C.c_void_p), ("numSeeds", C.c_uint64), ("seedEnds", C.c_void_p), ("seedLengths", C.c_void_p),
+                ("fixedLength", C.c_uint32), ("hitOffsets", C.c_void_p), ("numHits", C.c_uint64), ("positions", C.c_void_p),
+                ("sequenceNumbers", C.c_void_p)]
+
+
+class AwFmCandidateOutputs(C.Structure):
+    """struct AwFmCandidateOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("sequences", C.c_void_p), ("diagonals", C.c_void_p), ("votes", C.c_void_p), ("diagonalSpans", C.c_void_p),
+                ("readBegins", C.c_void_p), ("readEnds", C.c_void_p), ("numCandidates", C.c_void_p), ("keptHits", C.c_void_p),
+                ("numOverflowed", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -209,6 +224,11 @@ def lib():
         "awfmGpuLongestSuffixMatches": (C.c_int, [vp, vp, vp, vp, C.c_uint32, u64, C.c_uint32, vp, vp, vp, vp]),
         "awfmOneSubstitutionSearch": (C.c_int, [IP, vp, vp, C.c_uint32, u64, C.c_int, vp, vp, vp, u64, vp, vp, vp, C.c_uint]),
         "awfmGpuOneSubstitutionSearch": (C.c_int, [vp, vp, vp, C.c_uint32, u64, C.c_int, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "awfmReadCandidates": (C.c_int, [C.POINTER(AwFmCandidateInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.POINTER(AwFmCandidateOutputs), C.c_uint]),
+        "awfmGpuReadCandidatesScratchBytes": (u64, [u64]),
+        "awfmGpuReadCandidates": (C.c_int, [vp, C.POINTER(AwFmCandidateInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.POINTER(AwFmCandidateOutputs), vp, vp]),
         "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),
         "awfmGpuIndexNumRecords": (C.c_uint32, [vp]),
         "awfmGpuLocalPositions": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),

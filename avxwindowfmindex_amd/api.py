@@ -284,6 +284,80 @@ def longest_suffix_matches_host(index, chars, starts=None, ends=None, fixed_leng
     return lengths, ranges, counts
 
 
+CANDIDATES_MAX_HITS = 4096  # AWFM_CANDIDATES_MAX_HITS: kept hits per read beyond which a read is overflowed (include/awfm_gpu.h)
+CANDIDATES_NONE = 0xFFFFFFFF  # the sequence of an unused candidate slot
+CANDIDATE_SLOT_OUTPUTS = (("sequences", np.uint32), ("diagonals", np.int64), ("votes", np.uint32), ("diagonalSpans", np.uint32),
+                          ("readBegins", np.uint32), ("readEnds", np.uint32))
+CANDIDATE_READ_OUTPUTS = (("numCandidates", np.uint32), ("keptHits", np.uint32))
+
+
+def candidate_inputs(read_seed_offsets, num_seeds, seed_ends, seed_lengths, fixed_length, hit_offsets, num_hits, positions,
+                     sequence_numbers):
+    """struct AwFmCandidateInputs from addresses (ints; 0 or None: NULL), host or device alike"""
+    return _lib.AwFmCandidateInputs(read_seed_offsets or None, num_seeds, seed_ends or None, seed_lengths or None, fixed_length,
+                                    hit_offsets or None, num_hits, positions or None, sequence_numbers or None)
+
+
+def candidate_outputs(**addresses):
+    """struct AwFmCandidateOutputs from addresses by field name (sequences, diagonals, votes, diagonalSpans, readBegins, readEnds,
+    numCandidates, keptHits, numOverflowed); a field left out is NULL"""
+    out = _lib.AwFmCandidateOutputs()
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmCandidateOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def read_candidates_host(read_seed_offsets, seed_ends, hit_offsets, positions, sequence_numbers=None, seed_lengths=None, fixed_length=0,
+                         max_hits_per_seed=0, band=0, min_votes=1, max_candidates=4, threads=4, outputs=None, num_seeds=None,
+                         num_hits=None, fill=None, overflowed_before=0):
+    """awfmReadCandidates (include/awfm_gpu.h, "candidate loci"): the seeds [read_seed_offsets[r], read_seed_offsets[r + 1]) of
+    read r, their hits [hit_offsets[s], hit_offsets[s + 1]) of positions / sequence_numbers -> a dict of the outputs by field
+    name: the six per-slot arrays shaped (reads, max_candidates), numCandidates and keptHits per read, numOverflowed (an int:
+    overflowed_before plus this call's).  outputs: the names to compute (None: all); the others are passed as NULL and left out.
+    num_seeds / num_hits default to the arrays' sizes; fill: the value (per byte) the arrays hold before the call."""
+    o = np.ascontiguousarray(read_seed_offsets, dtype=np.uint64)
+    ends = np.ascontiguousarray(seed_ends, dtype=np.uint32)
+    ho = np.ascontiguousarray(hit_offsets, dtype=np.uint64)
+    pos = np.ascontiguousarray(positions, dtype=np.uint64)
+    sn = None if sequence_numbers is None else np.ascontiguousarray(sequence_numbers, dtype=np.uint32)
+    lengths = None if seed_lengths is None else np.ascontiguousarray(seed_lengths, dtype=np.uint32)
+    n = max(o.size - 1, 0)
+    names = [name for name, _ in CANDIDATE_SLOT_OUTPUTS + CANDIDATE_READ_OUTPUTS] + ["numOverflowed"]
+    outputs = names if outputs is None else list(outputs)
+    result = {}
+    for name, dtype in CANDIDATE_SLOT_OUTPUTS + CANDIDATE_READ_OUTPUTS:
+        if name in outputs:
+            shape = (n, max_candidates) if (name, dtype) in CANDIDATE_SLOT_OUTPUTS else (n,)
+            result[name] = np.zeros(shape, dtype)
+            if fill is not None:
+                result[name].view(np.uint8)[...] = fill
+    overflowed = np.array([overflowed_before], np.uint64)
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else None
+
+    cin = candidate_inputs(address(o), ends.size if num_seeds is None else num_seeds, address(ends), address(lengths), fixed_length,
+                           address(ho), pos.size if num_hits is None else num_hits, address(pos), address(sn))
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+    if lengths is not None and not lengths.size:  # (an empty array is still "lengths per seed")
+        cin.seedLengths = dummy.ctypes.data
+    cout = candidate_outputs(**{name: result[name].ctypes.data if result[name].size else dummy.ctypes.data for name in result})
+    if "numOverflowed" in outputs:
+        cout.numOverflowed = overflowed.ctypes.data
+    rc = _lib.lib().awfmReadCandidates(C.byref(cin), n, max_hits_per_seed, band, min_votes, max_candidates, C.byref(cout), threads)
+    _check("awfmReadCandidates", rc)
+    if "numOverflowed" in outputs:
+        result["numOverflowed"] = int(overflowed[0])
+    return result
+
+
+def read_candidates_scratch_bytes(n):
+    """awfmGpuReadCandidatesScratchBytes: the bytes of device scratch GpuIndex.read_candidates needs for n reads"""
+    return int(_lib.lib().awfmGpuReadCandidatesScratchBytes(n))
+
+
 AWFM_EDIT_NONE = 0xFFFFFFFF  # the edit of a record of the unedited query (include/awfm_gpu.h)
 
 
@@ -455,6 +529,14 @@ class GpuIndex:
         (sequence number, local position) on the device; d_local may be d_positions; *d_num_illegal is added to"""
         _check("awfmGpuLocalPositions", _lib.lib().awfmGpuLocalPositions(self.handle, d_positions or None, capacity, d_num_positions or None,
                                                                          d_seq or None, d_local or None, d_num_illegal or None, stream or None))
+
+    def read_candidates(self, inputs, num_reads, outputs, d_scratch, max_hits_per_seed=0, band=0, min_votes=1, max_candidates=4, stream=0):
+        """awfmGpuReadCandidates: inputs / outputs are candidate_inputs(...) / candidate_outputs(...) of device addresses, d_scratch
+        read_candidates_scratch_bytes(num_reads) bytes of device memory of this call's own; asynchronous on `stream`;
+        *numOverflowed is added to"""
+        _check("awfmGpuReadCandidates", _lib.lib().awfmGpuReadCandidates(
+            self.handle, C.byref(inputs), num_reads, max_hits_per_seed, band, min_votes, max_candidates, C.byref(outputs),
+            d_scratch or None, stream or None))
 
     def locate_host_local(self, chars, offsets=None, fixed_length=0):
         """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],

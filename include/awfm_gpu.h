@@ -78,7 +78,9 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   nuc_super_shift=13..31|auto   nucleotide superblocks of 2^shift positions: the arithmetic of images of 2^32 positions
  *                       and more on small ones
  *   record_lookup=lds|dir   which lookup a record table gets when it is installed (default: by its size; lds only where it fits)
- *   stream_trace=1, aos_trace=1   host timelines of the chunked pipelines / the AoS lanes on stderr */
+ *   candidates_tier=wave|group   awfmGpuReadCandidates: group sends every read with a kept hit to the workgroup tier; wave is the
+ *                       default (a read of up to 256 kept hits takes the wave tier) and changes nothing
+ *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
 
 /* ---- device image ---- */
 /* Builds the device image of `index` on GPU `device` (-1: current device or
@@ -388,6 +390,81 @@ enum AwFmReturnCode awfmGpuListLocateOnDevice(AwFmGpuIndex *g, const uint32_t *d
  * AwFmUnsupportedVersionError when the image has no record table. */
 enum AwFmReturnCode awfmGpuLocalPositions(AwFmGpuIndex *g, const uint64_t *dPositions, uint64_t capacity, const uint64_t *dNumPositions,
                                           uint32_t *dSequenceNumbers, uint64_t *dLocalPositions, uint64_t *dNumIllegal, void *stream);
+
+/* ---- candidate loci: the located seeds of a read, grouped by (sequence, diagonal) ----
+ * The stage after awfmGpuLocalPositions for a caller that maps reads: one definition on both sides, the host twin being the
+ * definition and the checker of the device call.  (The reference stops at positions: ref src/AwFmParallelSearch.c:315-365.)
+ *
+ * READS AND SEEDS.  The seeds of read r are the seed numbers [readSeedOffsets[r], readSeedOffsets[r + 1]) of numSeeds seeds
+ * (windows over reads and the k-mers of reads are contiguous per read in read order).  Seed s ends at seedEnds[s], the offset
+ * in its read one past its last character, and is seedLengths[s] characters long (seedLengths NULL: fixedLength each; the
+ * dMatchLengths of awfmGpuLongestSuffixMatches go in as they are).  Its ANCHOR is a = seedEnds[s] - length; a seed with
+ * length > seedEnds[s] contributes no hit.  Its hits are the entries [hitOffsets[s], hitOffsets[s + 1]) of positions /
+ * sequenceNumbers (numHits entries; sequenceNumbers NULL: every hit lies in sequence 0 and positions are global).  A seed with
+ * more than maxHitsPerSeed hits contributes none (0: no limit; the usual repeat filter), and hits of sequence 0xFFFFFFFF (the
+ * illegal positions of awfmGpuLocalPositions) are dropped.  What remains are the read's KEPT HITS.
+ *
+ * CLUSTERS.  A kept hit has the diagonal D = (int64_t)position - a (negative where the read overhangs its sequence's start).
+ * The kept hits of a read are ordered by (sequence ascending, D ascending as a signed value); a cluster is a maximal run in that
+ * order whose neighbours have the same sequence and D[k + 1] - D[k] <= band.  Its votes are the hits of the run -- a seed with
+ * two hits inside one band votes twice --, its diagonal is the run's smallest D, its span the largest D minus the smallest,
+ * saturated at 2^32 - 1, and its read interval runs from the smallest anchor to the largest seedEnd of the run.
+ *
+ * CANDIDATES.  A cluster with votes >= max(minVotes, 1) is a candidate; a read's candidates are ordered by (votes descending,
+ * sequence ascending, diagonal ascending).  With C = maxCandidates (1..16), the first min(C, number of candidates) candidates of
+ * read r are stored at r * C + j in the six per-slot arrays, and the remaining slots of the read hold {sequence 0xFFFFFFFF, 0,
+ * 0, 0, 0, 0}.  numCandidates[r] is the true number (it may exceed C), keptHits[r] the read's kept hits.
+ *
+ * LIMIT.  AWFM_CANDIDATES_MAX_HITS kept hits per read is part of the definition on both sides.  A read with more is
+ * OVERFLOWED: no candidates (all slots hold the fill, numCandidates 0), keptHits = the true number saturated at 0xFFFFFFFE, and
+ * it is counted in *numOverflowed, which is ADDED to (zero it first); the caller re-runs such reads with a stricter
+ * maxHitsPerSeed.  A read is MALFORMED when its seed range is inverted, leaves [0, numSeeds] or holds 2^32 seeds or more, or
+ * when the hit range of any of its seeds is inverted or leaves [0, numHits]: it is reported like an overflowed read, with
+ * keptHits = 0xFFFFFFFF.  Neither side reads outside the arrays it was given, whatever the offsets say.
+ *
+ * Every output may be NULL.  numReads == 0 succeeds and touches nothing; a missing input array (sequenceNumbers and seedLengths
+ * apart), or neither seedLengths nor a fixedLength: AwFmNullPtrError; numReads >= 2^32 or maxCandidates outside 1..16:
+ * AwFmIllegalPositionError.
+ *
+ * awfmReadCandidates: on the host over `threads` threads of the library's pool, one read at a time: collect, qsort, scan, select.
+ * awfmGpuReadCandidates (csrc/awfm_candidates_kernel.h): the same on device arrays (both structs live on the host and hold
+ * device addresses); asynchronous on `stream`, no host wait, no allocation, none of the handle's scratch slots: two streams may
+ * run it on one image at once, each with its own dScratch of awfmGpuReadCandidatesScratchBytes(numReads) bytes.  One wave per read
+ * gathers the read's stretch of hits, and sorts and scans reads of up to 256 kept hits in LDS; larger reads go onto a worklist
+ * in dScratch, which a second launch reads on the device and gives a workgroup each.  `g` names the device and takes the error
+ * text; the call reads nothing of the index. */
+#define AWFM_CANDIDATES_MAX_HITS 4096u
+#define AWFM_CANDIDATES_MAX_SLOTS 16u
+#define AWFM_CANDIDATES_NONE 0xFFFFFFFFu /* the sequence of an unused slot */
+struct AwFmCandidateInputs {
+  const uint64_t *readSeedOffsets; /* [numReads + 1] */
+  uint64_t numSeeds;
+  const uint32_t *seedEnds;    /* [numSeeds] */
+  const uint32_t *seedLengths; /* [numSeeds], or NULL: fixedLength */
+  uint32_t fixedLength;
+  const uint64_t *hitOffsets; /* [numSeeds + 1] */
+  uint64_t numHits;
+  const uint64_t *positions;       /* [numHits] */
+  const uint32_t *sequenceNumbers; /* [numHits], or NULL: sequence 0 */
+};
+struct AwFmCandidateOutputs {
+  uint32_t *sequences; /* the six per-slot arrays: [numReads * maxCandidates] */
+  int64_t *diagonals;
+  uint32_t *votes;
+  uint32_t *diagonalSpans;
+  uint32_t *readBegins;
+  uint32_t *readEnds;
+  uint32_t *numCandidates; /* [numReads] */
+  uint32_t *keptHits;      /* [numReads] */
+  uint64_t *numOverflowed; /* one counter, added to */
+};
+enum AwFmReturnCode awfmReadCandidates(const struct AwFmCandidateInputs *in, uint64_t numReads, uint32_t maxHitsPerSeed, uint32_t band,
+                                       uint32_t minVotes, uint32_t maxCandidates, const struct AwFmCandidateOutputs *out,
+                                       unsigned threads);
+uint64_t awfmGpuReadCandidatesScratchBytes(uint64_t numReads);
+enum AwFmReturnCode awfmGpuReadCandidates(AwFmGpuIndex *g, const struct AwFmCandidateInputs *dIn, uint64_t numReads,
+                                          uint32_t maxHitsPerSeed, uint32_t band, uint32_t minVotes, uint32_t maxCandidates,
+                                          const struct AwFmCandidateOutputs *dOut, void *dScratch, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
