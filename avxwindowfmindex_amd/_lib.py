@@ -42,6 +42,7 @@ GPU_SYMBOLS = [
     "awfmLocalPositions", "awfmGpuIndexSetRecordTable", "awfmGpuIndexNumRecords", "awfmGpuLocalPositions", "awfmGpuLocateHostLocal",
     "awfmLongestSuffixMatches", "awfmGpuLongestSuffixMatches", "awfmOneSubstitutionSearch", "awfmGpuOneSubstitutionSearch",
     "awfmReadCandidates", "awfmGpuReadCandidates", "awfmGpuReadCandidatesScratchBytes",
+    "awfmReadChains", "awfmGpuReadChains", "awfmGpuReadChainsScratchBytes",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -80,6 +81,13 @@ class AwFmCandidateOutputs(C.Structure):
     """struct AwFmCandidateOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
     _fields_ = [("sequences", C.c_void_p), ("diagonals", C.c_void_p), ("votes", C.c_void_p), ("diagonalSpans", C.c_void_p),
                 ("readBegins", C.c_void_p), ("readEnds", C.c_void_p), ("numCandidates", C.c_void_p), ("keptHits", C.c_void_p),
+                ("numOverflowed", C.c_void_p)]
+
+
+class AwFmChainOutputs(C.Structure):
+    """struct AwFmChainOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("chainScores", C.c_void_p), ("chainAnchors", C.c_void_p), ("chainReadBegins", C.c_void_p), ("chainReadEnds", C.c_void_p),
+                ("chainBeginDiagonals", C.c_void_p), ("chainEndDiagonals", C.c_void_p), ("bestSlots", C.c_void_p), ("keptHits", C.c_void_p),
                 ("numOverflowed", C.c_void_p)]
 
 
@@ -229,6 +237,11 @@ def lib():
         "awfmGpuReadCandidatesScratchBytes": (u64, [u64]),
         "awfmGpuReadCandidates": (C.c_int, [vp, C.POINTER(AwFmCandidateInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.POINTER(AwFmCandidateOutputs), vp, vp]),
+        "awfmReadChains": (C.c_int, [C.POINTER(AwFmCandidateInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32,
+                                     C.c_uint32, C.POINTER(AwFmChainOutputs), C.c_uint]),
+        "awfmGpuReadChainsScratchBytes": (u64, [u64]),
+        "awfmGpuReadChains": (C.c_int, [vp, C.POINTER(AwFmCandidateInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32,
+                                        C.c_uint32, C.POINTER(AwFmChainOutputs), vp, vp]),
         "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),
         "awfmGpuIndexNumRecords": (C.c_uint32, [vp]),
         "awfmGpuLocalPositions": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),

@@ -358,6 +358,81 @@ def read_candidates_scratch_bytes(n):
     return int(_lib.lib().awfmGpuReadCandidatesScratchBytes(n))
 
 
+CHAINS_MAX_LOOKBACK = 64  # AWFM_CHAINS_MAX_LOOKBACK: the predecessors an anchor looks back at, at the most
+CHAINS_NO_SLOT = 0xFFFFFFFF  # bestSlots of a read without an anchor
+CHAIN_SLOT_OUTPUTS = (("chainScores", np.uint32), ("chainAnchors", np.uint32), ("chainReadBegins", np.uint32), ("chainReadEnds", np.uint32),
+                      ("chainBeginDiagonals", np.int64), ("chainEndDiagonals", np.int64))
+CHAIN_READ_OUTPUTS = (("bestSlots", np.uint32), ("keptHits", np.uint32))
+
+
+def chain_outputs(**addresses):
+    """struct AwFmChainOutputs from addresses by field name (chainScores, chainAnchors, chainReadBegins, chainReadEnds,
+    chainBeginDiagonals, chainEndDiagonals, bestSlots, keptHits, numOverflowed); a field left out is NULL"""
+    out = _lib.AwFmChainOutputs()
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmChainOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def read_chains_host(read_seed_offsets, seed_ends, hit_offsets, positions, slot_sequences, slot_diagonals, slot_spans, sequence_numbers=None,
+                     seed_lengths=None, fixed_length=0, max_hits_per_seed=0, band=0, lookback=CHAINS_MAX_LOOKBACK, gap_penalty=0, threads=4,
+                     outputs=None, num_seeds=None, num_hits=None, fill=None, overflowed_before=0):
+    """awfmReadChains (include/awfm_gpu.h, "read chains"): the inputs of read_candidates_host and the slot arrays it returned
+    (sequences, diagonals, diagonalSpans, shaped (reads, max_candidates)) -> a dict of the outputs by field name: the six per-slot
+    arrays shaped like the slots, bestSlots and keptHits per read, numOverflowed (an int: overflowed_before plus this call's).
+    outputs: the names to compute (None: all); the others are passed as NULL and left out.  num_seeds / num_hits default to the
+    arrays' sizes; fill: the value (per byte) the arrays hold before the call."""
+    o = np.ascontiguousarray(read_seed_offsets, dtype=np.uint64)
+    ends = np.ascontiguousarray(seed_ends, dtype=np.uint32)
+    ho = np.ascontiguousarray(hit_offsets, dtype=np.uint64)
+    pos = np.ascontiguousarray(positions, dtype=np.uint64)
+    sn = None if sequence_numbers is None else np.ascontiguousarray(sequence_numbers, dtype=np.uint32)
+    lengths = None if seed_lengths is None else np.ascontiguousarray(seed_lengths, dtype=np.uint32)
+    n = max(o.size - 1, 0)
+    slot_seq = np.ascontiguousarray(slot_sequences, dtype=np.uint32)
+    slot_diag = np.ascontiguousarray(slot_diagonals, dtype=np.int64)
+    slot_span = np.ascontiguousarray(slot_spans, dtype=np.uint32)
+    if slot_seq.ndim != 2 or slot_seq.shape[0] != n or slot_diag.shape != slot_seq.shape or slot_span.shape != slot_seq.shape:
+        raise ValueError("the slot arrays are shaped (reads, max_candidates)")
+    max_candidates = slot_seq.shape[1]
+    names = [name for name, _ in CHAIN_SLOT_OUTPUTS + CHAIN_READ_OUTPUTS] + ["numOverflowed"]
+    outputs = names if outputs is None else list(outputs)
+    result = {}
+    for name, dtype in CHAIN_SLOT_OUTPUTS + CHAIN_READ_OUTPUTS:
+        if name in outputs:
+            shape = (n, max_candidates) if (name, dtype) in CHAIN_SLOT_OUTPUTS else (n,)
+            result[name] = np.zeros(shape, dtype)
+            if fill is not None:
+                result[name].view(np.uint8)[...] = fill
+    overflowed = np.array([overflowed_before], np.uint64)
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else None
+
+    cin = candidate_inputs(address(o), ends.size if num_seeds is None else num_seeds, address(ends), address(lengths), fixed_length,
+                           address(ho), pos.size if num_hits is None else num_hits, address(pos), address(sn))
+    if lengths is not None and not lengths.size:  # (an empty array is still "lengths per seed")
+        cin.seedLengths = dummy.ctypes.data
+    cout = chain_outputs(**{name: result[name].ctypes.data if result[name].size else dummy.ctypes.data for name in result})
+    if "numOverflowed" in outputs:
+        cout.numOverflowed = overflowed.ctypes.data
+    rc = _lib.lib().awfmReadChains(C.byref(cin), n, max_hits_per_seed, band, max_candidates, address(slot_seq) or dummy.ctypes.data,
+                                   address(slot_diag) or dummy.ctypes.data, address(slot_span) or dummy.ctypes.data, lookback, gap_penalty,
+                                   C.byref(cout), threads)
+    _check("awfmReadChains", rc)
+    if "numOverflowed" in outputs:
+        result["numOverflowed"] = int(overflowed[0])
+    return result
+
+
+def read_chains_scratch_bytes(n):
+    """awfmGpuReadChainsScratchBytes: the bytes of device scratch GpuIndex.read_chains needs for n reads"""
+    return int(_lib.lib().awfmGpuReadChainsScratchBytes(n))
+
+
 AWFM_EDIT_NONE = 0xFFFFFFFF  # the edit of a record of the unedited query (include/awfm_gpu.h)
 
 
@@ -537,6 +612,15 @@ class GpuIndex:
         _check("awfmGpuReadCandidates", _lib.lib().awfmGpuReadCandidates(
             self.handle, C.byref(inputs), num_reads, max_hits_per_seed, band, min_votes, max_candidates, C.byref(outputs),
             d_scratch or None, stream or None))
+
+    def read_chains(self, inputs, num_reads, d_sequences, d_diagonals, d_spans, outputs, d_scratch, max_hits_per_seed=0, band=0,
+                    max_candidates=4, lookback=CHAINS_MAX_LOOKBACK, gap_penalty=0, stream=0):
+        """awfmGpuReadChains: inputs as for read_candidates, d_sequences / d_diagonals / d_spans the slot arrays it wrote, outputs
+        chain_outputs(...) of device addresses, d_scratch read_chains_scratch_bytes(num_reads) bytes of device memory of this
+        call's own; asynchronous on `stream`; *numOverflowed is added to"""
+        _check("awfmGpuReadChains", _lib.lib().awfmGpuReadChains(
+            self.handle, C.byref(inputs), num_reads, max_hits_per_seed, band, max_candidates, d_sequences or None, d_diagonals or None,
+            d_spans or None, lookback, gap_penalty, C.byref(outputs), d_scratch or None, stream or None))
 
     def locate_host_local(self, chars, offsets=None, fixed_length=0):
         """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],

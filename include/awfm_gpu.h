@@ -80,6 +80,8 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   record_lookup=lds|dir   which lookup a record table gets when it is installed (default: by its size; lds only where it fits)
  *   candidates_tier=wave|group   awfmGpuReadCandidates: group sends every read with a kept hit to the workgroup tier; wave is the
  *                       default (a read of up to 256 kept hits takes the wave tier) and changes nothing
+ *   chains_tier=wave|group   awfmGpuReadChains: group sends every read with an anchor to the workgroup tier; wave is the default
+ *                       (a read of up to 256 anchors takes the wave tier) and changes nothing
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
 
 /* ---- device image ---- */
@@ -465,6 +467,79 @@ uint64_t awfmGpuReadCandidatesScratchBytes(uint64_t numReads);
 enum AwFmReturnCode awfmGpuReadCandidates(AwFmGpuIndex *g, const struct AwFmCandidateInputs *dIn, uint64_t numReads,
                                           uint32_t maxHitsPerSeed, uint32_t band, uint32_t minVotes, uint32_t maxCandidates,
                                           const struct AwFmCandidateOutputs *dOut, void *dScratch, void *stream);
+
+/* ---- read chains: the best colinear chain of the seeds of every candidate locus ----
+ * The stage after awfmGpuReadCandidates: votes count hits, a chain counts the read bases that distinct, colinear seeds support,
+ * and says where in its sequence the read begins and ends.  One definition on both sides, the host twin being the definition
+ * and the checker of the device call.  (The reference has no analogue: ref src/AwFmParallelSearch.c:315-365.)
+ *
+ * INPUTS.  struct AwFmCandidateInputs, numReads, maxHitsPerSeed, band and C = maxCandidates (1..16) as in "candidate loci": the
+ * KEPT HITS of a read are exactly those of that definition, dropped seeds, illegal hits and AWFM_CANDIDATES_MAX_HITS included.
+ * The slot arrays sequences, diagonals and diagonalSpans ([numReads * C], read only) name the loci; lookback
+ * (1..AWFM_CHAINS_MAX_LOOKBACK) and gapPenalty (per unit of diagonal change, 0 allowed) steer the chaining.
+ *
+ * ANCHORS.  Slot (r, j) with sequences != AWFM_CANDIDATES_NONE owns the kept hits of read r in its sequence whose diagonal D has
+ * 0 <= D - diagonals[slot] <= diagonalSpans[slot], the difference taken exactly (as the candidate definition's keys do: no
+ * wrap-around, so a D below the slot's diagonal is never inside).  For slots that awfmReadCandidates wrote with the same band
+ * that interval is exactly the cluster (clusters are maximal runs); the call does not otherwise depend on how the slots were
+ * made.  Each such hit is an anchor (e, D, len): e = seedEnd, len = the seed's length, a = e - len the read offset of its start.
+ * A slot's anchors are ordered by (e ascending, D ascending as a signed value, len ascending); identical triples may stand in
+ * any order, the result being a function of the sequence of triples.
+ *
+ * RECURRENCE, in exact integer arithmetic (everything fits 64 bits signed except g * gapPenalty, which fits 64 bits unsigned; a
+ * value that is not above len_i is never taken, so no side needs a negative score).  The predecessors of anchor i are the
+ * anchors at the order positions max(0, i - lookback) .. i - 1 of its slot; predecessor j is compatible when
+ *   dr = e_i - e_j > 0,   dt = dr + (D_i - D_j) > 0,   g = |D_i - D_j| <= band,   and then
+ *   f(i) = max(len_i, max over compatible j of f(j) + min(len_i, dr, dt) - g * gapPenalty),
+ * ties among predecessors going to the largest j, and a predecessor being taken only when its value is strictly greater than
+ * len_i.  f(j) <= e_j and min(...) <= dr give f(i) <= e_i: SCORES FIT 32 BITS (the host twin asserts it).  An anchor carries
+ * the a and the D of the first anchor of its chain and the number of its anchors; nothing is backtraced.  Two hits of one seed
+ * share e and are never in one chain.  The BEST CHAIN of a slot ends at the anchor with the largest f, ties to the smallest
+ * order position.
+ *
+ * OUTPUTS (struct AwFmChainOutputs, every pointer may be NULL).  Per slot: chainScores = that f, chainAnchors, chainReadBegins =
+ * a of the chain's first anchor, chainReadEnds = e of its last, chainBeginDiagonals / chainEndDiagonals = D of the first / last:
+ * the chain covers [readBegin + beginDiagonal, readEnd + endDiagonal) of the sequence.  Unused slots and slots without an anchor
+ * get all zeros.  Per read: bestSlots = the slot with the largest score among those with an anchor, ties to the lowest,
+ * 0xFFFFFFFF when there is none; keptHits as in the candidate call.  *numOverflowed is ADDED to.
+ *
+ * LIMITS.  Overflowed reads (more than AWFM_CANDIDATES_MAX_HITS kept hits) and malformed reads are reported exactly as
+ * awfmReadCandidates reports them: all slots zero, bestSlots 0xFFFFFFFF, keptHits the saturated number / 0xFFFFFFFF, counted in
+ * *numOverflowed.  A read is also MALFORMED when two of its slots name the same sequence and their intervals [diagonal,
+ * diagonal + span] intersect: neither side then has to decide whose hit it is.  Neither side reads outside the arrays it was
+ * given, whatever the offsets or the slot arrays say.
+ *
+ * Error codes as in the candidate call; lookback outside 1..64: AwFmIllegalPositionError; a missing slot array (or dScratch):
+ * AwFmNullPtrError; numReads == 0 succeeds and touches nothing.
+ *
+ * awfmReadChains (csrc/awfm_chains.c): on the host over `threads` threads of the pool, a read at a time: collect, assign to
+ * slots, qsort, recurrence.  awfmGpuReadChains (csrc/awfm_chains_kernel.h): the same on device arrays; asynchronous on `stream`,
+ * no host wait, no allocation, none of the handle's scratch slots: two streams may run it on one image at once, each with its
+ * own dScratch of awfmGpuReadChainsScratchBytes(numReads) bytes.  A wave per read for reads of up to 256 anchors, a worklist in
+ * dScratch and a workgroup per read beyond; per anchor one step of one wave, a lane per predecessor.  `g` names the device and
+ * takes the error text; the call reads nothing of the index. */
+#define AWFM_CHAINS_MAX_LOOKBACK 64u
+#define AWFM_CHAINS_NO_SLOT 0xFFFFFFFFu /* bestSlots of a read without an anchor */
+struct AwFmChainOutputs {
+  uint32_t *chainScores; /* the six per-slot arrays: [numReads * maxCandidates] */
+  uint32_t *chainAnchors;
+  uint32_t *chainReadBegins;
+  uint32_t *chainReadEnds;
+  int64_t *chainBeginDiagonals;
+  int64_t *chainEndDiagonals;
+  uint32_t *bestSlots;     /* [numReads] */
+  uint32_t *keptHits;      /* [numReads] */
+  uint64_t *numOverflowed; /* one counter, added to */
+};
+enum AwFmReturnCode awfmReadChains(const struct AwFmCandidateInputs *in, uint64_t numReads, uint32_t maxHitsPerSeed, uint32_t band,
+                                   uint32_t maxCandidates, const uint32_t *sequences, const int64_t *diagonals,
+                                   const uint32_t *diagonalSpans, uint32_t lookback, uint32_t gapPenalty,
+                                   const struct AwFmChainOutputs *out, unsigned threads);
+uint64_t awfmGpuReadChainsScratchBytes(uint64_t numReads);
+enum AwFmReturnCode awfmGpuReadChains(AwFmGpuIndex *g, const struct AwFmCandidateInputs *dIn, uint64_t numReads, uint32_t maxHitsPerSeed,
+                                      uint32_t band, uint32_t maxCandidates, const uint32_t *dSequences, const int64_t *dDiagonals,
+                                      const uint32_t *dDiagonalSpans, uint32_t lookback, uint32_t gapPenalty,
+                                      const struct AwFmChainOutputs *dOut, void *dScratch, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
