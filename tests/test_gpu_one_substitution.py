@@ -166,6 +166,54 @@ def test_overflow_counts_only_and_edge_cases(awfm, require_gpu):
     g.destroy()
 
 
+def test_a_batch_larger_than_the_persistent_grid(awfm, require_gpu):
+    """oneSubstitutionKernel runs on a grid of at most CUs x 8 workgroups of 64 groups (gridFor, csrc/awfm_device.h), one query per
+    group and round: only a batch beyond that makes a group come back for a second query (q += numGroups, with the loop's
+    values parked in vector registers).  2^14 queries of the mix, 17 times over plus 3: the host twin answers the 2^14 once and
+    the expectation is tiled, the records shifted by the query number."""
+    import torch
+    text, amino, ix = _small_case(awfm, "random", 8, 10)[:3]
+    rng = np.random.default_rng(68)
+    queries = []
+    while len(queries) < 1 << 14:
+        queries += [q for q, _, _ in osc.make_mix(rng, text, amino, 8, 10)]
+    queries = queries[:1 << 14]
+    base, times, more = len(queries), 17, 3
+    n = base * times + more
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    print(f"\n{cus} CUs: the grid has at most {cus * 8 * 64} groups, the batch {n} queries")
+    assert n == 278531 and n > cus * 8 * 64, (n, cus)  # a larger part has to get a larger batch
+    chars, offsets = osc.pack(queries * times + queries[:more])
+    for include_exact in (True, False):
+        q1, e1, r1, total1, v1, o1 = awfm.one_substitution_search_host(ix, *osc.pack(queries), include_exact=include_exact, threads=16)
+        assert total1 > 10000
+        first = q1 < more
+        shift = (np.arange(times, dtype=np.uint32) * np.uint32(base)).repeat(q1.size)
+        want = (np.concatenate([np.tile(q1, times) + shift, q1[first] + np.uint32(base * times)]), np.concatenate([np.tile(e1, times), e1[first]]),
+                np.concatenate([np.tile(r1, (times, 1)), r1[first]]), total1 * times + int(first.sum()),
+                np.concatenate([np.tile(v1, times), v1[:more]]), np.concatenate([np.tile(o1, times), o1[:more]]))
+        g = awfm.GpuIndex(ix)
+        g.set_pair_image(1)
+        g.set_deep_seed(10)
+        for kernel, what in ((awfm.AWFM_GPU_KERNEL_AUTO, "tables"), (awfm.AWFM_GPU_KERNEL_GROUP2, "plain path")):
+            g.set_kernel(kernel)
+            got = _device(g, chars, offsets, capacity=want[3] + 100, include_exact=include_exact)
+            total = want[3]
+            assert got[3] == total and int((got[0] != FILL).sum()) == total, (what, got[3], total)
+            assert (got[0][:total] != FILL).all() and (got[1][total:] == FILL).all() and (got[2][total:] == np.array([1, 0], np.uint64)).all(), what
+            # the records as sets: both lists in the order of (query, edit), which is a key (no record twice)
+            for k, (hq, he, hr) in enumerate((got[:3], want[:3])):
+                key = hq[:total].astype(np.uint64) << np.uint64(32) | he[:total].astype(np.uint64)
+                order = np.argsort(key, kind="stable")
+                assert (np.diff(key[order].view(np.int64)) != 0).all(), (what, "a record twice", k)
+                if k == 0:
+                    got_key, got_ranges = key[order], hr[:total][order]
+                else:
+                    assert np.array_equal(got_key, key[order]) and np.array_equal(got_ranges, hr[:total][order]), what
+            assert np.array_equal(got[4], want[4]) and np.array_equal(got[5], want[5]), what
+        g.destroy()
+
+
 def test_two_streams_on_one_image(awfm, require_gpu):
     import torch
     text, _ = lm.small_texts()["random"]
