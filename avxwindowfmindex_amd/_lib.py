@@ -43,6 +43,7 @@ GPU_SYMBOLS = [
     "awfmLongestSuffixMatches", "awfmGpuLongestSuffixMatches", "awfmOneSubstitutionSearch", "awfmGpuOneSubstitutionSearch",
     "awfmReadCandidates", "awfmGpuReadCandidates", "awfmGpuReadCandidatesScratchBytes",
     "awfmReadChains", "awfmGpuReadChains", "awfmGpuReadChainsScratchBytes",
+    "awfmGpuIndexSetText", "awfmGpuIndexTextLength", "awfmTextWindows", "awfmGpuTextWindows", "awfmVerifyChains", "awfmGpuVerifyChains",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -89,6 +90,18 @@ class AwFmChainOutputs(C.Structure):
     _fields_ = [("chainScores", C.c_void_p), ("chainAnchors", C.c_void_p), ("chainReadBegins", C.c_void_p), ("chainReadEnds", C.c_void_p),
                 ("chainBeginDiagonals", C.c_void_p), ("chainEndDiagonals", C.c_void_p), ("bestSlots", C.c_void_p), ("keptHits", C.c_void_p),
                 ("numOverflowed", C.c_void_p)]
+
+
+class AwFmVerifyInputs(C.Structure):
+    """struct AwFmVerifyInputs (include/awfm_gpu.h): host or device addresses"""
+    _fields_ = [("readChars", C.c_void_p), ("numReadChars", C.c_uint64), ("readOffsets", C.c_void_p), ("sequences", C.c_void_p),
+                ("chainAnchors", C.c_void_p), ("chainReadBegins", C.c_void_p), ("chainReadEnds", C.c_void_p),
+                ("chainBeginDiagonals", C.c_void_p), ("chainEndDiagonals", C.c_void_p)]
+
+
+class AwFmVerifyOutputs(C.Structure):
+    """struct AwFmVerifyOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("editDistances", C.c_void_p), ("bestSlots", C.c_void_p), ("numUnverified", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -242,6 +255,14 @@ def lib():
         "awfmGpuReadChainsScratchBytes": (u64, [u64]),
         "awfmGpuReadChains": (C.c_int, [vp, C.POINTER(AwFmCandidateInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32,
                                         C.c_uint32, C.POINTER(AwFmChainOutputs), vp, vp]),
+        "awfmGpuIndexSetText": (C.c_int, [vp, vp, u64]),
+        "awfmGpuIndexTextLength": (u64, [vp]),
+        "awfmTextWindows": (C.c_int, [vp, u64, vp, u64, C.c_uint32, C.c_uint32, vp, C.c_uint]),
+        "awfmGpuTextWindows": (C.c_int, [vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp, vp]),
+        "awfmVerifyChains": (C.c_int, [C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.c_int,
+                                       C.POINTER(AwFmVerifyOutputs), C.c_uint]),
+        "awfmGpuVerifyChains": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.POINTER(AwFmVerifyOutputs), vp]),
         "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),
         "awfmGpuIndexNumRecords": (C.c_uint32, [vp]),
         "awfmGpuLocalPositions": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),

@@ -433,6 +433,93 @@ def read_chains_scratch_bytes(n):
     return int(_lib.lib().awfmGpuReadChainsScratchBytes(n))
 
 
+VERIFY_MAX_BAND = 64  # AWFM_VERIFY_MAX_BAND: maxDrift + 2 bandPad + 1 diagonals at the most
+VERIFY_MAX_LENGTH = 1 << 20  # AWFM_VERIFY_MAX_LENGTH: read characters of a chain that is verified
+VERIFY_NONE, VERIFY_MALFORMED, VERIFY_TOO_WIDE, VERIFY_TOO_LONG = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+VERIFY_SLOT_INPUTS = (("sequences", np.uint32), ("chainAnchors", np.uint32), ("chainReadBegins", np.uint32), ("chainReadEnds", np.uint32),
+                      ("chainBeginDiagonals", np.int64), ("chainEndDiagonals", np.int64))
+
+
+def verify_inputs(read_chars, num_read_chars, read_offsets, **slot_addresses):
+    """struct AwFmVerifyInputs from addresses: the read buffer, its size, the read offsets, and the six per-slot arrays by field
+    name (sequences, chainAnchors, chainReadBegins, chainReadEnds, chainBeginDiagonals, chainEndDiagonals)"""
+    vin = _lib.AwFmVerifyInputs(read_chars or None, num_read_chars, read_offsets or None)
+    for name, address in slot_addresses.items():
+        if name not in dict(VERIFY_SLOT_INPUTS):
+            raise ValueError(f"no slot array called {name}")
+        setattr(vin, name, address or None)
+    return vin
+
+
+def verify_outputs(**addresses):
+    """struct AwFmVerifyOutputs from addresses by field name (editDistances, bestSlots, numUnverified); a field left out is NULL"""
+    out = _lib.AwFmVerifyOutputs()
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmVerifyOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def text_windows_host(text, positions, before, after, threads=4):
+    """awfmTextWindows: text (bytes or uint8 array), positions -> uint8 array shaped (positions, before + after): window i is
+    text[p - before, p + after) with every byte outside the text written as 0"""
+    t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    pos = np.ascontiguousarray(positions, dtype=np.uint64)
+    out = np.full((pos.size, max(before + after, 0)), 0xAA, np.uint8)
+    dummy = np.zeros(1, np.uint64)
+    rc = _lib.lib().awfmTextWindows(t.ctypes.data if t.size else None, t.size, pos.ctypes.data if pos.size else dummy.ctypes.data, pos.size,
+                                    before, after, out.ctypes.data if out.size else dummy.ctypes.data, threads)
+    _check("awfmTextWindows", rc)
+    return out
+
+
+def verify_chains_host(read_chars, read_offsets, slots, text, sequence_ends=None, alphabet=AwFmAlphabetDna, band_pad=8, max_drift=15,
+                       threads=4, outputs=None, num_read_chars=None, fill=None, unverified_before=0):
+    """awfmVerifyChains (include/awfm_gpu.h, "chain verification"): the read buffer and offsets, `slots` a dict of the six per-slot
+    arrays by field name shaped (reads, max_candidates), the text and the records' ends (None: one sequence) -> a dict of
+    editDistances shaped like the slots, bestSlots per read and numUnverified (an int: unverified_before plus this call's).
+    outputs: the names to compute (None: all); the others are passed as NULL and left out.  fill: the value (per byte) the
+    arrays hold before the call."""
+    chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
+    t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    ends = None if sequence_ends is None else np.ascontiguousarray(sequence_ends, dtype=np.uint64)
+    n = max(o.size - 1, 0)
+    arrays = {name: np.ascontiguousarray(slots[name], dtype=dtype) for name, dtype in VERIFY_SLOT_INPUTS}
+    shape = arrays["sequences"].shape
+    if len(shape) != 2 or shape[0] != n or any(a.shape != shape for a in arrays.values()):
+        raise ValueError("the slot arrays are shaped (reads, max_candidates)")
+    names = ["editDistances", "bestSlots", "numUnverified"]
+    outputs = names if outputs is None else list(outputs)
+    result = {}
+    if "editDistances" in outputs:
+        result["editDistances"] = np.zeros(shape, np.uint32)
+    if "bestSlots" in outputs:
+        result["bestSlots"] = np.zeros(n, np.uint32)
+    for a in result.values():
+        if fill is not None:
+            a.view(np.uint8)[...] = fill
+    unverified = np.array([unverified_before], np.uint64)
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else dummy.ctypes.data
+
+    vin = verify_inputs(address(chars), chars.size if num_read_chars is None else num_read_chars, address(o),
+                        **{name: address(a) for name, a in arrays.items()})
+    vout = verify_outputs(**{name: address(a) for name, a in result.items()})
+    if "numUnverified" in outputs:
+        vout.numUnverified = unverified.ctypes.data
+    rc = _lib.lib().awfmVerifyChains(C.byref(vin), n, shape[1], band_pad, max_drift, address(t), t.size,
+                                     None if ends is None or not ends.size else ends.ctypes.data, 0 if ends is None else ends.size, alphabet,
+                                     C.byref(vout), threads)
+    _check("awfmVerifyChains", rc)
+    if "numUnverified" in outputs:
+        result["numUnverified"] = int(unverified[0])
+    return result
+
+
 AWFM_EDIT_NONE = 0xFFFFFFFF  # the edit of a record of the unedited query (include/awfm_gpu.h)
 
 
@@ -621,6 +708,33 @@ class GpuIndex:
         _check("awfmGpuReadChains", _lib.lib().awfmGpuReadChains(
             self.handle, C.byref(inputs), num_reads, max_hits_per_seed, band, max_candidates, d_sequences or None, d_diagonals or None,
             d_spans or None, lookback, gap_penalty, C.byref(outputs), d_scratch or None, stream or None))
+
+    # chain verification (include/awfm_gpu.h) -----------------------------
+    def set_text(self, text):
+        """awfmGpuIndexSetText: uploads the indexed text (bytes or a uint8 array of bwtLength - 1 bytes, as it was given to the
+        index's constructor); None or an empty text removes it"""
+        if text is None:
+            t = np.zeros(0, np.uint8)
+        else:
+            t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+        _check("awfmGpuIndexSetText", _lib.lib().awfmGpuIndexSetText(self.handle, t.ctypes.data if t.size else None, t.size))
+
+    @property
+    def text_length(self):
+        """positions of the image's text (0: none)"""
+        return int(_lib.lib().awfmGpuIndexTextLength(self.handle))
+
+    def text_windows(self, d_positions, capacity, before, after, d_out, d_num_positions=0, stream=0):
+        """awfmGpuTextWindows: window i of the first min(*d_num_positions, capacity) positions (capacity without a count) is
+        d_out[i * (before + after) ..) = text[p - before, p + after), zero outside the text; asynchronous on `stream`"""
+        _check("awfmGpuTextWindows", _lib.lib().awfmGpuTextWindows(self.handle, d_positions or None, capacity, d_num_positions or None,
+                                                                   before, after, d_out or None, stream or None))
+
+    def verify_chains(self, inputs, num_reads, outputs, max_candidates=4, band_pad=8, max_drift=15, stream=0):
+        """awfmGpuVerifyChains: inputs / outputs are verify_inputs(...) / verify_outputs(...) of device addresses; text, record
+        table and alphabet are the image's; asynchronous on `stream`; *numUnverified is added to"""
+        _check("awfmGpuVerifyChains", _lib.lib().awfmGpuVerifyChains(self.handle, C.byref(inputs), num_reads, max_candidates, band_pad,
+                                                                     max_drift, C.byref(outputs), stream or None))
 
     def locate_host_local(self, chars, offsets=None, fixed_length=0):
         """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],

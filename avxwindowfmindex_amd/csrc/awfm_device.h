@@ -901,7 +901,7 @@ __global__ void relayoutAminoKernel(const unsigned long long *__restrict__ ref, 
 struct AwFmGpuIndex;
 /* Locks of an image and its handles, in the one order they are taken:
  *   awfm_gpu_image.hip's tableMutex (the registry) -> streamMutex -> handlesMutex -> for each handle in handle order: aosMutex ->
- *   workMutex -> orderMutex -> lengthMutex -> joinMutex -> recordMutex (a leaf: nothing is taken and nothing waited for under it).
+ *   workMutex -> orderMutex -> lengthMutex -> joinMutex -> recordMutex (a leaf: nothing is taken and nothing waited for under it; it guards the record table and the text).
  * A search takes one handle's locks in that order (AoS lane -> host-buffer call -> ordered search).  AwFmGpuExclusive is the only
  * holder of the locks of more than one handle: every change of an image's view (DevIndex and the arrays behind it) happens inside
  * it.  Nobody takes tableMutex while holding a handle's lock. */
@@ -983,6 +983,12 @@ struct AwFmGpuImage {
   bool recordsInLds = false;   /* the lookup the table got when it was installed: ends and directory staged into LDS, or read from memory */
   unsigned recordLdsBytes = 0; /* dynamic LDS of the LDS lookup */
   unsigned recordGrid = 0;     /* resident workgroups of the table's kernel on this device (persistent grid) */
+  /* The indexed text (awfm_gpu_verify.hip), one byte per position, installed by awfmGpuIndexSetText: one allocation of
+   * alignUp(textLength, 16) + 16 bytes, zero from textLength on.  Published under recordMutex exactly as the record table is (a
+   * verification reads both views under one shared hold); the old allocation is freed after publication. */
+  void *dText = nullptr;
+  uint64_t textLength = 0;
+  uint64_t textBytes = 0;
 };
 
 /* one caller's handle on an image: its staging, its scratch, its locks and its selections */
@@ -1249,6 +1255,10 @@ enum AwFmReturnCode awfmGpuInstallRecordTable(AwFmGpuIndex *g, const uint64_t *e
 enum AwFmReturnCode awfmGpuInstallRecordTableOf(AwFmGpuIndex *g, const struct AwFmIndex *index);
 /* one line for awfmGpuIndexDescribe ("" without a table) */
 std::string awfmGpuDescribeRecordTable(const AwFmGpuImage *image);
+/* awfm_gpu_verify.hip: installs (length == 0: drops) the image's text from host bytes; validates, uploads, publishes, then frees
+ * the text it replaces.  The caller holds AwFmGpuExclusive on an image somebody else may be using. */
+enum AwFmReturnCode awfmGpuInstallText(AwFmGpuIndex *g, const uint8_t *text, uint64_t length);
+std::string awfmGpuDescribeText(const AwFmGpuImage *image);
 /* awfm_gpu.hip: awfmGpuLocateHostWindows with every window mapped to sequence coordinates on the device before its download
  * (seqOfWindow != NULL: the sink's positions are then the local ones and *seqOfWindow the window's sequence numbers) */
 enum AwFmReturnCode awfmGpuLocateHostWindowsMapped(AwFmGpuIndex *g, const uint8_t *chars, const uint64_t *offsets, uint32_t fixedLength,

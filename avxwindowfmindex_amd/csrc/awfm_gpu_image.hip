@@ -442,7 +442,7 @@ void awfmGpuIndexDestroy(AwFmGpuIndex *g) {
       awfmGpuStreamStateFree(image);
       void *owned[] = {image->dBlocks, image->dSuper, image->dSeed, image->dSa, image->dPrefix, image->dDeepSeed, image->dDeepBig,
                        image->dDenseSa, image->dLengthTable, image->dLengthBig, image->dPairBlocks, image->dPairSuper,
-                       image->dPairSuper32, image->dPairC, image->dRecords};
+                       image->dPairSuper32, image->dPairC, image->dRecords, image->dText};
       for (void *p : owned)
         if (p) (void)hipFree(p);
     }
@@ -594,7 +594,7 @@ void awfmGpuAosUnlock(AwFmGpuIndex *g) {
 }
 
 static uint64_t imageBytes(const AwFmGpuImage *image) {
-  return image->deviceBytes + image->deepSeedBytes + image->denseSaBytes + image->pairBytes + image->lengthTableBytes + image->recordBytes;
+  return image->deviceBytes + image->deepSeedBytes + image->denseSaBytes + image->pairBytes + image->lengthTableBytes + image->recordBytes + image->textBytes;
 }
 uint64_t awfmGpuIndexDeviceBytes(const AwFmGpuIndex *g) { return g && !g->lane ? imageBytes(g->image) : 0; } /* (a lane holds none of it) */
 
@@ -819,6 +819,7 @@ int awfmGpuIndexDescribe(const AwFmGpuIndex *g, char *out, int outBytes) {
   text += image->dDenseSa ? "full suffix array yes; " : "full suffix array no; ";
   if (!g->amino) text += image->dLengthTable ? "tables per k-mer length 1.." + std::to_string(image->lengthDepths) + "; " : "tables per k-mer length not built (the first large mixed-length batch builds them); ";
   text += awfmGpuDescribeRecordTable(image);
+  text += awfmGpuDescribeText(image);
   if (!image->accelNotes.empty()) text += "notes: " + image->accelNotes;
   while (!text.empty() && (text.back() == ' ' || text.back() == ';')) text.pop_back();
   const int n = (int)text.size() < outBytes - 1 ? (int)text.size() : outBytes - 1;

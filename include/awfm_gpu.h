@@ -82,6 +82,8 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *                       default (a read of up to 256 kept hits takes the wave tier) and changes nothing
  *   chains_tier=wave|group   awfmGpuReadChains: group sends every read with an anchor to the workgroup tier; wave is the default
  *                       (a read of up to 256 anchors takes the wave tier) and changes nothing
+ *   verify_group=16|32|64   awfmGpuVerifyChains: lanes per slot, where that is more than the band's diagonals need (a smaller
+ *                       value than the band needs is ignored); the default is the smallest that holds the band
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
 
 /* ---- device image ---- */
@@ -540,6 +542,105 @@ enum AwFmReturnCode awfmGpuReadChains(AwFmGpuIndex *g, const struct AwFmCandidat
                                       uint32_t band, uint32_t maxCandidates, const uint32_t *dSequences, const int64_t *dDiagonals,
                                       const uint32_t *dDiagonalSpans, uint32_t lookback, uint32_t gapPenalty,
                                       const struct AwFmChainOutputs *dOut, void *dScratch, void *stream);
+
+/* ---- chain verification: the indexed text on the device, batched recall, and the banded edit distance of every chain ----
+ * The stage after awfmGpuReadChains: a chain says where a read probably lies; this stage compares the read's characters with the
+ * text there and gives the caller a number to rank or reject on.  One definition on both sides, the host twin being the
+ * definition and the checker of the device calls.  (The reference keeps the text for this purpose and reads one segment per
+ * call: ref src/AwFmFile.c awFmReadSequenceFromFile, one pread each.)
+ *
+ * THE TEXT ON THE DEVICE.  awfmGpuIndexSetText uploads the indexed text as it was given to awFmCreateIndex (host bytes, one per
+ * position, unchanged; a FASTA index's text is its records concatenated with their NUL terminators).  length must equal
+ * bwtLength - 1, else AwFmIllegalPositionError and the old text stays; NULL / 0 removes the text.  awfmGpuIndexTextLength
+ * returns the length, 0 without a text.  The text is ONE allocation of alignUp(length, 16) + 16 bytes whose bytes from `length`
+ * on are zero, so that any ALIGNED 4-, 8- or 16-byte load that holds at least one byte of [0, length) lies inside the
+ * allocation: that is the only kind of load a kernel makes of it.  It belongs to the image: all handles share it, it is counted
+ * in awfmGpuIndexDeviceBytes, named by awfmGpuIndexDescribe and freed by awfmGpuIndexDestroy; it is installed like the record
+ * table (waits for the searches on the image; calls already enqueued finish on the text they were enqueued with).  Nothing
+ * uploads it automatically: not awfmGpuCreateIndex, not an index that carries storeOriginalSequence.
+ *
+ * BATCHED RECALL.  Window i of positions[i] = p is out[i * (before + after) ..) = text[p - before, p + after): every byte
+ * outside [0, length) is written as 0, every byte of a window with p >= length included.  before + after must be 1..4096
+ * (AwFmIllegalPositionError).  awfmTextWindows: on the host over `threads` threads of the pool.  awfmGpuTextWindows: on device
+ * arrays, the first n positions, n = capacity when dNumPositions is NULL and min(*dNumPositions, capacity) otherwise, the count
+ * being read ON THE DEVICE as in awfmGpuLocalPositions; windows past the count stay as they were.  One launch, asynchronous on
+ * `stream`, no host wait, no allocation.  AwFmUnsupportedVersionError when the image has no text.
+ *
+ * VERIFICATION.  The reads: read r is readChars[readOffsets[r] .. readOffsets[r + 1]) of numReadChars characters.  C =
+ * maxCandidates (1..16); the per-slot arrays [numReads * C] are sequences as awfmReadCandidates wrote it and chainAnchors,
+ * chainReadBegins (rb), chainReadEnds (re), chainBeginDiagonals (bD), chainEndDiagonals (eD) as awfmReadChains wrote them.
+ * bandPad w and maxDrift x with x + 2 w + 1 <= AWFM_VERIFY_MAX_BAND, else AwFmIllegalPositionError.  The host twin takes text,
+ * length, the records' ends (numRecords == 0: one sequence [0, length)) and the alphabet; the device call takes text, record
+ * table (none: one sequence) and alphabet from the image, and gives AwFmUnsupportedVersionError without a text.
+ *
+ * Per slot, with s its sequence:
+ *   UNUSED     sequences == AWFM_CANDIDATES_NONE or chainAnchors == 0: AWFM_VERIFY_NONE.
+ *   INTERVALS  in exact arithmetic, no wrap-around (a value that does not fit is malformed): the record is [S, E[s]) with
+ *              S = s ? E[s - 1] + 1 : 0;  n = re - rb, tb = rb + bD, te = re + eD, m = te - tb, delta = m - n = eD - bD.
+ *   MALFORMED  s >= the number of sequences; rb > re or re > the read's length; the read's offsets inverted or beyond
+ *              numReadChars; tb < 0, tb > te, te > E[s] - S; or a record that leaves the text (E[s] < S or E[s] > length, which a
+ *              table that belongs to the text never has): AWFM_VERIFY_MALFORMED.  NOTHING is read through a malformed slot,
+ *              neither read nor text.  Chains that awfmReadChains made from located hits are never malformed.
+ *   TOO WIDE   |delta| > x: AWFM_VERIFY_TOO_WIDE.
+ *   TOO LONG   n > AWFM_VERIFY_MAX_LENGTH: AWFM_VERIFY_TOO_LONG (so every value fits 32 bits).
+ *   otherwise the BANDED GLOBAL EDIT DISTANCE of R = read[rb .. re) and T = text[S + tb .. S + te):
+ *     band        cell (i, j), 0 <= i <= n, 0 <= j <= m, is in the band when lo <= j - i <= hi, lo = min(0, delta) - w,
+ *                 hi = max(0, delta) + w;
+ *     recurrence  H(0, 0) = 0; H(i, j) = the minimum over those of its three predecessors that are in the band and in the matrix
+ *                 of H(i-1, j-1) + sub(R[i-1], T[j-1]), H(i-1, j) + 1, H(i, j-1) + 1;
+ *     sub         0 when both characters map to the same PROPER letter index under the library's mapping (the reference's
+ *                 letter tables, ref src/AwFmLetter.c:4-22 / :55-67: index < 4 of a nucleotide, < 20 of an amino index; blind to
+ *                 case), 1 otherwise: an ambiguity letter matches nothing, not even itself;
+ *     result      H(n, m); both corners are always in the band.
+ *   The value is an UPPER BOUND of the unbanded edit distance and EQUALS it whenever that distance is <= 2 w + |delta| (a
+ *   path of cost d takes a steps along T alone and b along R alone with a - b = delta and a + b <= d, and stays on the diagonals
+ *   [-b, a]; min(a, b) = (a + b - |delta|) / 2 <= w then keeps it inside [lo, hi]).
+ *
+ * OUTPUTS (every pointer may be NULL): editDistances [numReads * C]; bestSlots [numReads]: the slot with the smallest distance
+ * among those that have one, ties to the lowest slot, AWFM_CHAINS_NO_SLOT when none; *numUnverified: the slots that got
+ * MALFORMED, TOO_WIDE or TOO_LONG, ADDED to (zero it first).  numReads == 0 succeeds and touches nothing; a missing input array:
+ * AwFmNullPtrError; numReads >= 2^32 or maxCandidates outside 1..16: AwFmIllegalPositionError.
+ *
+ * awfmVerifyChains (csrc/awfm_verify.c): on the host over `threads` threads of the pool, a read at a time, two rows of at most
+ * 64 cells, the plain recurrence.  awfmGpuVerifyChains (csrc/awfm_verify_kernel.h): the same on device arrays (both structs live
+ * on the host and hold device addresses); one launch, asynchronous on `stream`, no host wait, no allocation, no scratch: two
+ * streams may run it on one image at once.  A wave per read; a group of G lanes (16, 32 or 64: the smallest that holds the band's
+ * x + 2 w + 1 diagonals) per slot, a lane per diagonal, a row per step.  $AWFM_GPU_DIAG verify_group=16|32|64 forces a larger G
+ * than the band needs (tests; the result does not depend on it). */
+#define AWFM_VERIFY_MAX_BAND 64u
+#define AWFM_VERIFY_MAX_LENGTH (1u << 20)
+#define AWFM_VERIFY_NONE 0xFFFFFFFFu
+#define AWFM_VERIFY_MALFORMED 0xFFFFFFFEu
+#define AWFM_VERIFY_TOO_WIDE 0xFFFFFFFDu
+#define AWFM_VERIFY_TOO_LONG 0xFFFFFFFCu
+struct AwFmVerifyInputs {
+  const uint8_t *readChars;
+  uint64_t numReadChars;
+  const uint64_t *readOffsets; /* [numReads + 1] */
+  const uint32_t *sequences;   /* the six per-slot arrays: [numReads * maxCandidates] */
+  const uint32_t *chainAnchors;
+  const uint32_t *chainReadBegins;
+  const uint32_t *chainReadEnds;
+  const int64_t *chainBeginDiagonals;
+  const int64_t *chainEndDiagonals;
+};
+struct AwFmVerifyOutputs {
+  uint32_t *editDistances; /* [numReads * maxCandidates] */
+  uint32_t *bestSlots;     /* [numReads] */
+  uint64_t *numUnverified; /* one counter, added to */
+};
+enum AwFmReturnCode awfmGpuIndexSetText(AwFmGpuIndex *g, const uint8_t *text, uint64_t length);
+uint64_t awfmGpuIndexTextLength(const AwFmGpuIndex *g);
+enum AwFmReturnCode awfmTextWindows(const uint8_t *text, uint64_t length, const uint64_t *positions, uint64_t numPositions,
+                                    uint32_t before, uint32_t after, uint8_t *out, unsigned threads);
+enum AwFmReturnCode awfmGpuTextWindows(AwFmGpuIndex *g, const uint64_t *dPositions, uint64_t capacity, const uint64_t *dNumPositions,
+                                       uint32_t before, uint32_t after, uint8_t *dOut, void *stream);
+enum AwFmReturnCode awfmVerifyChains(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
+                                     uint32_t maxDrift, const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds,
+                                     uint64_t numRecords, enum AwFmAlphabetType alphabet, const struct AwFmVerifyOutputs *out,
+                                     unsigned threads);
+enum AwFmReturnCode awfmGpuVerifyChains(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
+                                        uint32_t bandPad, uint32_t maxDrift, const struct AwFmVerifyOutputs *dOut, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
