@@ -44,6 +44,7 @@ GPU_SYMBOLS = [
     "awfmReadCandidates", "awfmGpuReadCandidates", "awfmGpuReadCandidatesScratchBytes",
     "awfmReadChains", "awfmGpuReadChains", "awfmGpuReadChainsScratchBytes",
     "awfmGpuIndexSetText", "awfmGpuIndexTextLength", "awfmTextWindows", "awfmGpuTextWindows", "awfmVerifyChains", "awfmGpuVerifyChains",
+    "awfmAlignChains", "awfmGpuAlignChainsScratchBytes", "awfmGpuAlignChains",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -102,6 +103,12 @@ class AwFmVerifyInputs(C.Structure):
 class AwFmVerifyOutputs(C.Structure):
     """struct AwFmVerifyOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
     _fields_ = [("editDistances", C.c_void_p), ("bestSlots", C.c_void_p), ("numUnverified", C.c_void_p)]
+
+
+class AwFmAlignOutputs(C.Structure):
+    """struct AwFmAlignOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("editDistances", C.c_void_p), ("textBegins", C.c_void_p), ("textEnds", C.c_void_p), ("numOps", C.c_void_p),
+                ("ops", C.c_void_p), ("numUnaligned", C.c_void_p), ("numTruncated", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -263,6 +270,11 @@ def lib():
                                        C.POINTER(AwFmVerifyOutputs), C.c_uint]),
         "awfmGpuVerifyChains": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.POINTER(AwFmVerifyOutputs), vp]),
+        "awfmAlignChains": (C.c_int, [C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64, vp, u64,
+                                      C.c_int, C.POINTER(AwFmAlignOutputs), C.c_uint]),
+        "awfmGpuAlignChainsScratchBytes": (u64, [vp, C.c_uint32]),
+        "awfmGpuAlignChains": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.POINTER(AwFmAlignOutputs), vp, vp]),
         "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),
         "awfmGpuIndexNumRecords": (C.c_uint32, [vp]),
         "awfmGpuLocalPositions": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),

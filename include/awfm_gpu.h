@@ -84,6 +84,7 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *                       (a read of up to 256 anchors takes the wave tier) and changes nothing
  *   verify_group=16|32|64   awfmGpuVerifyChains: lanes per slot, where that is more than the band's diagonals need (a smaller
  *                       value than the band needs is ignored); the default is the smallest that holds the band
+ *   align_group=16|32|64    awfmGpuAlignChains: lanes per read, in the same way
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
 
 /* ---- device image ---- */
@@ -641,6 +642,85 @@ enum AwFmReturnCode awfmVerifyChains(const struct AwFmVerifyInputs *in, uint64_t
                                      unsigned threads);
 enum AwFmReturnCode awfmGpuVerifyChains(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
                                         uint32_t bandPad, uint32_t maxDrift, const struct AwFmVerifyOutputs *dOut, void *stream);
+
+/* ---- chain alignment: where a read lies in its record, at what distance and by which operations ----
+ * The stage after verification: one slot of every read, slots[r], is ALIGNED -- the whole read, not the chain's interval, with
+ * free ends in the text, with a record of each cell's direction and a walk back that emits the edit script.  slots[r] is
+ * normally bestSlots of awfmGpuReadChains or awfmGpuVerifyChains as it is; a caller who wants secondary alignments calls again
+ * with another array.  Inputs, C = maxCandidates (1..16), bandPad w, maxDrift x (x + 2 w + 1 <= AWFM_VERIFY_MAX_BAND, else
+ * AwFmIllegalPositionError), text, record table and alphabet are verification's.  One definition on both sides, the host twin
+ * (csrc/awfm_align.c) being the definition and the checker of the device call.
+ *
+ * Per read, in this order, with j = slots[r] and n the length of the WHOLE read:
+ *   UNUSED     j == AWFM_CHAINS_NO_SLOT, or the slot's sequences == AWFM_CANDIDATES_NONE or its chainAnchors == 0:
+ *              AWFM_VERIFY_NONE.  Not counted.
+ *   MALFORMED  j >= C (and not the no-slot value), or the slot is malformed as in verification (record and sequence checks,
+ *              rb > re, re > n, read offsets inverted or beyond numReadChars, tb < 0, tb > te, te > the record's length L,
+ *              diagonals whose sums would wrap): AWFM_VERIFY_MALFORMED.  NOTHING is read through a malformed slot.
+ *   TOO WIDE   |eD - bD| > x: AWFM_VERIFY_TOO_WIDE.
+ *   TOO LONG   n > maxRows on the device (maxRows is 1..AWFM_ALIGN_MAX_LENGTH, else AwFmIllegalPositionError), n >
+ *              AWFM_ALIGN_MAX_LENGTH on the host: AWFM_VERIFY_TOO_LONG.
+ *   OVERHANG   with lo = min(bD, eD) - w and hi = max(bD, eD) + w: hi < 0 or lo + n > L -- the band around the chain's diagonals
+ *              has left the record before the read's first or after its last character: AWFM_ALIGN_OVERHANG.  Such reads are
+ *              reported, not clipped.
+ *   A read with one of these five gets the status in editDistances and zeros in textBegins, textEnds and numOps; its row of ops
+ *   is not written.  Only ALIGNED reads load text.
+ *   otherwise the BANDED FITTING ALIGNMENT of R = the whole read against the record T (sequence-local coordinates), global in
+ *   the read and free at both ends in the text:
+ *     cells       (i, t) exists for 0 <= i <= n, 0 <= t <= L, lo <= t - i <= hi;
+ *     recurrence  H(0, t) = 0; for i > 0, H(i, t) = the minimum over the existing predecessors of H(i-1, t-1) + sub(R[i-1],
+ *                 T[t-1]), H(i-1, t) + 1, H(i, t-1) + 1; sub is verification's (0 only for two characters of the same proper
+ *                 letter index, blind to case, an ambiguity letter matches nothing);
+ *     finiteness  every existing cell with i > 0 has an existing predecessor: the diagonal one exists whenever t >= 1 (same
+ *                 diagonal, 0 <= t - 1 <= L), and in column 0 the upper one does, its diagonal 1 - i <= 0 <= hi.  Row n has a
+ *                 cell because n + lo <= L and n + hi >= 0.  So no infinity ever reaches an output;
+ *     direction   of a cell, a function of the cell alone: DIAGONAL when the diagonal predecessor exists and attains the
+ *                 minimum, else UP when the upper one does, else LEFT;
+ *     end         textEnd = the smallest t that minimises H(n, t) over the existing cells of row n; editDistance that minimum;
+ *     walk back   follow the directions from (n, textEnd) to row 0; the column reached there is textBegin;
+ *     operations  from the read's first character on: diagonal gives '=' when sub is 0 and 'X' otherwise, up gives 'I' (a
+ *                 read character without a text character), left gives 'D'; equal neighbours are merged into runs, and run k
+ *                 is ops[r * maxOps + k] = run << 4 | op in BAM numbering (I = 1, D = 2, '=' = 7, X = 8); numOps is the
+ *                 number of runs.  Entries of the row from numOps on are not written.
+ *   The value is an UPPER BOUND of the unbanded fitting distance of the read against the record; the runs' read lengths sum to
+ *   n, their text lengths to textEnd - textBegin, and the number of X, I and D characters equals the distance.  A read with
+ *   n = 0 is aligned: distance 0, no run, textBegin = textEnd = max(lo, 0).
+ *   maxOps is 1..AWFM_ALIGN_MAX_OPS (AwFmIllegalPositionError).  When a read's numOps > maxOps its row of ops has unspecified
+ *   content, nothing outside the row is written, the read is counted in *numTruncated and every other output stays valid
+ *   (numOps is the true number).
+ *
+ * OUTPUTS (every pointer may be NULL): see the struct; the two counters are ADDED to.  numReads == 0 succeeds and touches nothing;
+ * a missing input array, slots or dScratch: AwFmNullPtrError; numReads >= 2^32, C outside 1..16: AwFmIllegalPositionError.
+ *
+ * awfmAlignChains (csrc/awfm_align.c): on the host over `threads` threads of the pool, a read at a time, the plain recurrence
+ * with a direction byte per cell in an n x band table, then the walk.  awfmGpuAlignChains (csrc/awfm_align_kernel.h): the same on
+ * device arrays; text, record table and alphabet are the image's (AwFmUnsupportedVersionError without a text); one launch,
+ * asynchronous on `stream`, no host wait, no allocation.  A group of G lanes (16, 32 or 64: the smallest that holds the band)
+ * per read, a lane per diagonal, a row per step; the directions of a row go to the group's trace arena in dScratch, 16 bytes
+ * per row and wave of a persistent grid: awfmGpuAlignChainsScratchBytes(g, maxRows) bytes, 16-byte aligned
+ * (AwFmIllegalPositionError otherwise), of this call's own until it has finished -- two streams may run the call at once with
+ * a dScratch each.  $AWFM_GPU_DIAG align_group=16|32|64 forces a larger G than the band needs (tests; the result does not
+ * depend on it). */
+#define AWFM_ALIGN_MAX_LENGTH (1u << 16) /* read characters per aligned read */
+#define AWFM_ALIGN_MAX_OPS 4096u         /* upper limit of maxOps */
+#define AWFM_ALIGN_OVERHANG 0xFFFFFFFBu  /* beside AWFM_VERIFY_NONE / MALFORMED / TOO_WIDE / TOO_LONG, which are reused */
+struct AwFmAlignOutputs {
+  uint32_t *editDistances; /* [numReads]  a distance or one of the five status values */
+  uint64_t *textBegins;    /* [numReads]  sequence-local, of the slot's sequence */
+  uint64_t *textEnds;      /* [numReads] */
+  uint32_t *numOps;        /* [numReads]  the true number of runs, also when it exceeds maxOps */
+  uint32_t *ops;           /* [numReads * maxOps]  run << 4 | op, BAM numbering: I = 1, D = 2, '=' = 7, X = 8 */
+  uint64_t *numUnaligned;  /* one counter, added to: MALFORMED, TOO_WIDE, TOO_LONG, OVERHANG */
+  uint64_t *numTruncated;  /* one counter, added to: aligned reads with numOps > maxOps */
+};
+enum AwFmReturnCode awfmAlignChains(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads, uint32_t maxCandidates,
+                                    uint32_t bandPad, uint32_t maxDrift, uint32_t maxOps, const uint8_t *text, uint64_t length,
+                                    const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
+                                    const struct AwFmAlignOutputs *out, unsigned threads);
+uint64_t awfmGpuAlignChainsScratchBytes(const AwFmGpuIndex *g, uint32_t maxRows);
+enum AwFmReturnCode awfmGpuAlignChains(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, const uint32_t *dSlots, uint64_t numReads,
+                                       uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift, uint32_t maxOps, uint32_t maxRows,
+                                       const struct AwFmAlignOutputs *dOut, void *dScratch, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
