@@ -29,7 +29,7 @@ API_SYMBOLS = [
 GPU_SYMBOLS = [
     "awfmGpuDeviceCount", "awfmGpuLastError", "awfmGpuIndexCreate", "awfmGpuIndexDestroy", "awfmGpuIndexAcquire", "awfmGpuIndexAcquireAll",
     "awfmGpuIndexRelease", "awfmGpuIndexDeviceBytes", "awfmGpuIndexDevice", "awfmGpuIndexSetKernel", "awfmGpuIndexSetWide", "awfmGpuIndexIsWide", "awfmGpuLastBatchStatus", "awfmGpuIndexSetDeepSeed", "awfmGpuIndexSetDenseSa", "awfmGpuPinnedBuffer", "awfmGpuLocateHostWindows", "awfmGpuLocateWindow", "awfmGpuAosLock",
-    "awfmGpuAosUnlock", "awfmGpuSearch", "awfmGpuSearchHits", "awfmGpuSearchHitsSparse", "awfmGpuIndexSetOrdered", "awfmGpuSearchHitsIsOrdered", "awfmGpuLastOrderedKernelMs", "awfmGpuLastOrderedKernelIsLookup", "awfmGpuLastOrderedKept",
+    "awfmGpuAosUnlock", "awfmGpuSearch", "awfmGpuSearchHits", "awfmGpuSearchHitsSparse", "awfmGpuIndexSetOrdered", "awfmGpuSearchHitsIsOrdered", "awfmGpuLastOrderedKernelMs", "awfmGpuLastOrderedKernelIsLookup", "awfmGpuLastOrderedKept", "awfmGpuLastSecondWindow",
     "awfmGpuScanScratchBytes", "awfmGpuHitOffsets", "awfmGpuHitOffsetsFromCounts", "awfmGpuLocate", "awfmGpuCountHost", "awfmGpuLocateHost",
     "awfmGpuCreateIndex", "awfmGpuSearchTally", "awfmGpuSynthText", "awfmGpuSynthRandomQueries", "awfmGpuSynthPlantedQueries",
     "awfmGpuSynthMixedLengths", "awfmGpuSynthMixedQueries", "awfmGpuSynthGenomeText", "awfmGpuSynthPlantedQueriesClean",
@@ -199,6 +199,7 @@ def lib():
         "awfmGpuLastOrderedKernelMs": (C.c_double, [vp]),
         "awfmGpuLastOrderedKernelIsLookup": (C.c_int, [vp]),
         "awfmGpuLastOrderedKept": (C.c_uint64, [vp]),
+        "awfmGpuLastSecondWindow": (None, [vp, C.POINTER(C.c_uint64 * 2)]),
         "awfmGpuIndexSetDeepSeed": (C.c_int, [vp, C.c_uint]),
         "awfmGpuIndexSetDenseSa": (C.c_int, [vp, C.c_int]),
         "awfmGpuIndexSetPairImage": (C.c_int, [vp, C.c_int]),

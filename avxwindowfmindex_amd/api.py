@@ -1129,6 +1129,13 @@ class GpuIndex:
         """k-mers the last seed-order search with 8-byte records ordered and searched (awfmGpuLastOrderedKept)"""
         return int(_lib.lib().awfmGpuLastOrderedKept(self.handle))
 
+    def last_second_window(self):
+        """(tested, dropped): the survivors the lookup kernel of the last seed-order search put to its second table window, and
+        those it dropped there (awfmGpuLastSecondWindow)"""
+        out = (C.c_uint64 * 2)()
+        _lib.lib().awfmGpuLastSecondWindow(self.handle, C.byref(out))
+        return int(out[0]), int(out[1])
+
     def last_ordered_kernel_is_lookup(self):
         """the kernel last_ordered_kernel_ms() timed was encodeLookupKernel ("lookup first", include/awfm_gpu.h)"""
         return bool(_lib.lib().awfmGpuLastOrderedKernelIsLookup(self.handle))

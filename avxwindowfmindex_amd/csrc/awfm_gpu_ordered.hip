@@ -343,6 +343,27 @@ extern "C" uint64_t awfmGpuLastOrderedKept(AwFmGpuIndex *g) {
   return kept;
 }
 
+/* {survivors the lookup kernel of the last seed-order search put to its second table window, survivors that window dropped}:
+ * words 1 and 2 of the lines its waves count their survivors into (reporting; waits for the device).  Zeros when the last
+ * search did not run that kernel. */
+extern "C" void awfmGpuLastSecondWindow(AwFmGpuIndex *g, uint64_t out[2]) {
+  if (!out) return;
+  out[0] = out[1] = 0;
+  if (!g) return;
+  std::lock_guard<std::mutex> lock(g->orderMutex);
+  if (!g->orderLookupFused || !g->orderFusedKeptAt || !lastSearchLookedUpFirst(g)) return;
+  DeviceGuard guard(g->device);
+  unsigned words[kFusedCounters * 16u];
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(words, g->orderFusedKeptAt, sizeof words, hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    return;
+  }
+  for (unsigned i = 0; i < kFusedCounters; i++) {
+    out[0] += words[i * 16u + 1u];
+    out[1] += words[i * 16u + 2u];
+  }
+}
+
 /* milliseconds the dominant kernel of the last awfmGpuSearchHits* on this image took -- encodeLookupKernel when the batch
  * was one for "lookup first", orderedSearchKernel otherwise -- when the call ran with $AWFM_GPU_TIME_ORDERED set (waits
  * for it); negative when there is none */
@@ -799,6 +820,10 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
     {
       const bool pairOff = !pairSteps(g);
       const bool superInLds = !pairOff && narrow && awfmPairSuperInLds(g);
+      /* $AWFM_GPU_DIAG second_window=0|1: the kernel's second table window never / on every trip (bits 8 and 32 of its
+       * useNext; unset: its own gate decides, trip by trip) */
+      unsigned secondBits = 0u;
+      if (const char *env = awfmGpuDiag("second_window")) secondBits = atoi(env) == 0 ? 8u : 32u;
       DevIndex dev = g->image->dev;
       dev.pairSuperInLds = superInLds ? 1u : 0u;
       const size_t lds = superInLds ? (size_t)g->image->dev.numPairSuper * 64u : 0u;
@@ -819,7 +844,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
       /* (lookup only: what the kernel does not search itself goes to the END of the record array, 8 bytes a k-mer number,
        * counted in the general kernel's word -- no code words, no numbers, no histogram) */
 #define AWFM_LOOKUP_GO(NR)                                                                                                               \
-  launchLookupSearchAt<32u, NR>(fixedLength, fusedGrid, lds, s, dev, dChars, fmt, useNext | (pairOff ? 2u : 0u) | (lookupOnly ? 4u : 0u), nq, \
+  launchLookupSearchAt<32u, NR>(fixedLength, fusedGrid, lds, s, dev, dChars, fmt, useNext | (pairOff ? 2u : 0u) | (lookupOnly ? 4u : 0u) | secondBits, nq, \
                                 (unsigned long long *)(w + codesAt), lookupOnly ? (unsigned *)recs : numbers, lookupOnly ? generalCount : shareCount, \
                                 hist, binsPad, sampleAlive, kSamples, rng, dCounts, sparse ? *sparse : SparseOut(),                      \
                                 (unsigned *)(w + kKeptAt), timed ? g->orderTiming[0] : nullptr, timed ? g->orderTiming[1] : nullptr)

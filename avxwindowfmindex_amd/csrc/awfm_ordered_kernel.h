@@ -382,6 +382,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
   const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   unsigned blockBase = 0, blockUsed = 0, blockSlots = 0; /* the wave's block of slots in its share's region: general k-mers */
   unsigned hitFill = 0, keptHere = 0; /* wave-uniform */
+  /* the second window (below): the characters it takes -- the table's, and the two the next-step bits speak of --, whether
+   * this k-mer length has that many and one more, the hook's two bits ($AWFM_GPU_DIAG second_window: 8 never, 32 on every
+   * trip), the gate's estimate and what the wave reports.  All wave-uniform. */
+  const unsigned secondW = f.depth + ((useNext & 1u) != 0u ? 2u : 0u);
+  const bool second = K > secondW && (useNext & 8u) == 0u, forceSecond = (useNext & 32u) != 0u;
+  const unsigned secondShift = second ? 2u * (K - secondW) : 0u;
+  unsigned gateTested = 0, gateDropped = 0, testedHere = 0, droppedHere = 0, trip = 0;
   auto flushHits = [&]() {
     if (hitFill != 0u) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -522,12 +529,64 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
         }
       blockUsed += atotal;
     }
-    const unsigned inBatch = stotal < kFusedSlots ? stotal : kFusedSlots;
+    unsigned inBatch = stotal < kFusedSlots ? stotal : kFusedSlots;
     keptHere += inBatch;
+    trip++;
     if (inBatch != 0u) { /* wave-uniform */
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      /* the second window: a k-mer that occurs in the text has its LEFTMOST secondW characters in the text as well, which
+       * one more table line says -- an independent read, a lane per survivor -- where the steps below take 1-2 dependent
+       * lines to learn nothing (the first pair step cannot fail: the bit said so) and another to drop 94 % of the survivors
+       * of random k-mers.  The gate (wave-uniform) shuts it on batches whose survivors are mostly hits: the line pays
+       * when it drops more than about 40 %, which the wave estimates from what it has dropped so far (looking again every
+       * 16th trip).  A round with more survivors than slots -- more than a quarter of its k-mers alive, where looking the
+       * table up first does not pay either -- is not put to the window at all: a wave of a small batch makes one trip
+       * and has no estimate.  A k-mer with hits always passes: results do not depend on the gate. */
+      if (second && (forceSecond || (stotal <= kFusedSlots && (gateTested < 64u || 2u * gateDropped >= gateTested || (trip & 15u) == 0u)))) {
+        bool passes = false;
+        unsigned long long c = 0;
+        if (lane < inBatch) {
+          c = sCodes[w][lane];
+          const unsigned long long window = c >> secondShift;
+          const uint2 e = ((const uint2 *)ix.deepSeed)[window & tableMask];
+          passes = (e.y & lengthBits) != 0u &&
+                   ((useNext & 1u) == 0u || ((e.y >> (16u + ((unsigned)(window >> (2u * f.depth)) & 15u))) & 1u) != 0u);
+        }
+        const unsigned long long passMask = __ballot(passes);
+        const unsigned passed = (unsigned)__popcll(passMask);
+        if (passed != inBatch) { /* wave-uniform: the slots compacted to the k-mers that passed */
+          unsigned num = 0;
+          pos_t sp = 0, ep = 0;
+          if (passes) {
+            num = sNum[w][lane];
+            sp = sSp[w][lane];
+            ep = sEp[w][lane];
+          }
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          if (passes) {
+            const unsigned rank = (unsigned)__popcll(passMask & ((1ull << lane) - 1ull));
+            sCodes[w][rank] = c;
+            sNum[w][rank] = num;
+            sSp[w][rank] = sp;
+            sEp[w][rank] = ep;
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        testedHere += inBatch;
+        droppedHere += inBatch - passed;
+        gateTested += inBatch;
+        gateDropped += inBatch - passed;
+        if (gateTested >= 4096u) {
+          gateTested >>= 1;
+          gateDropped >>= 1;
+        }
+        inBatch = passed;
+      }
       for (unsigned pass = 0; pass < inBatch; pass += 64u / G) { /* wave-uniform */
         const unsigned slot = pass + lane / G;
         const bool live = slot < inBatch;
@@ -588,6 +647,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
   }
   for (unsigned at = blockUsed + lane; at < blockSlots; at += 64u) codesOut[first + blockBase + at] = kCodeNone;
   if (lane == 0 && keptHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u], keptHere);
+  /* (words 1 and 2 of the same line: the survivors put to the second window, and those it dropped) */
+  if (lane == 0 && testedHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u + 1u], testedHere);
+  if (lane == 0 && droppedHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u + 2u], droppedHere);
   if (LIST) { /* the waves' leftovers in one reservation, as in orderedSearchKernel */
     if (lane == 0) sHitLeft[w] = hitFill;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

@@ -85,6 +85,8 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   verify_group=16|32|64   awfmGpuVerifyChains: lanes per slot, where that is more than the band's diagonals need (a smaller
  *                       value than the band needs is ignored); the default is the smallest that holds the band
  *   align_group=16|32|64    awfmGpuAlignChains: lanes per read, in the same way
+ *   second_window=0|1   the lookup kernel's second table window (a survivor's leftmost characters): 0 never, 1 on every trip;
+ *                       unset, the kernel's own gate decides trip by trip (the results are the same either way)
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
 
 /* ---- device image ---- */
@@ -767,6 +769,10 @@ int awfmGpuOrderedKernelLog(AwFmGpuIndex *g, double *frontMs, double *kernelMs, 
 /* k-mers the last seed-order search with 8-byte records ordered and searched: the batch, or what the lookup-first pass kept
  * of it (reporting; waits for the device) */
 uint64_t awfmGpuLastOrderedKept(AwFmGpuIndex *g);
+/* out = {tested, dropped}: the survivors the lookup kernel of the last seed-order search put to its second table window -- the
+ * entry of a k-mer's LEFTMOST characters: a k-mer that occurs in the text has every window of itself in the text -- and those
+ * the window dropped before any step.  Zeros when that kernel did not run.  Reporting: waits for the device. */
+void awfmGpuLastSecondWindow(AwFmGpuIndex *g, uint64_t out[2]);
 
 /* Instrumented run of the same kernel for the roofline accounting: tallyOut =
  * {queries that used the seed table, backward steps executed, distinct blocks over those steps,
