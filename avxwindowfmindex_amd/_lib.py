@@ -45,6 +45,7 @@ GPU_SYMBOLS = [
     "awfmReadChains", "awfmGpuReadChains", "awfmGpuReadChainsScratchBytes",
     "awfmGpuIndexSetText", "awfmGpuIndexTextLength", "awfmTextWindows", "awfmGpuTextWindows", "awfmVerifyChains", "awfmGpuVerifyChains",
     "awfmAlignChains", "awfmGpuAlignChainsScratchBytes", "awfmGpuAlignChains",
+    "awfmAlignChainsAffine", "awfmGpuAlignChainsAffineScratchBytes", "awfmGpuAlignChainsAffine",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -109,6 +110,18 @@ class AwFmAlignOutputs(C.Structure):
     """struct AwFmAlignOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
     _fields_ = [("editDistances", C.c_void_p), ("textBegins", C.c_void_p), ("textEnds", C.c_void_p), ("numOps", C.c_void_p),
                 ("ops", C.c_void_p), ("numUnaligned", C.c_void_p), ("numTruncated", C.c_void_p)]
+
+
+class AwFmAlignScoring(C.Structure):
+    """struct AwFmAlignScoring (include/awfm_gpu.h): match 1..255, mismatch 0..255, gapOpen 0..255, gapExtend 1..255"""
+    _fields_ = [("match", C.c_uint32), ("mismatch", C.c_uint32), ("gapOpen", C.c_uint32), ("gapExtend", C.c_uint32)]
+
+
+class AwFmAffineOutputs(C.Structure):
+    """struct AwFmAffineOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("scores", C.c_void_p), ("editDistances", C.c_void_p), ("readBegins", C.c_void_p), ("readEnds", C.c_void_p),
+                ("textBegins", C.c_void_p), ("textEnds", C.c_void_p), ("numOps", C.c_void_p), ("ops", C.c_void_p),
+                ("numUnaligned", C.c_void_p), ("numTruncated", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -276,6 +289,11 @@ def lib():
         "awfmGpuAlignChainsScratchBytes": (u64, [vp, C.c_uint32]),
         "awfmGpuAlignChains": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.POINTER(AwFmAlignOutputs), vp, vp]),
+        "awfmAlignChainsAffine": (C.c_int, [C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmAlignScoring),
+                                            C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmAffineOutputs), C.c_uint]),
+        "awfmGpuAlignChainsAffineScratchBytes": (u64, [vp, C.c_uint32]),
+        "awfmGpuAlignChainsAffine": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmAffineOutputs), vp, vp]),
         "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),
         "awfmGpuIndexNumRecords": (C.c_uint32, [vp]),
         "awfmGpuLocalPositions": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),

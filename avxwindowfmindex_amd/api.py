@@ -523,7 +523,7 @@ def verify_chains_host(read_chars, read_offsets, slots, text, sequence_ends=None
 ALIGN_MAX_LENGTH = 1 << 16  # AWFM_ALIGN_MAX_LENGTH: read characters per aligned read
 ALIGN_MAX_OPS = 4096  # AWFM_ALIGN_MAX_OPS: upper limit of max_ops
 ALIGN_OVERHANG = 0xFFFFFFFB  # AWFM_ALIGN_OVERHANG, beside VERIFY_NONE .. VERIFY_TOO_LONG
-ALIGN_OP_LETTERS = {1: "I", 2: "D", 7: "=", 8: "X"}  # BAM numbering of the operations a run carries in its low four bits
+ALIGN_OP_LETTERS = {1: "I", 2: "D", 4: "S", 7: "=", 8: "X"}  # BAM numbering of the operations a run carries in its low four bits
 ALIGN_READ_OUTPUTS = (("editDistances", np.uint32), ("textBegins", np.uint64), ("textEnds", np.uint64), ("numOps", np.uint32))
 
 
@@ -583,6 +583,75 @@ def align_chains_host(read_chars, read_offsets, slots, chosen, text, sequence_en
                                     None if ends is None or not ends.size else ends.ctypes.data, 0 if ends is None else ends.size, alphabet,
                                     C.byref(aout), threads)
     _check("awfmAlignChains", rc)
+    for name, counter in counters.items():
+        if name in outputs:
+            result[name] = int(counter[0])
+    return result
+
+
+AFFINE_READ_OUTPUTS = (("scores", np.uint32), ("editDistances", np.uint32), ("readBegins", np.uint32), ("readEnds", np.uint32),
+                       ("textBegins", np.uint64), ("textEnds", np.uint64), ("numOps", np.uint32))
+AFFINE_SCORING = (1, 4, 6, 1)  # match, mismatch, gapOpen, gapExtend: the scoring of the examples and the measurements
+
+
+def align_scoring(match=1, mismatch=4, gap_open=6, gap_extend=1):
+    """struct AwFmAlignScoring: a gap of g characters costs gap_open + g * gap_extend"""
+    return _lib.AwFmAlignScoring(match, mismatch, gap_open, gap_extend)
+
+
+def affine_outputs(**addresses):
+    """struct AwFmAffineOutputs from addresses by field name (scores, editDistances, readBegins, readEnds, textBegins, textEnds,
+    numOps, ops, numUnaligned, numTruncated); a field left out is NULL"""
+    out = _lib.AwFmAffineOutputs()
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmAffineOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def align_chains_affine_host(read_chars, read_offsets, slots, chosen, text, sequence_ends=None, alphabet=AwFmAlphabetDna, band_pad=8,
+                             max_drift=15, scoring=AFFINE_SCORING, max_ops=32, threads=4, outputs=None, num_read_chars=None, fill=None,
+                             unaligned_before=0, truncated_before=0):
+    """awfmAlignChainsAffine (include/awfm_gpu.h, "affine alignment"): the inputs of align_chains_host and `scoring` = (match,
+    mismatch, gap_open, gap_extend) -> a dict of scores, editDistances, readBegins, readEnds, textBegins, textEnds, numOps per read,
+    ops shaped (reads, max_ops), numUnaligned and numTruncated (ints: the values before plus this call's).  outputs: the names to
+    compute (None: all); the others are passed as NULL and left out.  fill: the value (per byte) the arrays hold before the call."""
+    chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
+    t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    ends = None if sequence_ends is None else np.ascontiguousarray(sequence_ends, dtype=np.uint64)
+    n = max(o.size - 1, 0)
+    arrays = {name: np.ascontiguousarray(slots[name], dtype=dtype) for name, dtype in VERIFY_SLOT_INPUTS}
+    shape = arrays["sequences"].shape
+    which = np.ascontiguousarray(chosen, dtype=np.uint32)
+    if len(shape) != 2 or shape[0] != n or any(a.shape != shape for a in arrays.values()) or which.shape != (n,):
+        raise ValueError("the slot arrays are shaped (reads, max_candidates), the chosen slots (reads,)")
+    names = [name for name, _ in AFFINE_READ_OUTPUTS] + ["ops", "numUnaligned", "numTruncated"]
+    outputs = names if outputs is None else list(outputs)
+    result = {name: np.zeros(n, dtype) for name, dtype in AFFINE_READ_OUTPUTS if name in outputs}
+    if "ops" in outputs:
+        result["ops"] = np.zeros((n, max(int(max_ops), 0)), np.uint32)
+    for a in result.values():
+        if fill is not None:
+            a.view(np.uint8)[...] = fill
+    counters = {"numUnaligned": np.array([unaligned_before], np.uint64), "numTruncated": np.array([truncated_before], np.uint64)}
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else dummy.ctypes.data
+
+    vin = verify_inputs(address(chars), chars.size if num_read_chars is None else num_read_chars, address(o),
+                        **{name: address(a) for name, a in arrays.items()})
+    aout = affine_outputs(**{name: address(a) for name, a in result.items()})
+    for name, counter in counters.items():
+        if name in outputs:
+            setattr(aout, name, counter.ctypes.data)
+    costs = scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+    rc = _lib.lib().awfmAlignChainsAffine(C.byref(vin), address(which), n, shape[1], band_pad, max_drift, C.byref(costs), max_ops, address(t),
+                                          t.size, None if ends is None or not ends.size else ends.ctypes.data,
+                                          0 if ends is None else ends.size, alphabet, C.byref(aout), threads)
+    _check("awfmAlignChainsAffine", rc)
     for name, counter in counters.items():
         if name in outputs:
             result[name] = int(counter[0])
@@ -818,6 +887,24 @@ class GpuIndex:
         _check("awfmGpuAlignChains", _lib.lib().awfmGpuAlignChains(self.handle, C.byref(inputs), d_slots or None, num_reads, max_candidates,
                                                                    band_pad, max_drift, max_ops, max_rows, C.byref(outputs),
                                                                    d_scratch or None, stream or None))
+
+    # affine alignment (include/awfm_gpu.h) -------------------------------
+    def align_chains_affine_scratch_bytes(self, max_rows):
+        """awfmGpuAlignChainsAffineScratchBytes: the bytes of device scratch align_chains_affine needs for reads of up to max_rows
+        characters"""
+        return int(_lib.lib().awfmGpuAlignChainsAffineScratchBytes(self.handle, max_rows))
+
+    def align_chains_affine(self, inputs, d_slots, num_reads, outputs, d_scratch, max_candidates=4, band_pad=8, max_drift=15,
+                            scoring=AFFINE_SCORING, max_ops=32, max_rows=4096, stream=0):
+        """awfmGpuAlignChainsAffine: inputs verify_inputs(...) and outputs affine_outputs(...) of device addresses, d_slots the slot of
+        every read to align (bestSlots of read_chains or verify_chains), scoring (match, mismatch, gap_open, gap_extend) or an
+        align_scoring(...), d_scratch align_chains_affine_scratch_bytes(max_rows) bytes of device memory of this call's own,
+        aligned to 16 bytes; asynchronous on `stream`; *numUnaligned and *numTruncated are added to"""
+        costs = None if scoring is None else scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+        _check("awfmGpuAlignChainsAffine",
+               _lib.lib().awfmGpuAlignChainsAffine(self.handle, C.byref(inputs), d_slots or None, num_reads, max_candidates, band_pad, max_drift,
+                                                   None if costs is None else C.byref(costs), max_ops, max_rows, C.byref(outputs),
+                                                   d_scratch or None, stream or None))
 
     def locate_host_local(self, chars, offsets=None, fixed_length=0):
         """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],

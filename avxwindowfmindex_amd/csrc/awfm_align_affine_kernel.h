@@ -1,0 +1,320 @@
+/*
+ * awfm_align_affine_kernel.h -- alignChainsAffineKernel<G>, the kernel of "affine alignment" (include/awfm_gpu.h): the banded local
+ * alignment with affine gap costs of every read against the record its chosen slot names, with soft clipping and the walk back
+ * that emits the edit script.  The definition is the header's; the host twin and checker is awfm_align_affine.c.
+ *
+ * The layout is alignChainsKernel<G>'s (awfm_align_kernel.h): a group of G lanes per read (persistent grid over reads), lane k is
+ * diagonal lo + k of the band in sequence-local coordinates, the rows go in chunks of kVerifyChunk whose read characters and
+ * text characters the group stages into its own words of LDS through stageBytes -- EVERY LOAD OF TEXT OR READ is an aligned
+ * dword that holds a byte the slot owns, and the record is checked against the text's length before anything is read; only
+ * aligned reads load text.  A lane carries H and F of the previous row; M comes from the lane itself, F from lane k + 1.  The
+ * horizontal value is one exclusive max-prefix-scan per row over the group: E[k] = max over k' < k of (H~[k'] + k' e) - o - k e
+ * with H~ = max(0, M, F) -- a gap that extends from a cell whose H came from E pays o twice and is dominated, so
+ * the scan's E is the recurrence's.  Lanes and rows without a cell carry kAffineNeg and need no other case: max(0, ...) is
+ * taken for existing cells only, and their trace code is "stop".
+ *
+ * THE TRACE.  Five wave-wide ballots give a row: three bits of the source of H (0 stop, 1 diagonal with equal letters, 2
+ * diagonal with a substitution, 3 F, 4 E), "F of this cell opens its gap above" and "E of this cell opens its gap on the
+ * left".  A group keeps its G bits of each -- 5 G / 8 bytes a row, kAffineRowBytes = 40 per row and wave whatever G --
+ * and lane 0 stores them as row i - 1 of the group's part of the wave's arena in dScratch.  The end cell -- largest H, then
+ * smallest i, then smallest k -- is each lane's own best (strict-greater update, no reduction per row) and one butterfly over
+ * the group.  A fence orders the stores before the loads of the walk: every lane of the group walks back from the end cell
+ * through the arena in the three states H, F, E -- the same addresses and the same state in all of them, neither read nor text
+ * --, lane 0 writes the runs, last to first, and turns them round when they fit maxOps.  Counters take one atomic per wave.
+ * Vector loads and stores only.
+ */
+#ifndef AWFM_ALIGN_AFFINE_KERNEL_H
+#define AWFM_ALIGN_AFFINE_KERNEL_H
+
+#include "awfm_verify_kernel.h"
+
+namespace {
+
+constexpr unsigned kAffineThreads = 256;    /* per workgroup: four waves */
+constexpr unsigned kAffineLdsBytes = 3360;  /* static LDS at G = 16, the most groups: 16 x 52 words and the amino letter table */
+constexpr unsigned kAffineBlocksPerCU = 4;  /* up to 128 VGPRs: four waves per SIMD, i.e. four workgroups of four waves per CU */
+constexpr unsigned kAffineRowBytes = 40;    /* of trace per row and wave: five ballots of 64 lanes, whatever G */
+static_assert(kAffineLdsBytes == (kAffineThreads / 16u) * kVerifyGroupWords * 4u + 32u, "the staging words of sixteen groups and the letter table");
+constexpr int kAffineNeg = -0x40000000; /* minus infinity: a lane resets it every row, so it only has to survive o + 64 e */
+
+struct DevAffineParams {
+  struct AwFmVerifyInputs in;
+  struct AwFmAffineOutputs out;
+  const unsigned *chosen;
+  const unsigned char *text;
+  unsigned long long length;
+  const unsigned long long *ends; /* the image's record table; numRecords == 0: one sequence [0, length) */
+  unsigned numRecords;
+  unsigned long long numReads;
+  unsigned char *arena; /* kAffineRowBytes * maxRows bytes per wave of the grid */
+  unsigned slots, pad, drift, amino, maxOps, maxRows;
+  int match, mismatch, open, extend; /* open: what the first character of a gap costs, o + e */
+};
+
+struct DevAffineAlignment {
+  unsigned distance, readBegin, readEnd, numOps;
+  unsigned long long textBegin, textEnd;
+};
+
+/* a group's G bits of one ballot: five of them make its row of trace */
+template <int G>
+struct AffineBits {
+  typedef unsigned short type;
+};
+template <>
+struct AffineBits<32> {
+  typedef unsigned type;
+};
+template <>
+struct AffineBits<64> {
+  typedef unsigned long long type;
+};
+
+/* the group's bits of ballot q of a row (above bit G - 1: the groups behind this one) */
+template <int G>
+__device__ __forceinline__ void storeAffineBits(unsigned char *trace, unsigned row, unsigned q, unsigned long long bits) {
+  typedef typename AffineBits<G>::type Bits;
+  ((Bits *)trace)[row * 5u + q] = (Bits)bits;
+}
+
+/* the five bits of lane k's cell in that row: source in bits 0 .. 2, F opens in bit 3, E opens in bit 4 */
+template <int G>
+__device__ __forceinline__ unsigned loadAffineCode(const unsigned char *trace, unsigned row, unsigned k) {
+  typedef typename AffineBits<G>::type Bits;
+  const Bits *bits = (const Bits *)trace + row * 5u;
+  unsigned code = 0;
+#pragma unroll
+  for (unsigned q = 0; q < 5u; q++) code |= (unsigned)((bits[q] >> (k & (unsigned)(G - 1))) & 1u) << q;
+  return code;
+}
+
+/* a run of the script, met last to first: lane 0 stores a finished one */
+struct AffineRuns {
+  unsigned *ops;
+  unsigned maxOps, numOps, run, op;
+  bool writer;
+  __device__ __forceinline__ void flush() {
+    if (!run) return;
+    if (ops && writer && numOps < maxOps) ops[numOps] = run << 4 | op;
+    numOps++;
+    run = 0;
+  }
+  __device__ __forceinline__ void emit(unsigned now, unsigned count) {
+    if (!count) return;
+    if (run && now != op) flush();
+    op = now;
+    run += count;
+  }
+};
+
+/* the status of read r (header: UNUSED .. TOO LONG) or its score; every lane of the group returns the same */
+template <int G>
+__device__ __forceinline__ unsigned alignReadAffine(const DevAffineParams &p, const unsigned long long r, unsigned *sRead, unsigned *sText,
+                                                    const unsigned char *sAmino, unsigned char *trace, const unsigned k,
+                                                    const unsigned groupShift, DevAffineAlignment &a) {
+  const unsigned j = p.chosen[r];
+  if (j == AWFM_CHAINS_NO_SLOT) return AWFM_VERIFY_NONE;
+  if (j >= p.slots) return AWFM_VERIFY_MALFORMED;
+  const unsigned long long at = r * p.slots + j;
+  const unsigned s = p.in.sequences[at];
+  if (s == AWFM_CANDIDATES_NONE || p.in.chainAnchors[at] == 0u) return AWFM_VERIFY_NONE;
+  const unsigned long long readBegin = p.in.readOffsets[r], readEnd = p.in.readOffsets[r + 1ull];
+  if (readBegin > readEnd || readEnd > p.in.numReadChars) return AWFM_VERIFY_MALFORMED;
+  const unsigned long long rb = p.in.chainReadBegins[at], re = p.in.chainReadEnds[at], n64 = readEnd - readBegin;
+  if (rb > re || re > n64) return AWFM_VERIFY_MALFORMED;
+  if (s >= (p.numRecords ? p.numRecords : 1u)) return AWFM_VERIFY_MALFORMED;
+  const unsigned long long S = p.numRecords && s ? p.ends[s - 1u] + 1ull : 0ull, E = p.numRecords ? p.ends[s] : p.length;
+  if (E < S || E > p.length) return AWFM_VERIFY_MALFORMED;
+  const long long bD = p.in.chainBeginDiagonals[at], eD = p.in.chainEndDiagonals[at];
+  /* E - S < 2^62 and rb, re < 2^32: a diagonal outside [-2^33, 2^62] makes tb < 0, tb > te or te > E - S whatever the other is,
+   * and inside it the sums are exact in 64 bits */
+  if (bD < -(1ll << 33) || eD < -(1ll << 33) || bD > (1ll << 62) || eD > (1ll << 62)) return AWFM_VERIFY_MALFORMED;
+  const long long tb = (long long)rb + bD, te = (long long)re + eD, L = (long long)(E - S);
+  if (tb < 0 || tb > te || te > L) return AWFM_VERIFY_MALFORMED;
+  const long long delta = eD - bD;
+  if (delta > (long long)p.drift || delta < -(long long)p.drift) return AWFM_VERIFY_TOO_WIDE;
+  if (n64 > (unsigned long long)p.maxRows) return AWFM_VERIFY_TOO_LONG;
+  const int n = (int)n64; /* <= 2^16 */
+  const long long lo = (bD < eD ? bD : eD) - (long long)p.pad, hi = (bD > eD ? bD : eD) + (long long)p.pad;
+  if (n == 0 || (long long)n + hi < 0 || lo + 1 > L) return 0u; /* no existing cell with i >= 1: nothing is aligned, nothing is read */
+  /* columns counted from lo: lane k's cell of row i is u = i + k, t = lo + u; it exists for uMin <= u <= uMax inside the band.
+   * Here -n - 63 <= lo <= L - 1, so uMin <= n + 63 and uMax >= 1; what lies beyond 2^30 is beyond every row */
+  const int width = (int)(hi - lo) + 1;
+  const int uMin = lo < 0 ? (int)-lo : 0, uMax = L - lo < (1ll << 30) ? (int)(L - lo) : 1 << 30;
+  const int uOne = lo < 1 ? (int)(1 - lo) : 0; /* t >= 1 from here on: the cell has a diagonal predecessor */
+  const bool inBand = (int)k < width;
+  const unsigned char *R = p.in.readChars + readBegin, *T = p.text + S;
+  const unsigned char *sReadBytes = (const unsigned char *)sRead, *sTextBytes = (const unsigned char *)sText;
+  const unsigned proper = p.amino ? 20u : 4u;
+  const int kExtend = (int)k * p.extend;
+  int prevH = inBand && (int)k >= uMin && (int)k <= uMax ? 0 : kAffineNeg, prevF = kAffineNeg; /* row 0: H(0, t) = 0 */
+  int bestH = 0, bestI = 0;
+  for (int i0 = 0; i0 < n; i0 += (int)kVerifyChunk) {
+    const int rows = n - i0 < (int)kVerifyChunk ? n - i0 : (int)kVerifyChunk;
+    /* the text characters T[t - 1] of the chunk's rows i0 + 1 .. i0 + rows: u - 1 = i0 .. i0 + rows + width - 2, cut to the record */
+    const int uFrom = i0 > uMin ? i0 : uMin, uTo = i0 + rows + width - 1 < uMax ? i0 + rows + width - 1 : uMax;
+    __builtin_amdgcn_wave_barrier(); /* (the rows of the chunk before have read their bytes) */
+    const unsigned rOff = stageBytes<G>(R, (unsigned long long)i0, (unsigned long long)(i0 + rows), sRead, k);
+    const unsigned tOff = uTo > uFrom ? stageBytes<G>(T, (unsigned long long)(lo + uFrom), (unsigned long long)(lo + uTo), sText, k) : 0u;
+    __builtin_amdgcn_wave_barrier();
+    for (int q = 0; q < rows; q++) {
+      const int u = i0 + q + 1 + (int)k;
+      const bool inMatrix = inBand && u >= uMin && u <= uMax;
+      const unsigned rLetter = verifyLetter(sAmino, p.amino, sReadBytes[rOff + (unsigned)q]);
+      unsigned tLetter = 0xFFu;
+      if (inMatrix && u >= uOne) tLetter = verifyLetter(sAmino, p.amino, sTextBytes[tOff + (unsigned)(u - 1 - uFrom)]);
+      const bool sub = !(rLetter == tLetter && rLetter < proper);
+      int upH = __shfl_down(prevH, 1, G), upF = __shfl_down(prevF, 1, G);
+      upH = k == (unsigned)(G - 1) ? kAffineNeg : upH;
+      upF = k == (unsigned)(G - 1) ? kAffineNeg : upF;
+      const int M = prevH + (sub ? -p.mismatch : p.match); /* (prevH is kAffineNeg when t = 0) */
+      const int fOpens = upH - p.open, fExtends = upF - p.extend;
+      const int F = fOpens > fExtends ? fOpens : fExtends;
+      int tilde = M > F ? M : F;
+      tilde = tilde > 0 ? tilde : 0;
+      tilde = inMatrix ? tilde : kAffineNeg;
+      /* E[k] + o + k e = max over k' < k of H~[k'] + k' e: shifted by a lane, then the inclusive scan */
+      int v = __shfl_up(tilde + kExtend, 1, G);
+      v = k == 0u ? kAffineNeg : v;
+#pragma unroll
+      for (int step = 1; step < G; step <<= 1) {
+        const int other = __shfl_up(v, step, G);
+        v = (int)k >= step && other > v ? other : v;
+      }
+      const int e = v - (p.open - p.extend) - kExtend;
+      const int h = inMatrix ? (tilde > e ? tilde : e) : kAffineNeg;
+      int leftH = __shfl_up(h, 1, G);
+      leftH = k == 0u ? kAffineNeg : leftH;
+      const unsigned source = !inMatrix || h == 0 ? 0u : M == h ? (sub ? 2u : 1u) : F == h ? 3u : 4u;
+      /* the five ballots, each out of the scalar registers and into the arena at once */
+      const bool bit[5] = {(source & 1u) != 0u, (source & 2u) != 0u, (source & 4u) != 0u, fOpens >= fExtends,
+                           e == leftH - p.open /* e = max(leftH - o - e, E[k - 1] - e) */};
+#pragma unroll
+      for (unsigned b = 0; b < 5u; b++) {
+        unsigned long long bits = __builtin_amdgcn_ballot_w64(bit[b]) >> groupShift;
+        asm volatile("" : "+v"(bits));
+        if (k == 0u) storeAffineBits<G>(trace, (unsigned)(i0 + q), b, bits);
+      }
+      if (h > bestH) { /* (strictly: the smallest i of the lane's largest H) */
+        bestH = h;
+        bestI = i0 + q + 1;
+      }
+      prevH = h;
+      prevF = inMatrix ? F : kAffineNeg;
+    }
+  }
+  /* the end cell: the largest H, then the smallest i, then the smallest k.  H < 2^24, i <= 2^16 */
+  unsigned long long key = ((unsigned long long)(unsigned)bestH << 32) | ((unsigned long long)(0x1FFFFu - (unsigned)bestI) << 6) | (63u - k);
+#pragma unroll
+  for (int step = 1; step < G; step <<= 1) {
+    const unsigned otherLow = (unsigned)__shfl_xor((int)(unsigned)key, step, G), otherHigh = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), step, G);
+    const unsigned long long other = ((unsigned long long)otherHigh << 32) | otherLow;
+    key = other > key ? other : key;
+  }
+  const unsigned score = (unsigned)(key >> 32);
+  if (score == 0u) return 0u;
+  int i = (int)(0x1FFFFu - ((unsigned)(key >> 6) & 0x1FFFFu));
+  unsigned at2 = 63u - ((unsigned)key & 63u);
+  a.readEnd = (unsigned)i;
+  a.textEnd = (unsigned long long)(lo + (long long)i + (long long)at2);
+  __threadfence_block(); /* the rows lane 0 stored are read by every lane of the group */
+  AffineRuns runs = {p.out.ops ? p.out.ops + r * p.maxOps : nullptr, p.maxOps, 0u, 0u, 0u, k == 0u};
+  runs.emit(AWFM_ALIGN_OP_S, (unsigned)(n - i));
+  unsigned state = 0u, distance = 0u; /* 0 H, 1 F, 2 E */
+  /* (n steps to row 0 and at most n + 63 to the left; the bound only matters to a trace that is not this call's own) */
+  for (int budget = 2 * n + 64; i > 0 && budget > 0; budget--) {
+    const unsigned code = loadAffineCode<G>(trace, (unsigned)(i - 1), at2);
+    if (state == 0u) {
+      const unsigned source = code & 7u;
+      if (source == 0u || source > 4u) break;
+      if (source <= 2u) {
+        runs.emit(source == 2u ? 8u : 7u, 1u);
+        distance += source == 2u ? 1u : 0u;
+        i--;
+        continue;
+      }
+      state = source == 3u ? 1u : 2u;
+    }
+    distance++;
+    if (state == 1u) {
+      runs.emit(1u, 1u);
+      state = code & 8u ? 0u : 1u;
+      i--;
+      at2++;
+    } else {
+      runs.emit(2u, 1u);
+      state = code & 16u ? 0u : 2u;
+      at2--;
+    }
+  }
+  runs.emit(AWFM_ALIGN_OP_S, (unsigned)i);
+  runs.flush();
+  a.distance = distance;
+  a.readBegin = (unsigned)i;
+  a.textBegin = (unsigned long long)(lo + (long long)i + (long long)(int)at2);
+  a.numOps = runs.numOps;
+  if (runs.ops && k == 0u && runs.numOps <= p.maxOps) /* (the lane that stored them: its loads follow its stores) */
+    for (unsigned q = 0; q < runs.numOps / 2u; q++) {
+      const unsigned other = runs.ops[runs.numOps - 1u - q];
+      runs.ops[runs.numOps - 1u - q] = runs.ops[q];
+      runs.ops[q] = other;
+    }
+  return score;
+}
+
+template <int G>
+__global__ void __launch_bounds__(kAffineThreads, 4) alignChainsAffineKernel(const DevAffineParams args) {
+  constexpr unsigned kGroupsPerWave = 64u / (unsigned)G;
+  /* the arguments live in vector registers, as in alignChainsKernel: the addresses, the nested loops' masks and five ballots a
+   * row are more scalar registers than a wave has, and the compiler would spill some of them into lanes of a vector register */
+  DevAffineParams p = args;
+  asm volatile("" : "+v"(p.in.sequences), "+v"(p.in.chainAnchors), "+v"(p.in.chainReadBegins), "+v"(p.in.chainReadEnds));
+  asm volatile("" : "+v"(p.in.chainBeginDiagonals), "+v"(p.in.chainEndDiagonals), "+v"(p.out.scores), "+v"(p.out.editDistances));
+  asm volatile("" : "+v"(p.out.readBegins), "+v"(p.out.readEnds), "+v"(p.out.textBegins), "+v"(p.out.textEnds));
+  asm volatile("" : "+v"(p.out.numOps), "+v"(p.out.ops), "+v"(p.chosen), "+v"(p.in.readOffsets));
+  asm volatile("" : "+v"(p.in.readChars), "+v"(p.in.numReadChars), "+v"(p.text), "+v"(p.ends));
+  asm volatile("" : "+v"(p.length), "+v"(p.out.numUnaligned), "+v"(p.out.numTruncated), "+v"(p.numReads));
+  asm volatile("" : "+v"(p.numRecords), "+v"(p.slots), "+v"(p.pad), "+v"(p.drift), "+v"(p.maxOps), "+v"(p.maxRows));
+  __shared__ unsigned sStage[kAffineThreads / (unsigned)G][kVerifyGroupWords];
+  __shared__ unsigned char sAmino[32];
+  if (threadIdx.x < 32u) sAmino[threadIdx.x] = kAminoTables.letterOfAscii[threadIdx.x];
+  __syncthreads();
+  const unsigned lane = threadIdx.x & 63u, k = lane % (unsigned)G, groupInWave = lane / (unsigned)G;
+  unsigned *sRead = sStage[threadIdx.x / (unsigned)G], *sText = sRead + kVerifyReadWords;
+  const unsigned long long wave = (unsigned long long)blockIdx.x * (kAffineThreads / 64u) + threadIdx.x / 64u;
+  const unsigned long long numGroups = (unsigned long long)gridDim.x * (kAffineThreads / 64u) * kGroupsPerWave;
+  /* the wave's arena, and in it the group's rows */
+  unsigned char *trace = p.arena + wave * ((unsigned long long)kAffineRowBytes * p.maxRows) +
+                         (unsigned long long)groupInWave * ((unsigned long long)(5 * G / 8) * p.maxRows);
+  unsigned unaligned = 0, truncated = 0;
+  for (unsigned long long r = wave * kGroupsPerWave + groupInWave; r < p.numReads; r += numGroups) {
+    DevAffineAlignment a = {0u, 0u, 0u, 0u, 0ull, 0ull};
+    const unsigned value = alignReadAffine<G>(p, r, sRead, sText, sAmino, trace, k, groupInWave * (unsigned)G, a);
+    if (value >= AWFM_VERIFY_TOO_LONG) {
+      unaligned += value != AWFM_VERIFY_NONE && k == 0u ? 1u : 0u;
+    } else {
+      truncated += a.numOps > p.maxOps && k == 0u ? 1u : 0u;
+    }
+    if (k == 0u) {
+      if (p.out.scores) p.out.scores[r] = value;
+      if (p.out.editDistances) p.out.editDistances[r] = a.distance;
+      if (p.out.readBegins) p.out.readBegins[r] = a.readBegin;
+      if (p.out.readEnds) p.out.readEnds[r] = a.readEnd;
+      if (p.out.textBegins) p.out.textBegins[r] = a.textBegin;
+      if (p.out.textEnds) p.out.textEnds[r] = a.textEnd;
+      if (p.out.numOps) p.out.numOps[r] = a.numOps;
+    }
+  }
+  /* one atomic per wave and counter that met any */
+#pragma unroll
+  for (int offset = 32; offset > 0; offset >>= 1) {
+    unaligned += (unsigned)__shfl_xor((int)unaligned, offset, 64);
+    truncated += (unsigned)__shfl_xor((int)truncated, offset, 64);
+  }
+  if (lane == 0u && unaligned && p.out.numUnaligned) atomicAdd((unsigned long long *)p.out.numUnaligned, (unsigned long long)unaligned);
+  if (lane == 0u && truncated && p.out.numTruncated) atomicAdd((unsigned long long *)p.out.numTruncated, (unsigned long long)truncated);
+}
+
+}  // namespace
+
+#endif

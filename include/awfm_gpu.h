@@ -85,6 +85,7 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   verify_group=16|32|64   awfmGpuVerifyChains: lanes per slot, where that is more than the band's diagonals need (a smaller
  *                       value than the band needs is ignored); the default is the smallest that holds the band
  *   align_group=16|32|64    awfmGpuAlignChains: lanes per read, in the same way
+ *   affine_group=32|64      awfmGpuAlignChainsAffine: lanes per read, in the same way
  *   second_window=0|1   the lookup kernel's second table window (a survivor's leftmost characters): 0 never, 1 on every trip;
  *                       unset, the kernel's own gate decides trip by trip (the results are the same either way)
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
@@ -723,6 +724,89 @@ uint64_t awfmGpuAlignChainsScratchBytes(const AwFmGpuIndex *g, uint32_t maxRows)
 enum AwFmReturnCode awfmGpuAlignChains(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, const uint32_t *dSlots, uint64_t numReads,
                                        uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift, uint32_t maxOps, uint32_t maxRows,
                                        const struct AwFmAlignOutputs *dOut, void *dScratch, void *stream);
+
+/* ---- affine alignment: the scored local alignment of a read against its record, with soft clipping ----
+ * A stage BESIDE chain alignment, for callers that report what a read mapper reports: an alignment score under affine gap
+ * costs, a script whose gaps are whole runs, and clips ('S') where the read's ends do not pay.  Inputs, slots, C = maxCandidates,
+ * bandPad w, maxDrift x, maxOps, maxRows, text, record table and alphabet are chain alignment's, as are the error codes, the
+ * NULL rules, "every output may be NULL" and "counters are added to".  scoring: match 1..255, mismatch 0..255, gapOpen o 0..255,
+ * gapExtend e 1..255 (a value outside its range: AwFmIllegalPositionError; scoring == NULL: AwFmNullPtrError); a gap of g
+ * characters costs o + g e.  One definition on both sides, the host twin (csrc/awfm_align_affine.c) being the definition and
+ * the checker of the device call.
+ *
+ * Per read, in this order, with j = slots[r] and n the length of the WHOLE read:
+ *   UNUSED, MALFORMED, TOO WIDE, TOO LONG exactly as in chain alignment; the value goes to scores, the read's other outputs are
+ *   0 and its row of ops is not written.  There is NO OVERHANG: a band that leaves the record clips the read.
+ *   otherwise the BANDED LOCAL ALIGNMENT of R = the whole read against the record T of length L (sequence-local coordinates),
+ *   with lo = min(bD, eD) - w and hi = max(bD, eD) + w:
+ *     cells       (i, t) exists for 0 <= i <= n, 0 <= t <= L, lo <= t - i <= hi; a row may have no cell.  A cell has three values
+ *                 H, E, F in exact signed arithmetic; the values of a cell that does not exist are minus infinity;
+ *     s(R, T)     + match when verification's sub is 0, - mismatch otherwise (an ambiguity letter matches nothing);
+ *     recurrence  row 0: H(0, t) = 0, E = F = -inf.  For i >= 1:
+ *                   M = H(i-1, t-1) + s(R[i-1], T[t-1]);
+ *                   F(i, t) = max(H(i-1, t) - o - e, F(i-1, t) - e);
+ *                   E(i, t) = max(H(i, t-1) - o - e, E(i, t-1) - e);
+ *                   H(i, t) = max(0, M, F, E).
+ *                 H <= 2^16 * 255 < 2^24: everything fits 32 bits, and the stand-in for -inf only has to survive one
+ *                 subtraction of o + 64 e;
+ *     end cell    the existing cell with i >= 1 of the largest H; ties go to the smallest i, then the smallest t (on equal
+ *                 score the shorter alignment).  score is that H.  When it is 0 (also n = 0, or no existing cell with i >= 1)
+ *                 NOTHING is aligned: every other output of the read is 0, numOps is 0, the read is counted nowhere;
+ *     walk back   from the end cell in state H; each decision is a function of the cell alone.
+ *                   state H: stop when H = 0 (readBegin = i, textBegin = t); else DIAGONAL when M = H: emit '=' or 'X' by sub,
+ *                            go to (i-1, t-1); else UP when F = H: state F at the same cell; else state E at the same cell;
+ *                   state F at (i, t): emit 'I'; go to (i-1, t), in state H when H(i-1, t) - o - e >= F(i-1, t) - e (the gap was
+ *                            opened there), else in state F;
+ *                   state E at (i, t): emit 'D'; go to (i, t-1), in state H when H(i, t-1) - o - e >= E(i, t-1) - e, else in
+ *                            state E.
+ *                 readEnd and textEnd are the end cell's i and t;
+ *     script      from the read's first character: readBegin << 4 | 4 ('S') when readBegin > 0; the merged runs of '=', 'X', 'I',
+ *                 'D' as in chain alignment; (n - readEnd) << 4 | 4 when readEnd < n.  numOps counts all of them; maxOps,
+ *                 numTruncated and the unspecified row of a truncated read are chain alignment's.  editDistance is the number
+ *                 of X, I and D characters.
+ *   INVARIANTS: the runs' read lengths sum to n; their text lengths to textEnd - textBegin; the script re-scored with the four
+ *   costs (match per '=', - mismatch per 'X', - o - g e per run of g 'I' or 'D') equals score; the script neither begins nor
+ *   ends with 'I', 'D' or 'X' next to a clip or a read end (a first operation that is not '=' would start from H = 0 at no
+ *   gain, and a last one would leave an earlier cell with at least the score); 0 <= textBegin <= textEnd <= L whatever the
+ *   band does.  The score never exceeds the unbanded local score and equals it when an optimal unbanded path lies inside
+ *   [lo, hi].
+ *   Only ALIGNED reads load text, every load of text or read is an aligned dword that holds a byte the slot owns, and the record
+ *   is checked against the text's length before anything is read.
+ *
+ * awfmAlignChainsAffine (csrc/awfm_align_affine.c): on the host over `threads` threads of the pool, a read at a time, the
+ * recurrence as written with three rows of at most 64 cells and a trace byte per cell in an n x width table, then the walk.
+ * awfmGpuAlignChainsAffine (csrc/awfm_align_affine_kernel.h): the same on device arrays with the image's text, record table and
+ * alphabet; one launch, asynchronous on `stream`, no host wait, no allocation; a group of G lanes per read as in chain
+ * alignment, E of a row by one max-prefix-scan over the group, five trace bits per cell in dScratch:
+ * awfmGpuAlignChainsAffineScratchBytes(g, maxRows) bytes, 16-byte aligned, of this call's own until it has finished -- two
+ * streams may run the call at once with a dScratch each.  $AWFM_GPU_DIAG affine_group=32|64 forces a larger G than the band
+ * needs (tests; the result does not depend on it). */
+#define AWFM_ALIGN_OP_S 4u /* the soft clip among the operations, BAM numbering */
+struct AwFmAlignScoring {
+  uint32_t match, mismatch, gapOpen, gapExtend;
+};
+struct AwFmAffineOutputs {
+  uint32_t *scores;        /* [numReads]  a score (0: nothing aligned) or one of the four status values */
+  uint32_t *editDistances; /* [numReads]  X + I + D characters of the script */
+  uint32_t *readBegins;    /* [numReads]  the aligned part of the read: [readBegin, readEnd) */
+  uint32_t *readEnds;      /* [numReads] */
+  uint64_t *textBegins;    /* [numReads]  sequence-local, of the slot's sequence */
+  uint64_t *textEnds;      /* [numReads] */
+  uint32_t *numOps;        /* [numReads]  the true number of runs, also when it exceeds maxOps */
+  uint32_t *ops;           /* [numReads * maxOps]  run << 4 | op: I = 1, D = 2, S = 4, '=' = 7, X = 8 */
+  uint64_t *numUnaligned;  /* one counter, added to: MALFORMED, TOO_WIDE, TOO_LONG */
+  uint64_t *numTruncated;  /* one counter, added to: aligned reads with numOps > maxOps */
+};
+enum AwFmReturnCode awfmAlignChainsAffine(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
+                                          uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                          const struct AwFmAlignScoring *scoring, uint32_t maxOps, const uint8_t *text, uint64_t length,
+                                          const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
+                                          const struct AwFmAffineOutputs *out, unsigned threads);
+uint64_t awfmGpuAlignChainsAffineScratchBytes(const AwFmGpuIndex *g, uint32_t maxRows);
+enum AwFmReturnCode awfmGpuAlignChainsAffine(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, const uint32_t *dSlots, uint64_t numReads,
+                                             uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                             const struct AwFmAlignScoring *scoring, uint32_t maxOps, uint32_t maxRows,
+                                             const struct AwFmAffineOutputs *dOut, void *dScratch, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
