@@ -46,6 +46,7 @@ GPU_SYMBOLS = [
     "awfmGpuIndexSetText", "awfmGpuIndexTextLength", "awfmTextWindows", "awfmGpuTextWindows", "awfmVerifyChains", "awfmGpuVerifyChains",
     "awfmAlignChains", "awfmGpuAlignChainsScratchBytes", "awfmGpuAlignChains",
     "awfmAlignChainsAffine", "awfmGpuAlignChainsAffineScratchBytes", "awfmGpuAlignChainsAffine",
+    "awfmScoreChainsAffine", "awfmGpuScoreChainsAffine",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -122,6 +123,13 @@ class AwFmAffineOutputs(C.Structure):
     _fields_ = [("scores", C.c_void_p), ("editDistances", C.c_void_p), ("readBegins", C.c_void_p), ("readEnds", C.c_void_p),
                 ("textBegins", C.c_void_p), ("textEnds", C.c_void_p), ("numOps", C.c_void_p), ("ops", C.c_void_p),
                 ("numUnaligned", C.c_void_p), ("numTruncated", C.c_void_p)]
+
+
+class AwFmSlotScoreOutputs(C.Structure):
+    """struct AwFmSlotScoreOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("slotScores", C.c_void_p), ("slotReadEnds", C.c_void_p), ("slotTextEnds", C.c_void_p), ("bestSlots", C.c_void_p),
+                ("bestScores", C.c_void_p), ("secondSlots", C.c_void_p), ("secondScores", C.c_void_p), ("mappingQualities", C.c_void_p),
+                ("numUnscored", C.c_void_p), ("numMapped", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -294,6 +302,10 @@ def lib():
         "awfmGpuAlignChainsAffineScratchBytes": (u64, [vp, C.c_uint32]),
         "awfmGpuAlignChainsAffine": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmAffineOutputs), vp, vp]),
+        "awfmScoreChainsAffine": (C.c_int, [C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmAlignScoring),
+                                            C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmSlotScoreOutputs), C.c_uint]),
+        "awfmGpuScoreChainsAffine": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmSlotScoreOutputs), vp]),
         "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),
         "awfmGpuIndexNumRecords": (C.c_uint32, [vp]),
         "awfmGpuLocalPositions": (C.c_int, [vp, vp, u64, vp, vp, vp, vp, vp]),

@@ -658,6 +658,70 @@ def align_chains_affine_host(read_chars, read_offsets, slots, chosen, text, sequ
     return result
 
 
+SCORE_MAX_MAPQ = 254  # AWFM_SCORE_MAX_MAPQ: upper limit of mapq_cap (255 is SAM's "unavailable")
+SCORE_SLOT_OUTPUTS = (("slotScores", np.uint32), ("slotReadEnds", np.uint32), ("slotTextEnds", np.uint64))
+SCORE_READ_OUTPUTS = (("bestSlots", np.uint32), ("bestScores", np.uint32), ("secondSlots", np.uint32), ("secondScores", np.uint32),
+                      ("mappingQualities", np.uint8))
+
+
+def slot_score_outputs(**addresses):
+    """struct AwFmSlotScoreOutputs from addresses by field name (slotScores, slotReadEnds, slotTextEnds, bestSlots, bestScores,
+    secondSlots, secondScores, mappingQualities, numUnscored, numMapped); a field left out is NULL"""
+    out = _lib.AwFmSlotScoreOutputs()
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmSlotScoreOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def score_chains_affine_host(read_chars, read_offsets, slots, text, sequence_ends=None, alphabet=AwFmAlphabetDna, band_pad=8, max_drift=15,
+                             scoring=AFFINE_SCORING, min_score=0, mapq_cap=60, threads=4, outputs=None, num_read_chars=None, fill=None,
+                             unscored_before=0, mapped_before=0):
+    """awfmScoreChainsAffine (include/awfm_gpu.h, "slot scores and mapping quality"): the inputs of verify_chains_host and `scoring`
+    = (match, mismatch, gap_open, gap_extend) -> a dict of slotScores, slotReadEnds, slotTextEnds shaped like the slots, bestSlots,
+    bestScores, secondSlots, secondScores, mappingQualities per read, numUnscored and numMapped (ints: the values before plus this
+    call's).  outputs: the names to compute (None: all); the others are passed as NULL and left out.  fill: the value (per byte)
+    the arrays hold before the call."""
+    chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
+    t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    ends = None if sequence_ends is None else np.ascontiguousarray(sequence_ends, dtype=np.uint64)
+    n = max(o.size - 1, 0)
+    arrays = {name: np.ascontiguousarray(slots[name], dtype=dtype) for name, dtype in VERIFY_SLOT_INPUTS}
+    shape = arrays["sequences"].shape
+    if len(shape) != 2 or shape[0] != n or any(a.shape != shape for a in arrays.values()):
+        raise ValueError("the slot arrays are shaped (reads, max_candidates)")
+    names = [name for name, _ in SCORE_SLOT_OUTPUTS + SCORE_READ_OUTPUTS] + ["numUnscored", "numMapped"]
+    outputs = names if outputs is None else list(outputs)
+    result = {name: np.zeros(shape, dtype) for name, dtype in SCORE_SLOT_OUTPUTS if name in outputs}
+    result.update({name: np.zeros(n, dtype) for name, dtype in SCORE_READ_OUTPUTS if name in outputs})
+    for a in result.values():
+        if fill is not None:
+            a.view(np.uint8)[...] = fill
+    counters = {"numUnscored": np.array([unscored_before], np.uint64), "numMapped": np.array([mapped_before], np.uint64)}
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else dummy.ctypes.data
+
+    vin = verify_inputs(address(chars), chars.size if num_read_chars is None else num_read_chars, address(o),
+                        **{name: address(a) for name, a in arrays.items()})
+    sout = slot_score_outputs(**{name: address(a) for name, a in result.items()})
+    for name, counter in counters.items():
+        if name in outputs:
+            setattr(sout, name, counter.ctypes.data)
+    costs = scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+    rc = _lib.lib().awfmScoreChainsAffine(C.byref(vin), n, shape[1], band_pad, max_drift, C.byref(costs), min_score, mapq_cap, address(t), t.size,
+                                          None if ends is None or not ends.size else ends.ctypes.data, 0 if ends is None else ends.size,
+                                          alphabet, C.byref(sout), threads)
+    _check("awfmScoreChainsAffine", rc)
+    for name, counter in counters.items():
+        if name in outputs:
+            result[name] = int(counter[0])
+    return result
+
+
 AWFM_EDIT_NONE = 0xFFFFFFFF  # the edit of a record of the unedited query (include/awfm_gpu.h)
 
 
@@ -905,6 +969,19 @@ class GpuIndex:
                _lib.lib().awfmGpuAlignChainsAffine(self.handle, C.byref(inputs), d_slots or None, num_reads, max_candidates, band_pad, max_drift,
                                                    None if costs is None else C.byref(costs), max_ops, max_rows, C.byref(outputs),
                                                    d_scratch or None, stream or None))
+
+    # slot scores and mapping quality (include/awfm_gpu.h) -----------------
+    def score_chains_affine(self, inputs, num_reads, outputs, max_candidates=4, band_pad=8, max_drift=15, scoring=AFFINE_SCORING,
+                            min_score=0, mapq_cap=60, stream=0):
+        """awfmGpuScoreChainsAffine: inputs verify_inputs(...) and outputs slot_score_outputs(...) of device addresses, scoring (match,
+        mismatch, gap_open, gap_extend) or an align_scoring(...); the affine score and end cell of every slot, per read the best
+        slot (what align_chains_affine takes as d_slots), the second and the mapping quality; one launch, no scratch,
+        asynchronous on `stream`; *numUnscored and *numMapped are added to"""
+        costs = None if scoring is None else scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+        _check("awfmGpuScoreChainsAffine",
+               _lib.lib().awfmGpuScoreChainsAffine(self.handle, C.byref(inputs), num_reads, max_candidates, band_pad, max_drift,
+                                                   None if costs is None else C.byref(costs), min_score, mapq_cap, C.byref(outputs),
+                                                   stream or None))
 
     def locate_host_local(self, chars, offsets=None, fixed_length=0):
         """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],

@@ -1,0 +1,243 @@
+/*
+ * awfm_score_affine_kernel.h -- scoreChainsAffineKernel<G>, the kernel of "slot scores and mapping quality" (include/awfm_gpu.h):
+ * the banded local affine score and end cell of every slot of every read, and per read the best slot, the runner-up and the
+ * mapping quality.  The definition is the header's; the host twin and checker is awfm_score_affine.c.
+ *
+ * The layout is verifyChainsKernel<G>'s (awfm_verify_kernel.h): a wave takes a read (persistent grid over reads), its 64 / G
+ * groups of G lanes take the read's slots in turn, lane k of a group is diagonal lo + k of the band in sequence-local
+ * coordinates.  The rows go in chunks of kVerifyChunk whose read characters and text characters the group stages into its own
+ * words of LDS through stageBytes -- EVERY LOAD OF TEXT OR READ is an aligned dword that holds a byte the slot owns, and the
+ * record is checked against the text's length before anything is read; a slot with a status or without an existing cell loads
+ * no text.  The row is alignChainsAffineKernel's (awfm_align_affine_kernel.h) without its trace: a lane carries H and F of the
+ * previous row, M comes from the lane itself, F from lane k + 1, and E is one exclusive max-prefix-scan per row over the group,
+ * E[k] = max over k' < k of (H~[k'] + k' e) - o - k e with H~ = max(0, M, F) (a gap that extends from a cell whose H
+ * came from E pays o twice and is dominated).  No ballot, no store and no other shuffle per row.  Lanes and rows without a cell
+ * carry kScoreNeg.  The end cell -- largest H, then smallest i, then smallest k -- is each lane's own best (strict-greater
+ * update) and one butterfly over the group.
+ *
+ * THE READ'S RULES.  Lane 0 of a group leaves the slot's value, readEnd, textEnd and sequence in the wave's kScoreSlotWords words
+ * of LDS; behind a wave barrier lane j < C holds slot j, stores the three per-slot outputs (one coalesced store each) and
+ * enters the keyed maxima over the wave's first sixteen lanes: score << 4 | 15 - slot among the slots that count gives the best
+ * slot with ties to the lowest, the same among those that are neither the best nor its duplicate gives the second.  Lane 0
+ * stores the per-read outputs.  Counters take one atomic per wave.  Vector loads and stores only.
+ */
+#ifndef AWFM_SCORE_AFFINE_KERNEL_H
+#define AWFM_SCORE_AFFINE_KERNEL_H
+
+#include "awfm_verify_kernel.h"
+
+namespace {
+
+constexpr unsigned kScoreThreads = 256;    /* per workgroup: four waves, each with reads of its own */
+constexpr unsigned kScoreSlotWords = 80;   /* per wave: value, readEnd, the two halves of textEnd and the sequence of sixteen slots */
+constexpr unsigned kScoreLdsBytes = 4640;  /* static LDS at G = 16: 16 x 52 staging words, the letter table, four waves' slot words */
+constexpr unsigned kScoreBlocksPerCU = 7;  /* up to 72 VGPRs: seven waves per SIMD, i.e. seven workgroups of four waves per CU */
+static_assert(kScoreSlotWords == 5u * AWFM_CANDIDATES_MAX_SLOTS, "five words a slot");
+static_assert(kScoreLdsBytes == (kScoreThreads / 16u) * kVerifyGroupWords * 4u + 32u + (kScoreThreads / 64u) * kScoreSlotWords * 4u,
+              "the staging words of sixteen groups, the letter table and the slot words of four waves");
+constexpr int kScoreNeg = -0x40000000; /* minus infinity: a lane resets it every row, so it only has to survive o + 64 e */
+
+struct DevScoreParams {
+  struct AwFmVerifyInputs in;
+  struct AwFmSlotScoreOutputs out;
+  const unsigned char *text;
+  unsigned long long length;
+  const unsigned long long *ends; /* the image's record table; numRecords == 0: one sequence [0, length) */
+  unsigned numRecords;
+  unsigned long long numReads;
+  unsigned slots, pad, drift, amino, floor, cap; /* floor: max(minScore, 1) */
+  int match, mismatch, open, extend;             /* open: what the first character of a gap costs, o + e */
+};
+
+/* the launch's parameters where the launch left them, in the kernel's argument segment: a field is loaded where it is used
+ * instead of living in a register from the kernel's first instruction to its last */
+typedef const __attribute__((address_space(4))) DevScoreParams *ScoreParamsRef;
+
+/* the value of slot `at` of read r (header: UNUSED .. TOO LONG, else the score) with its end cell; every lane of the group
+ * returns the same */
+template <int G>
+__device__ __forceinline__ unsigned scoreSlot(const ScoreParamsRef p, const unsigned long long at, const unsigned s,
+                                              const unsigned long long readBegin, const unsigned long long n64, const bool readOk,
+                                              unsigned *sRead, unsigned *sText, const unsigned char *sAmino, const unsigned k,
+                                              unsigned &endRead, unsigned long long &endText) {
+  endRead = 0u;
+  endText = 0ull;
+  if (s == AWFM_CANDIDATES_NONE || p->in.chainAnchors[at] == 0u) return AWFM_VERIFY_NONE;
+  if (!readOk) return AWFM_VERIFY_MALFORMED;
+  const unsigned long long rb = p->in.chainReadBegins[at], re = p->in.chainReadEnds[at];
+  if (rb > re || re > n64) return AWFM_VERIFY_MALFORMED;
+  if (s >= (p->numRecords ? p->numRecords : 1u)) return AWFM_VERIFY_MALFORMED;
+  const unsigned long long S = p->numRecords && s ? p->ends[s - 1u] + 1ull : 0ull, E = p->numRecords ? p->ends[s] : p->length;
+  if (E < S || E > p->length) return AWFM_VERIFY_MALFORMED;
+  const long long bD = p->in.chainBeginDiagonals[at], eD = p->in.chainEndDiagonals[at];
+  /* E - S < 2^62 and rb, re < 2^32: a diagonal outside [-2^33, 2^62] makes tb < 0, tb > te or te > E - S whatever the other is,
+   * and inside it the sums are exact in 64 bits */
+  if (bD < -(1ll << 33) || eD < -(1ll << 33) || bD > (1ll << 62) || eD > (1ll << 62)) return AWFM_VERIFY_MALFORMED;
+  const long long tb = (long long)rb + bD, te = (long long)re + eD, L = (long long)(E - S);
+  if (tb < 0 || tb > te || te > L) return AWFM_VERIFY_MALFORMED;
+  const long long delta = eD - bD;
+  if (delta > (long long)p->drift || delta < -(long long)p->drift) return AWFM_VERIFY_TOO_WIDE;
+  if (n64 > (unsigned long long)AWFM_ALIGN_MAX_LENGTH) return AWFM_VERIFY_TOO_LONG;
+  const int n = (int)n64; /* <= 2^16 */
+  const long long lo = (bD < eD ? bD : eD) - (long long)p->pad, hi = (bD > eD ? bD : eD) + (long long)p->pad;
+  if (n == 0 || (long long)n + hi < 0 || lo + 1 > L) return 0u; /* no existing cell with i >= 1: nothing is aligned, nothing is read */
+  /* columns counted from lo: lane k's cell of row i is u = i + k, t = lo + u; it exists for uMin <= u <= uMax inside the band.
+   * Here -n - 63 <= lo <= L - 1, so uMin <= n + 63 and uMax >= 1; what lies beyond 2^30 is beyond every row */
+  const int width = (int)(hi - lo) + 1;
+  const int uMin = lo < 0 ? (int)-lo : 0, uMax = L - lo < (1ll << 30) ? (int)(L - lo) : 1 << 30;
+  const int uOne = lo < 1 ? (int)(1 - lo) : 0; /* t >= 1 from here on: the cell has a diagonal predecessor */
+  const bool inBand = (int)k < width;
+  const unsigned char *R = p->in.readChars + readBegin, *T = p->text + S;
+  const unsigned char *sReadBytes = (const unsigned char *)sRead, *sTextBytes = (const unsigned char *)sText;
+  const unsigned proper = p->amino ? 20u : 4u;
+  const int kExtend = (int)k * p->extend;
+  int prevH = inBand && (int)k >= uMin && (int)k <= uMax ? 0 : kScoreNeg, prevF = kScoreNeg; /* row 0: H(0, t) = 0 */
+  int bestH = 0, bestI = 0;
+  for (int i0 = 0; i0 < n; i0 += (int)kVerifyChunk) {
+    const int rows = n - i0 < (int)kVerifyChunk ? n - i0 : (int)kVerifyChunk;
+    /* the text characters T[t - 1] of the chunk's rows i0 + 1 .. i0 + rows: u - 1 = i0 .. i0 + rows + width - 2, cut to the record */
+    const int uFrom = i0 > uMin ? i0 : uMin, uTo = i0 + rows + width - 1 < uMax ? i0 + rows + width - 1 : uMax;
+    __builtin_amdgcn_wave_barrier(); /* (the rows of the chunk before have read their bytes) */
+    const unsigned rOff = stageBytes<G>(R, (unsigned long long)i0, (unsigned long long)(i0 + rows), sRead, k);
+    const unsigned tOff = uTo > uFrom ? stageBytes<G>(T, (unsigned long long)(lo + uFrom), (unsigned long long)(lo + uTo), sText, k) : 0u;
+    __builtin_amdgcn_wave_barrier();
+    for (int q = 0; q < rows; q++) {
+      const int u = i0 + q + 1 + (int)k;
+      const bool inMatrix = inBand && u >= uMin && u <= uMax;
+      const unsigned rLetter = verifyLetter(sAmino, p->amino, sReadBytes[rOff + (unsigned)q]);
+      unsigned tLetter = 0xFFu;
+      if (inMatrix && u >= uOne) tLetter = verifyLetter(sAmino, p->amino, sTextBytes[tOff + (unsigned)(u - 1 - uFrom)]);
+      const bool sub = !(rLetter == tLetter && rLetter < proper);
+      int upH = __shfl_down(prevH, 1, G), upF = __shfl_down(prevF, 1, G);
+      upH = k == (unsigned)(G - 1) ? kScoreNeg : upH;
+      upF = k == (unsigned)(G - 1) ? kScoreNeg : upF;
+      const int M = prevH + (sub ? -p->mismatch : p->match); /* (prevH is kScoreNeg when t = 0) */
+      const int fOpens = upH - p->open, fExtends = upF - p->extend;
+      const int F = fOpens > fExtends ? fOpens : fExtends;
+      int tilde = M > F ? M : F;
+      tilde = tilde > 0 ? tilde : 0;
+      tilde = inMatrix ? tilde : kScoreNeg;
+      /* E[k] + o + k e = max over k' < k of H~[k'] + k' e: shifted by a lane, then the inclusive scan */
+      int v = __shfl_up(tilde + kExtend, 1, G);
+      v = k == 0u ? kScoreNeg : v;
+#pragma unroll
+      for (int step = 1; step < G; step <<= 1) {
+        const int other = __shfl_up(v, step, G);
+        v = (int)k >= step && other > v ? other : v;
+      }
+      const int e = v - (p->open - p->extend) - kExtend;
+      const int h = inMatrix ? (tilde > e ? tilde : e) : kScoreNeg;
+      if (h > bestH) { /* (strictly: the smallest i of the lane's largest H) */
+        bestH = h;
+        bestI = i0 + q + 1;
+      }
+      prevH = h;
+      prevF = inMatrix ? F : kScoreNeg;
+    }
+  }
+  /* the end cell: the largest H, then the smallest i, then the smallest k.  H < 2^24, i <= 2^16 */
+  unsigned long long key = ((unsigned long long)(unsigned)bestH << 32) | ((unsigned long long)(0x1FFFFu - (unsigned)bestI) << 6) | (63u - k);
+#pragma unroll
+  for (int step = 1; step < G; step <<= 1) {
+    const unsigned otherLow = (unsigned)__shfl_xor((int)(unsigned)key, step, G), otherHigh = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), step, G);
+    const unsigned long long other = ((unsigned long long)otherHigh << 32) | otherLow;
+    key = other > key ? other : key;
+  }
+  const unsigned score = (unsigned)(key >> 32);
+  if (score == 0u) return 0u;
+  const unsigned i = 0x1FFFFu - ((unsigned)(key >> 6) & 0x1FFFFu), at2 = 63u - ((unsigned)key & 63u);
+  endRead = i;
+  endText = (unsigned long long)(lo + (long long)i + (long long)at2);
+  return score;
+}
+
+/* the largest key of the wave's first sixteen lanes, in each of them */
+__device__ __forceinline__ unsigned scoreMaxOfSixteen(unsigned key) {
+#pragma unroll
+  for (int step = 1; step < 16; step <<= 1) {
+    const unsigned other = (unsigned)__shfl_xor((int)key, step, 16);
+    key = other > key ? other : key;
+  }
+  return key;
+}
+
+template <int G>
+__global__ void __launch_bounds__(kScoreThreads) scoreChainsAffineKernel(const DevScoreParams args) {
+  constexpr unsigned kGroupsPerWave = 64u / (unsigned)G;
+  /* thirty-odd parameters, the nested loops' masks and a slot's own values are more scalar registers than a wave has, and pinned
+   * into vector registers they cost a wave its occupancy: the parameters stay in the argument segment (the struct is the
+   * kernel's only argument, so it begins the segment) and every trip of the read loop takes the address anew, so that what a
+   * field's load yields lives no longer than the trip needs it */
+  (void)args;
+  ScoreParamsRef p = (ScoreParamsRef)__builtin_amdgcn_kernarg_segment_ptr();
+  __shared__ unsigned sStage[kScoreThreads / (unsigned)G][kVerifyGroupWords];
+  __shared__ unsigned sSlots[kScoreThreads / 64u][kScoreSlotWords];
+  __shared__ unsigned char sAmino[32];
+  if (threadIdx.x < 32u) sAmino[threadIdx.x] = kAminoTables.letterOfAscii[threadIdx.x];
+  __syncthreads();
+  const unsigned lane = threadIdx.x & 63u, k = lane % (unsigned)G, groupInWave = lane / (unsigned)G;
+  unsigned *sRead = sStage[threadIdx.x / (unsigned)G], *sText = sRead + kVerifyReadWords;
+  unsigned *sValue = sSlots[threadIdx.x / 64u], *sEndRead = sValue + 16, *sEndLow = sValue + 32, *sEndHigh = sValue + 48, *sSequence = sValue + 64;
+  const unsigned long long numWaves = (unsigned long long)gridDim.x * (kScoreThreads / 64u);
+  const unsigned long long numReads = p->numReads;
+  unsigned unscored = 0, mapped = 0;
+  for (unsigned long long r = (unsigned long long)blockIdx.x * (kScoreThreads / 64u) + threadIdx.x / 64u; r < numReads; r += numWaves) {
+    asm volatile("" : "+s"(p));
+    const unsigned long long readBegin = p->in.readOffsets[r], readEnd = p->in.readOffsets[r + 1ull];
+    const bool readOk = readBegin <= readEnd && readEnd <= p->in.numReadChars;
+    __builtin_amdgcn_wave_barrier(); /* (the read before has read its slot words) */
+    for (unsigned j = groupInWave; j < p->slots; j += kGroupsPerWave) {
+      const unsigned long long at = r * p->slots + j;
+      const unsigned s = p->in.sequences[at];
+      unsigned endRead;
+      unsigned long long endText;
+      const unsigned value = scoreSlot<G>(p, at, s, readBegin, readEnd - readBegin, readOk, sRead, sText, sAmino, k, endRead, endText);
+      if (k == 0u) {
+        sValue[j] = value;
+        sEndRead[j] = endRead;
+        sEndLow[j] = (unsigned)endText;
+        sEndHigh[j] = (unsigned)(endText >> 32);
+        sSequence[j] = s;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    /* lane j holds slot j */
+    const bool holds = lane < p->slots;
+    const unsigned mine = lane & 15u;
+    const unsigned value = holds ? sValue[mine] : AWFM_VERIFY_NONE, endRead = holds ? sEndRead[mine] : 0u;
+    const unsigned endLow = holds ? sEndLow[mine] : 0u, endHigh = holds ? sEndHigh[mine] : 0u, sequence = holds ? sSequence[mine] : 0u;
+    if (holds) {
+      const unsigned long long at = r * p->slots + lane;
+      if (p->out.slotScores) p->out.slotScores[at] = value;
+      if (p->out.slotReadEnds) p->out.slotReadEnds[at] = endRead;
+      if (p->out.slotTextEnds) p->out.slotTextEnds[at] = ((unsigned long long)endHigh << 32) | endLow;
+    }
+    unscored += holds && value >= AWFM_VERIFY_TOO_LONG && value != AWFM_VERIFY_NONE ? 1u : 0u;
+    /* a score is below 2^24: score << 4 | 15 - slot orders by score, then by the lowest slot; 0 is "none" */
+    const bool counts = holds && value < AWFM_VERIFY_TOO_LONG && value >= p->floor;
+    const unsigned key = counts ? (value << 4) | (15u - mine) : 0u;
+    const unsigned bestKey = scoreMaxOfSixteen(key);
+    const unsigned best = 15u - (bestKey & 15u); /* (slot 15 when there is none: its words are read and not used) */
+    const bool duplicate = sequence == sSequence[best] && endRead == sEndRead[best] && endLow == sEndLow[best] && endHigh == sEndHigh[best];
+    const unsigned secondKey = scoreMaxOfSixteen(counts && mine != best && !duplicate ? key : 0u);
+    if (lane == 0u) {
+      const unsigned bestScore = bestKey >> 4, secondScore = secondKey >> 4;
+      mapped += bestKey ? 1u : 0u;
+      if (p->out.bestSlots) p->out.bestSlots[r] = bestKey ? best : AWFM_CHAINS_NO_SLOT;
+      if (p->out.bestScores) p->out.bestScores[r] = bestScore;
+      if (p->out.secondSlots) p->out.secondSlots[r] = secondKey ? 15u - (secondKey & 15u) : AWFM_CHAINS_NO_SLOT;
+      if (p->out.secondScores) p->out.secondScores[r] = secondScore;
+      /* exact in 32 bits: best < 2^24 and cap <= 254 */
+      if (p->out.mappingQualities) p->out.mappingQualities[r] = (unsigned char)(bestKey ? p->cap * (bestScore - secondScore) / bestScore : 0u);
+    }
+  }
+  /* one atomic per wave and counter that met any */
+#pragma unroll
+  for (int offset = 32; offset > 0; offset >>= 1) unscored += (unsigned)__shfl_xor((int)unscored, offset, 64);
+  if (lane == 0u && unscored && p->out.numUnscored) atomicAdd((unsigned long long *)p->out.numUnscored, (unsigned long long)unscored);
+  if (lane == 0u && mapped && p->out.numMapped) atomicAdd((unsigned long long *)p->out.numMapped, (unsigned long long)mapped);
+}
+
+}  // namespace
+
+#endif

@@ -86,6 +86,7 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *                       value than the band needs is ignored); the default is the smallest that holds the band
  *   align_group=16|32|64    awfmGpuAlignChains: lanes per read, in the same way
  *   affine_group=32|64      awfmGpuAlignChainsAffine: lanes per read, in the same way
+ *   score_group=32|64       awfmGpuScoreChainsAffine: lanes per slot, in the same way
  *   second_window=0|1   the lookup kernel's second table window (a survivor's leftmost characters): 0 never, 1 on every trip;
  *                       unset, the kernel's own gate decides trip by trip (the results are the same either way)
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
@@ -807,6 +808,66 @@ enum AwFmReturnCode awfmGpuAlignChainsAffine(AwFmGpuIndex *g, const struct AwFmV
                                              uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
                                              const struct AwFmAlignScoring *scoring, uint32_t maxOps, uint32_t maxRows,
                                              const struct AwFmAffineOutputs *dOut, void *dScratch, void *stream);
+
+/* ---- slot scores and mapping quality: the affine score of EVERY slot, the best one, the runner-up and how far to trust it ----
+ * The stage BETWEEN chains and affine alignment, for callers that report a mapping quality: the banded local affine score and
+ * end cell of every slot of every read -- score only, no trace, no script --, and per read the best slot, the second and a
+ * mapping quality.  bestSlots goes straight into awfmGpuAlignChainsAffine as its slots, which then produces the script of the
+ * slot that wins under the scoring the caller reports (awfmGpuVerifyChains ranks by a unit-cost distance over the chain's own
+ * interval, another objective); secondary alignments are a second call with secondSlots.  Inputs, C = maxCandidates, bandPad
+ * w, maxDrift x, scoring, text, record table and alphabet are affine alignment's, as are the scoring ranges, the band rule, the
+ * limits of C and numReads, the NULL rules, "every output may be NULL", "counters are added to" and "numReads == 0 touches
+ * nothing".  One definition on both sides, the host twin (csrc/awfm_score_affine.c) being the definition and the checker.
+ *
+ * PER SLOT (r, j): slotScores, slotReadEnds, slotTextEnds [r * C + j] are EXACTLY what awfmAlignChainsAffine puts into scores[r],
+ * readEnds[r] and textEnds[r] when slots[r] = j: the same order UNUSED, MALFORMED, TOO WIDE, TOO LONG, the same cells, the same
+ * three-value recurrence, the same end cell (the largest H over existing cells with i >= 1, then the smallest i, then the
+ * smallest t), and "score 0 means nothing aligned, and nothing is read" (then both ends are 0, as with a status).  One
+ * difference: there is no trace, hence no maxRows: TOO LONG is n > AWFM_ALIGN_MAX_LENGTH on BOTH sides, the affine host twin's
+ * rule.  The tests hold the two calls to this equivalence.
+ *
+ * PER READ, over its C slots:
+ *   1. a slot COUNTS when it has a score (not a status) that is >= max(minScore, 1); minScore may be any value;
+ *   2. the BEST slot is the counting slot with the largest score, ties to the lowest slot; without one bestSlots[r] =
+ *      AWFM_CHAINS_NO_SLOT and bestScores[r] = 0;
+ *   3. a counting slot other than the best is a DUPLICATE when it names the best slot's sequence and has the best slot's
+ *      (readEnd, textEnd): the same alignment reached through two clusters whose bands overlap, not a competitor;
+ *   4. the SECOND slot is the largest-scoring counting slot that is neither the best nor a duplicate, ties to the lowest slot;
+ *      without one secondSlots[r] = AWFM_CHAINS_NO_SLOT and secondScores[r] = 0;
+ *   5. mappingQualities[r] = 0 without a best slot, else floor(mapqCap * (best - second) / best) with second = 0 when there is
+ *      none: exact in unsigned 32 bits, since best < 2^24 and mapqCap <= AWFM_SCORE_MAX_MAPQ = 254 (255 is SAM's "unavailable":
+ *      AwFmIllegalPositionError).
+ * This rule is the library's OWN, not BWA's and not minimap2's; nothing on the path is floating-point.  A caller with another
+ * rule takes bestScores and secondScores.  Duplicates are told by their end cell only; mates are not paired.
+ * *numUnscored: the slots that got MALFORMED, TOO_WIDE or TOO_LONG; *numMapped: the reads with a best slot.
+ *
+ * awfmScoreChainsAffine (csrc/awfm_score_affine.c): on the host over `threads` threads of the pool, a read at a time, three rows
+ * of at most 64 cells, the recurrence as written, then the rules above over the read's C results.  awfmGpuScoreChainsAffine
+ * (csrc/awfm_score_affine_kernel.h): the same on device arrays with the image's text, record table and alphabet
+ * (AwFmUnsupportedVersionError without a text); ONE launch, asynchronous on `stream`, no host wait, no allocation, no scratch:
+ * two streams may run it on one image at once.  A wave per read, a group of G lanes (16, 32 or 64: the smallest that holds the
+ * band) per slot, a lane per diagonal, a row per step; E of a row by one max-prefix-scan over the group.  $AWFM_GPU_DIAG
+ * score_group=32|64 forces a larger G than the band needs (tests; the result does not depend on it). */
+#define AWFM_SCORE_MAX_MAPQ 254u
+struct AwFmSlotScoreOutputs {
+  uint32_t *slotScores;       /* [numReads * C]  a score (0: nothing aligned) or one of the four status values */
+  uint32_t *slotReadEnds;     /* [numReads * C]  the end cell's i; 0 with a status or score 0 */
+  uint64_t *slotTextEnds;     /* [numReads * C]  the end cell's t, sequence-local; 0 likewise */
+  uint32_t *bestSlots;        /* [numReads]  AWFM_CHAINS_NO_SLOT when no slot counts */
+  uint32_t *bestScores;       /* [numReads]  0 when none */
+  uint32_t *secondSlots;      /* [numReads]  AWFM_CHAINS_NO_SLOT when none */
+  uint32_t *secondScores;     /* [numReads]  0 when none */
+  uint8_t *mappingQualities;  /* [numReads] */
+  uint64_t *numUnscored;      /* one counter, added to: slots that got MALFORMED, TOO_WIDE or TOO_LONG */
+  uint64_t *numMapped;        /* one counter, added to: reads with a best slot */
+};
+enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
+                                          uint32_t maxDrift, const struct AwFmAlignScoring *scoring, uint32_t minScore, uint32_t mapqCap,
+                                          const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
+                                          enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads);
+enum AwFmReturnCode awfmGpuScoreChainsAffine(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
+                                             uint32_t bandPad, uint32_t maxDrift, const struct AwFmAlignScoring *scoring, uint32_t minScore,
+                                             uint32_t mapqCap, const struct AwFmSlotScoreOutputs *dOut, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
