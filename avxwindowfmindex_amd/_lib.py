@@ -47,6 +47,7 @@ GPU_SYMBOLS = [
     "awfmAlignChains", "awfmGpuAlignChainsScratchBytes", "awfmGpuAlignChains",
     "awfmAlignChainsAffine", "awfmGpuAlignChainsAffineScratchBytes", "awfmGpuAlignChainsAffine",
     "awfmScoreChainsAffine", "awfmGpuScoreChainsAffine",
+    "awfmScoreWindowsAffine", "awfmGpuScoreWindowsAffineScratchBytes", "awfmGpuScoreWindowsAffine",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -130,6 +131,20 @@ class AwFmSlotScoreOutputs(C.Structure):
     _fields_ = [("slotScores", C.c_void_p), ("slotReadEnds", C.c_void_p), ("slotTextEnds", C.c_void_p), ("bestSlots", C.c_void_p),
                 ("bestScores", C.c_void_p), ("secondSlots", C.c_void_p), ("secondScores", C.c_void_p), ("mappingQualities", C.c_void_p),
                 ("numUnscored", C.c_void_p), ("numMapped", C.c_void_p)]
+
+
+class AwFmWindowInputs(C.Structure):
+    """struct AwFmWindowInputs (include/awfm_gpu.h): host or device addresses"""
+    _fields_ = [("readChars", C.c_void_p), ("numReadChars", C.c_uint64), ("readOffsets", C.c_void_p), ("windowSequences", C.c_void_p),
+                ("windowBegins", C.c_void_p), ("windowEnds", C.c_void_p)]
+
+
+class AwFmWindowOutputs(C.Structure):
+    """struct AwFmWindowOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("scores", C.c_void_p), ("readBegins", C.c_void_p), ("readEnds", C.c_void_p), ("textBegins", C.c_void_p),
+                ("textEnds", C.c_void_p), ("sequences", C.c_void_p), ("chainAnchors", C.c_void_p), ("chainReadBegins", C.c_void_p),
+                ("chainReadEnds", C.c_void_p), ("chainBeginDiagonals", C.c_void_p), ("chainEndDiagonals", C.c_void_p),
+                ("numUnscored", C.c_void_p), ("numFound", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -304,6 +319,11 @@ def lib():
                                                C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmAffineOutputs), vp, vp]),
         "awfmScoreChainsAffine": (C.c_int, [C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmAlignScoring),
                                             C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmSlotScoreOutputs), C.c_uint]),
+        "awfmScoreWindowsAffine": (C.c_int, [C.POINTER(AwFmWindowInputs), u64, C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.c_uint32,
+                                             vp, u64, vp, u64, C.c_int, C.POINTER(AwFmWindowOutputs), C.c_uint]),
+        "awfmGpuScoreWindowsAffineScratchBytes": (u64, [vp, C.c_uint32]),
+        "awfmGpuScoreWindowsAffine": (C.c_int, [vp, C.POINTER(AwFmWindowInputs), u64, C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, C.POINTER(AwFmWindowOutputs), vp, vp]),
         "awfmGpuScoreChainsAffine": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmSlotScoreOutputs), vp]),
         "awfmGpuIndexSetRecordTable": (C.c_int, [vp, vp, u64]),

@@ -722,6 +722,86 @@ def score_chains_affine_host(read_chars, read_offsets, slots, text, sequence_end
     return result
 
 
+WINDOW_MAX_WIDTH = 4096   # AWFM_WINDOW_MAX_WIDTH: text characters per window after clipping to the record
+WINDOW_MAX_LENGTH = 4096  # AWFM_WINDOW_MAX_LENGTH: read characters
+WINDOW_READ_OUTPUTS = (("scores", np.uint32), ("readBegins", np.uint32), ("readEnds", np.uint32), ("textBegins", np.uint64),
+                       ("textEnds", np.uint64))
+
+
+def window_inputs(read_chars, num_read_chars, read_offsets, window_sequences, window_begins, window_ends):
+    """struct AwFmWindowInputs from addresses: the read buffer, its size, the read offsets and the three per-read window arrays"""
+    return _lib.AwFmWindowInputs(read_chars or None, num_read_chars, read_offsets or None, window_sequences or None, window_begins or None,
+                                 window_ends or None)
+
+
+def window_score_outputs(**addresses):
+    """struct AwFmWindowOutputs from addresses by field name (scores, readBegins, readEnds, textBegins, textEnds, the six slot arrays
+    sequences, chainAnchors, chainReadBegins, chainReadEnds, chainBeginDiagonals, chainEndDiagonals, numUnscored, numFound); a field
+    left out is NULL"""
+    out = _lib.AwFmWindowOutputs()
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmWindowOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def score_windows_affine(read_chars, read_offsets, window_sequences, window_begins, window_ends, text, sequence_ends=None,
+                         alphabet=AwFmAlphabetDna, scoring=AFFINE_SCORING, min_score=0, slots=None, slot_stride=1, slot_column=0, threads=4,
+                         outputs=None, num_read_chars=None, fill=None, unscored_before=0, found_before=0):
+    """awfmScoreWindowsAffine (include/awfm_gpu.h, "window scores"), the host twin: the full-width local affine alignment of read r
+    against the window [window_begins[r], window_ends[r]) of record window_sequences[r] -> a dict of scores, readBegins, readEnds,
+    textBegins, textEnds per read, the six slot arrays shaped (reads, slot_stride) of which column slot_column is written,
+    numUnscored and numFound (ints: the values before plus this call's).  slots: a dict of slot arrays to write into (copied;
+    None: arrays of the unused slot), so that the reads not looked at keep theirs.  outputs: the names to compute (None: all);
+    the others are passed as NULL and left out.  fill: the value (per byte) the per-read arrays hold before the call."""
+    chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
+    t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    ends = None if sequence_ends is None else np.ascontiguousarray(sequence_ends, dtype=np.uint64)
+    n = max(o.size - 1, 0)
+    ws = np.ascontiguousarray(window_sequences, dtype=np.uint32)
+    wb = np.ascontiguousarray(window_begins, dtype=np.uint64)
+    we = np.ascontiguousarray(window_ends, dtype=np.uint64)
+    if ws.shape != (n,) or wb.shape != (n,) or we.shape != (n,):
+        raise ValueError("the window arrays are shaped (reads,)")
+    names = [name for name, _ in WINDOW_READ_OUTPUTS] + [name for name, _ in VERIFY_SLOT_INPUTS] + ["numUnscored", "numFound"]
+    outputs = names if outputs is None else list(outputs)
+    result = {name: np.zeros(n, dtype) for name, dtype in WINDOW_READ_OUTPUTS if name in outputs}
+    for a in result.values():
+        if fill is not None:
+            a.view(np.uint8)[...] = fill
+    rows = max(n, 1) if not 1 <= slot_stride <= 16 else n  # (a refused stride never indexes the arrays)
+    for name, dtype in VERIFY_SLOT_INPUTS:
+        if name in outputs:
+            if slots is not None:
+                result[name] = np.array(slots[name], dtype=dtype, order="C")
+            else:
+                result[name] = np.zeros((rows, max(min(int(slot_stride), 16), 1)), dtype)
+                if name == "sequences":
+                    result[name][...] = 0xFFFFFFFF
+    counters = {"numUnscored": np.array([unscored_before], np.uint64), "numFound": np.array([found_before], np.uint64)}
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else dummy.ctypes.data
+
+    win = window_inputs(address(chars), chars.size if num_read_chars is None else num_read_chars, address(o), address(ws), address(wb), address(we))
+    wout = window_score_outputs(**{name: address(a) for name, a in result.items()})
+    for name, counter in counters.items():
+        if name in outputs:
+            setattr(wout, name, counter.ctypes.data)
+    costs = scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+    rc = _lib.lib().awfmScoreWindowsAffine(C.byref(win), n, C.byref(costs), min_score, slot_stride, slot_column, address(t), t.size,
+                                           None if ends is None or not ends.size else ends.ctypes.data, 0 if ends is None else ends.size,
+                                           alphabet, C.byref(wout), threads)
+    _check("awfmScoreWindowsAffine", rc)
+    for name, counter in counters.items():
+        if name in outputs:
+            result[name] = int(counter[0])
+    return result
+
+
 AWFM_EDIT_NONE = 0xFFFFFFFF  # the edit of a record of the unedited query (include/awfm_gpu.h)
 
 
@@ -982,6 +1062,26 @@ class GpuIndex:
                _lib.lib().awfmGpuScoreChainsAffine(self.handle, C.byref(inputs), num_reads, max_candidates, band_pad, max_drift,
                                                    None if costs is None else C.byref(costs), min_score, mapq_cap, C.byref(outputs),
                                                    stream or None))
+
+    # window scores (include/awfm_gpu.h) ----------------------------------
+    def score_windows_affine_scratch_bytes(self, max_length):
+        """awfmGpuScoreWindowsAffineScratchBytes: the bytes of device scratch score_windows_affine needs for reads of up to max_length
+        characters (1..4096)"""
+        return int(_lib.lib().awfmGpuScoreWindowsAffineScratchBytes(self.handle, max_length))
+
+    def score_windows_affine(self, inputs, num_reads, outputs, d_scratch, max_length, scoring=AFFINE_SCORING, min_score=0, slot_stride=1,
+                             slot_column=0, stream=0):
+        """awfmGpuScoreWindowsAffine: inputs window_inputs(...) and outputs window_score_outputs(...) of device addresses, scoring
+        (match, mismatch, gap_open, gap_extend) or an align_scoring(...), d_scratch score_windows_affine_scratch_bytes(max_length)
+        bytes of device memory of this call's own, aligned to 16 bytes; the full-width local affine alignment of every read against
+        the window it names, and column slot_column of a slot table of slot_stride columns that align_chains_affine and
+        score_chains_affine take as it is; a read longer than max_length is TOO LONG; one launch, asynchronous on `stream`;
+        *numUnscored and *numFound are added to"""
+        costs = None if scoring is None else scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+        _check("awfmGpuScoreWindowsAffine",
+               _lib.lib().awfmGpuScoreWindowsAffine(self.handle, C.byref(inputs), num_reads, None if costs is None else C.byref(costs), min_score,
+                                                    slot_stride, slot_column, max_length, C.byref(outputs), d_scratch or None,
+                                                    stream or None))
 
     def locate_host_local(self, chars, offsets=None, fixed_length=0):
         """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],

@@ -87,6 +87,7 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   align_group=16|32|64    awfmGpuAlignChains: lanes per read, in the same way
  *   affine_group=32|64      awfmGpuAlignChainsAffine: lanes per read, in the same way
  *   score_group=32|64       awfmGpuScoreChainsAffine: lanes per slot, in the same way
+ *   window_q=4|8|12         awfmGpuScoreWindowsAffine: columns per lane for every read (narrower column blocks)
  *   second_window=0|1   the lookup kernel's second table window (a survivor's leftmost characters): 0 never, 1 on every trip;
  *                       unset, the kernel's own gate decides trip by trip (the results are the same either way)
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
@@ -868,6 +869,90 @@ enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uin
 enum AwFmReturnCode awfmGpuScoreChainsAffine(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
                                              uint32_t bandPad, uint32_t maxDrift, const struct AwFmAlignScoring *scoring, uint32_t minScore,
                                              uint32_t mapqCap, const struct AwFmSlotScoreOutputs *dOut, void *stream);
+
+/* ---- window scores: the full-width local affine alignment of a read against a text window the caller names, as a slot ----
+ * The stage for reads WITHOUT a chain: a mate with a burst of errors, a read across a divergent stretch, a read shorter than a
+ * seed, whose place the caller knows to within some hundred positions (from its mate, from an earlier pass).  No seeds, no
+ * chain, no band: every cell of read x window.  The result is the score with its begin and end cell, and a chain slot that
+ * affine alignment and slot scores take as it is.  It does not pair mates, choose an insert size or handle strands: one window
+ * per read and call, no second best inside a window.  Read buffer, scoring and its ranges, the letter rule (an ambiguity
+ * letter matches nothing), text, record table, alphabet, the NULL rules, "every output may be NULL", "counters are added to",
+ * "numReads == 0 touches nothing" and numReads < 2^32 are affine alignment's.  slotStride 1..16 and slotColumn < slotStride,
+ * else AwFmIllegalPositionError.  One definition on both sides, the host twin (csrc/awfm_window_affine.c) being the definition
+ * and the checker of the device call.
+ *
+ * Per read r, in this order, with n the read's length and L the length of the record windowSequences[r]:
+ *   NOT LOOKED AT  windowSequences[r] == AWFM_CANDIDATES_NONE: scores[r] = AWFM_VERIFY_NONE, the read's other per-read outputs are 0
+ *                  and ITS SLOT ELEMENT IS NOT WRITTEN: a caller fills column j of an existing slot table for the reads that need
+ *                  it and keeps the chains of the others.
+ *   MALFORMED      the sequence is >= the number of sequences, windowBegins[r] > windowEnds[r], the read's offsets are inverted or
+ *                  beyond numReadChars, or the record leaves the text: AWFM_VERIFY_MALFORMED, nothing is read through it.
+ *   clipping       b = min(begin, L), e = min(end, L), W = e - b: a window is clipped to its record, never refused for leaving it.
+ *   TOO WIDE       W > AWFM_WINDOW_MAX_WIDTH.
+ *   TOO LONG       n > AWFM_WINDOW_MAX_LENGTH; ON THE DEVICE ALSO n > maxLength, the read length the call's scratch was sized for
+ *                  (the one place where the two sides may differ: a checker passes maxLength >= the longest read).
+ *   otherwise      the LOCAL affine alignment of the whole read R against T = record[b, e): the recurrence of "affine alignment"
+ *                  word for word (row 0: H = 0, E = F = -inf; M, F, E, H = max(0, M, F, E)) over ALL cells 0 <= i <= n,
+ *                  0 <= t <= W, and its end cell: the largest H with i >= 1, then the smallest i, then the smallest t.  scores[r]
+ *                  is that H; when it is 0 (also n = 0 or W = 0) nothing is aligned and every other output of the read is 0.
+ *                  readEnds[r] = i, textEnds[r] = b + t.
+ *   begin cell     where affine alignment's walk back from that end cell stops, defined FORWARD so that neither side keeps a
+ *                  trace.  Every value carries an origin:
+ *                    O_H(i, t) = (i, t) when H = 0; else O_H(i-1, t-1) when M = H; else O_F(i, t) when F = H; else O_E(i, t);
+ *                    O_F(i, t) = O_H(i-1, t) when H(i-1, t) - o - e >= F(i-1, t) - e, else O_F(i-1, t);
+ *                    O_E(i, t) = O_H(i, t-1) when H(i, t-1) - o - e >= E(i, t-1) - e, else O_E(i, t-1).
+ *                  (i0, t0) = O_H(end cell): readBegins[r] = i0, textBegins[r] = b + t0.
+ *   THE SLOT, element r * slotStride + slotColumn of the six arrays, is written for every read that is looked at: with a score
+ *   >= max(minScore, 1): sequences = the window's sequence, chainAnchors = 1, chainReadBegins = readBegin, chainReadEnds =
+ *   readEnd, chainBeginDiagonals = textBegin - readBegin, chainEndDiagonals = textEnd - readEnd; otherwise, status values
+ *   included, the unused slot AWFM_CANDIDATES_NONE, 0, 0, 0, 0, 0.  A written slot is never malformed under chain verification's
+ *   rules (0 <= tb <= te <= L).  Handed to awfmAlignChainsAffine with (w, x) it yields a score <= this one, and the same score,
+ *   begin and end whenever the optimal path stays within [min(bD, eD) - w, max(bD, eD) + w]; |eD - bD| > x is TOO WIDE there:
+ *   the caller chooses x for the gaps it expects.
+ *   *numUnscored: reads that got MALFORMED, TOO_WIDE or TOO_LONG; *numFound: reads with a score >= max(minScore, 1).
+ *
+ * awfmScoreWindowsAffine (csrc/awfm_window_affine.c): on the host over `threads` threads of the pool, a read at a time, two rows
+ * of W + 1 cells with the three values and their origins; no n x W table.  awfmGpuScoreWindowsAffine
+ * (csrc/awfm_window_affine_kernel.h): the same on device arrays with the image's text, record table and alphabet
+ * (AwFmUnsupportedVersionError without a text); ONE launch, asynchronous on `stream`, no host wait, no allocation.  A wave per
+ * read as a systolic array: a lane owns Q consecutive columns (4, 8 or 12: the smallest with 64 Q >= W, chosen per read),
+ * rows flow through the lanes a step apart; a window wider than 768 goes in blocks of 768 columns whose boundary column
+ * passes through dScratch: awfmGpuScoreWindowsAffineScratchBytes(g, maxLength) bytes (maxLength 1..AWFM_WINDOW_MAX_LENGTH, else
+ * 0), 16-byte aligned, this call's own until it has finished -- two streams may run the call at once with a dScratch each.
+ * dScratch == NULL or maxLength outside its range: AwFmNullPtrError / AwFmIllegalPositionError.  $AWFM_GPU_DIAG
+ * window_q=4|8|12 fixes Q for every read (tests: narrower blocks, so the column-block path at small widths; the result
+ * does not depend on it). */
+#define AWFM_WINDOW_MAX_WIDTH 4096u  /* text characters per window after clipping to the record */
+#define AWFM_WINDOW_MAX_LENGTH 4096u /* read characters */
+struct AwFmWindowInputs {
+  const uint8_t *readChars; /* as AwFmVerifyInputs */
+  uint64_t numReadChars;
+  const uint64_t *readOffsets;     /* [numReads + 1] */
+  const uint32_t *windowSequences; /* [numReads]  AWFM_CANDIDATES_NONE: this read is not looked at */
+  const uint64_t *windowBegins;    /* [numReads]  sequence-local, [begin, end) */
+  const uint64_t *windowEnds;      /* [numReads] */
+};
+struct AwFmWindowOutputs {
+  uint32_t *scores;     /* [numReads]  a score (0: nothing aligned) or a status value */
+  uint32_t *readBegins; /* [numReads]  the aligned part of the read: [readBegin, readEnd) */
+  uint32_t *readEnds;   /* [numReads] */
+  uint64_t *textBegins; /* [numReads]  sequence-local */
+  uint64_t *textEnds;   /* [numReads] */
+  /* the slot, element r * slotStride + slotColumn of each: the six per-slot arrays of AwFmVerifyInputs */
+  uint32_t *sequences, *chainAnchors, *chainReadBegins, *chainReadEnds;
+  int64_t *chainBeginDiagonals, *chainEndDiagonals;
+  uint64_t *numUnscored; /* one counter, added to: MALFORMED, TOO_WIDE, TOO_LONG */
+  uint64_t *numFound;    /* one counter, added to: reads with score >= max(minScore, 1) */
+};
+enum AwFmReturnCode awfmScoreWindowsAffine(const struct AwFmWindowInputs *in, uint64_t numReads, const struct AwFmAlignScoring *scoring,
+                                           uint32_t minScore, uint32_t slotStride, uint32_t slotColumn, const uint8_t *text, uint64_t length,
+                                           const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
+                                           const struct AwFmWindowOutputs *out, unsigned threads);
+uint64_t awfmGpuScoreWindowsAffineScratchBytes(const AwFmGpuIndex *g, uint32_t maxLength);
+enum AwFmReturnCode awfmGpuScoreWindowsAffine(AwFmGpuIndex *g, const struct AwFmWindowInputs *dIn, uint64_t numReads,
+                                              const struct AwFmAlignScoring *scoring, uint32_t minScore, uint32_t slotStride,
+                                              uint32_t slotColumn, uint32_t maxLength, const struct AwFmWindowOutputs *dOut, void *dScratch,
+                                              void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
