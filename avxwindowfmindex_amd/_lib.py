@@ -48,6 +48,7 @@ GPU_SYMBOLS = [
     "awfmAlignChainsAffine", "awfmGpuAlignChainsAffineScratchBytes", "awfmGpuAlignChainsAffine",
     "awfmScoreChainsAffine", "awfmGpuScoreChainsAffine",
     "awfmScoreWindowsAffine", "awfmGpuScoreWindowsAffineScratchBytes", "awfmGpuScoreWindowsAffine",
+    "awfmPairMates", "awfmGpuPairMates", "awfmReverseComplementReads", "awfmGpuReverseComplementReads",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -145,6 +146,26 @@ class AwFmWindowOutputs(C.Structure):
                 ("textEnds", C.c_void_p), ("sequences", C.c_void_p), ("chainAnchors", C.c_void_p), ("chainReadBegins", C.c_void_p),
                 ("chainReadEnds", C.c_void_p), ("chainBeginDiagonals", C.c_void_p), ("chainEndDiagonals", C.c_void_p),
                 ("numUnscored", C.c_void_p), ("numFound", C.c_void_p)]
+
+
+class AwFmPairInputs(C.Structure):
+    """struct AwFmPairInputs (include/awfm_gpu.h): host or device addresses; mappingQualities may be NULL"""
+    _fields_ = [("readOffsets", C.c_void_p), ("sequences", C.c_void_p), ("slotScores", C.c_void_p), ("slotReadEnds", C.c_void_p),
+                ("slotTextEnds", C.c_void_p), ("mappingQualities", C.c_void_p)]
+
+
+class AwFmPairParams(C.Structure):
+    """struct AwFmPairParams (include/awfm_gpu.h): minInsert <= maxInsert within +-2^40, mapqCap 0..254"""
+    _fields_ = [("minInsert", C.c_int64), ("maxInsert", C.c_int64), ("minScore", C.c_uint32), ("unpairedPenalty", C.c_uint32),
+                ("windowPad", C.c_uint32), ("mapqCap", C.c_uint32)]
+
+
+class AwFmPairOutputs(C.Structure):
+    """struct AwFmPairOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("properPairs", C.c_void_p), ("pairSlots", C.c_void_p), ("pairScores", C.c_void_p), ("pairSecondScores", C.c_void_p),
+                ("templateLengths", C.c_void_p), ("pairQualities", C.c_void_p), ("mappingQualities", C.c_void_p),
+                ("windowSequences", C.c_void_p), ("windowBegins", C.c_void_p), ("windowEnds", C.c_void_p), ("numProper", C.c_void_p),
+                ("numWindows", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -322,6 +343,10 @@ def lib():
         "awfmScoreWindowsAffine": (C.c_int, [C.POINTER(AwFmWindowInputs), u64, C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.c_uint32,
                                              vp, u64, vp, u64, C.c_int, C.POINTER(AwFmWindowOutputs), C.c_uint]),
         "awfmGpuScoreWindowsAffineScratchBytes": (u64, [vp, C.c_uint32]),
+        "awfmPairMates": (C.c_int, [C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmPairParams), C.POINTER(AwFmPairOutputs), C.c_uint]),
+        "awfmGpuPairMates": (C.c_int, [vp, C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmPairParams), C.POINTER(AwFmPairOutputs), vp]),
+        "awfmReverseComplementReads": (C.c_int, [vp, u64, vp, u64, C.c_uint32, vp, vp, C.c_uint]),
+        "awfmGpuReverseComplementReads": (C.c_int, [vp, vp, u64, vp, u64, C.c_uint32, vp, vp, vp]),
         "awfmGpuScoreWindowsAffine": (C.c_int, [vp, C.POINTER(AwFmWindowInputs), u64, C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.c_uint32, C.POINTER(AwFmWindowOutputs), vp, vp]),
         "awfmGpuScoreChainsAffine": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,

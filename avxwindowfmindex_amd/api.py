@@ -802,6 +802,104 @@ def score_windows_affine(read_chars, read_offsets, window_sequences, window_begi
     return result
 
 
+COMPLEMENT_ALL, COMPLEMENT_ODD, COMPLEMENT_EVEN = 0, 1, 2  # AWFM_COMPLEMENT_*: the reads reverse_complement_reads selects
+PAIR_MAX_INSERT = 1 << 40  # AWFM_PAIR_MAX_INSERT: |min_insert|, |max_insert| <= this
+PAIR_SLOT_INPUTS = (("sequences", np.uint32), ("slotScores", np.uint32), ("slotReadEnds", np.uint32), ("slotTextEnds", np.uint64))
+PAIR_PAIR_OUTPUTS = (("properPairs", np.uint8), ("pairScores", np.uint32), ("pairSecondScores", np.uint32), ("templateLengths", np.int64),
+                     ("pairQualities", np.uint8))
+PAIR_READ_OUTPUTS = (("pairSlots", np.uint32), ("mappingQualities", np.uint8), ("windowSequences", np.uint32), ("windowBegins", np.uint64),
+                     ("windowEnds", np.uint64))
+
+
+def pair_inputs(read_offsets, sequences, slot_scores, slot_read_ends, slot_text_ends, mapping_qualities=0):
+    """struct AwFmPairInputs from addresses: the read offsets, the slot table's sequences, the three per-slot arrays slot scores
+    wrote and (0: NULL, every quality 0) its mapping qualities"""
+    return _lib.AwFmPairInputs(read_offsets or None, sequences or None, slot_scores or None, slot_read_ends or None, slot_text_ends or None,
+                               mapping_qualities or None)
+
+
+def pair_params(min_insert, max_insert, min_score=0, unpaired_penalty=0, window_pad=0, mapq_cap=60):
+    """struct AwFmPairParams"""
+    return _lib.AwFmPairParams(min_insert, max_insert, min_score, unpaired_penalty, window_pad, mapq_cap)
+
+
+def pair_outputs(**addresses):
+    """struct AwFmPairOutputs from addresses by field name (properPairs, pairSlots, pairScores, pairSecondScores, templateLengths,
+    pairQualities, mappingQualities, windowSequences, windowBegins, windowEnds, numProper, numWindows); a field left out is NULL"""
+    out = _lib.AwFmPairOutputs()
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmPairOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def pair_mates_host(read_offsets, slots, min_insert, max_insert, mapping_qualities=None, min_score=0, unpaired_penalty=0, window_pad=0,
+                    mapq_cap=60, threads=4, outputs=None, fill=None, proper_before=0, windows_before=0, max_candidates=None):
+    """awfmPairMates (include/awfm_gpu.h, "pair mates"), the host twin: reads 2p and 2p + 1 are a pair on one strand; slots: a dict
+    of sequences, slotScores, slotReadEnds, slotTextEnds shaped (reads, max_candidates) as score_chains_affine_host returns them
+    -> a dict of properPairs, pairScores, pairSecondScores, templateLengths, pairQualities per pair, pairSlots, mappingQualities,
+    windowSequences, windowBegins, windowEnds per read, numProper and numWindows (ints: the values before plus this call's).
+    outputs: the names to compute (None: all); the others are passed as NULL and left out.  fill: the value (per byte) the arrays
+    hold before the call.  max_candidates: what the call is told (None: the arrays' second dimension)."""
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    n = max(o.size - 1, 0)
+    if n % 2:
+        raise ValueError("pairs are reads 2p and 2p + 1: an even number of reads")
+    arrays = {name: np.ascontiguousarray(slots[name], dtype=dtype) for name, dtype in PAIR_SLOT_INPUTS}
+    shape = arrays["sequences"].shape
+    if len(shape) != 2 or shape[0] != n or any(a.shape != shape for a in arrays.values()):
+        raise ValueError("the slot arrays are shaped (reads, max_candidates)")
+    given = None if mapping_qualities is None else np.ascontiguousarray(mapping_qualities, dtype=np.uint8)
+    if given is not None and given.shape != (n,):
+        raise ValueError("mapping_qualities is shaped (reads,)")
+    names = [name for name, _ in PAIR_PAIR_OUTPUTS + PAIR_READ_OUTPUTS] + ["numProper", "numWindows"]
+    outputs = names if outputs is None else list(outputs)
+    result = {name: np.zeros(n // 2, dtype) for name, dtype in PAIR_PAIR_OUTPUTS if name in outputs}
+    result.update({name: np.zeros(n, dtype) for name, dtype in PAIR_READ_OUTPUTS if name in outputs})
+    for a in result.values():
+        if fill is not None:
+            a.view(np.uint8)[...] = fill
+    counters = {"numProper": np.array([proper_before], np.uint64), "numWindows": np.array([windows_before], np.uint64)}
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else dummy.ctypes.data
+
+    pin = pair_inputs(address(o), *(address(arrays[name]) for name, _ in PAIR_SLOT_INPUTS), 0 if given is None else address(given))
+    pout = pair_outputs(**{name: address(a) for name, a in result.items()})
+    for name, counter in counters.items():
+        if name in outputs:
+            setattr(pout, name, counter.ctypes.data)
+    params = pair_params(min_insert, max_insert, min_score, unpaired_penalty, window_pad, mapq_cap)
+    rc = _lib.lib().awfmPairMates(C.byref(pin), n // 2, shape[1] if max_candidates is None else max_candidates, C.byref(params), C.byref(pout),
+                                  threads)
+    _check("awfmPairMates", rc)
+    for name, counter in counters.items():
+        if name in outputs:
+            result[name] = int(counter[0])
+    return result
+
+
+def reverse_complement_reads_host(read_chars, read_offsets, which=COMPLEMENT_ODD, threads=4, num_read_chars=None, fill=0,
+                                  malformed_before=0):
+    """awfmReverseComplementReads (include/awfm_gpu.h, "pair mates"), DNA: -> (out uint8[len(read_chars)], numMalformed): the reads
+    `which` selects (COMPLEMENT_ALL, COMPLEMENT_ODD: mate 2 of interleaved pairs, COMPLEMENT_EVEN) reverse-complemented, the others
+    copied, a malformed read neither read nor written and counted.  fill: what the output holds before the call."""
+    chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    n = max(o.size - 1, 0)
+    out = np.full(chars.size, fill, np.uint8)
+    counter = np.array([malformed_before], np.uint64)
+    dummy = np.zeros(1, np.uint64)
+    rc = _lib.lib().awfmReverseComplementReads(chars.ctypes.data if chars.size else dummy.ctypes.data,
+                                               chars.size if num_read_chars is None else num_read_chars,
+                                               o.ctypes.data if o.size else dummy.ctypes.data, n, which,
+                                               out.ctypes.data if out.size else dummy.ctypes.data + 4, counter.ctypes.data, threads)
+    _check("awfmReverseComplementReads", rc)
+    return out, int(counter[0])
+
+
 AWFM_EDIT_NONE = 0xFFFFFFFF  # the edit of a record of the unedited query (include/awfm_gpu.h)
 
 
@@ -1082,6 +1180,26 @@ class GpuIndex:
                _lib.lib().awfmGpuScoreWindowsAffine(self.handle, C.byref(inputs), num_reads, None if costs is None else C.byref(costs), min_score,
                                                     slot_stride, slot_column, max_length, C.byref(outputs), d_scratch or None,
                                                     stream or None))
+
+    # pair mates (include/awfm_gpu.h) --------------------------------------
+    def pair_mates(self, inputs, num_pairs, outputs, min_insert, max_insert, max_candidates=4, min_score=0, unpaired_penalty=0,
+                   window_pad=0, mapq_cap=60, stream=0):
+        """awfmGpuPairMates: inputs pair_inputs(...) and outputs pair_outputs(...) of device addresses; reads 2p and 2p + 1 are a
+        pair on one strand (reverse_complement_reads); per pair the winner among the concordant slot pairs (min_insert <= T <=
+        max_insert) and the discordant candidate, the second and the pair's quality, per read pairSlots (what align_chains_affine
+        takes as d_slots), the mapping quality and the rescue window (what window_inputs takes); one launch, no scratch,
+        asynchronous on `stream`; *numProper and *numWindows are added to"""
+        params = pair_params(min_insert, max_insert, min_score, unpaired_penalty, window_pad, mapq_cap)
+        _check("awfmGpuPairMates", _lib.lib().awfmGpuPairMates(self.handle, C.byref(inputs), num_pairs, max_candidates, C.byref(params),
+                                                               C.byref(outputs), stream or None))
+
+    def reverse_complement_reads(self, d_read_chars, num_read_chars, d_read_offsets, num_reads, d_out, which=COMPLEMENT_ODD,
+                                 d_num_malformed=0, stream=0):
+        """awfmGpuReverseComplementReads (DNA): d_out, num_read_chars bytes that do not overlap the input, gets the reads `which`
+        selects reverse-complemented and the others copied; one launch, asynchronous on `stream`; *d_num_malformed is added to"""
+        _check("awfmGpuReverseComplementReads",
+               _lib.lib().awfmGpuReverseComplementReads(self.handle, d_read_chars or None, num_read_chars, d_read_offsets or None, num_reads,
+                                                        which, d_out or None, d_num_malformed or None, stream or None))
 
     def locate_host_local(self, chars, offsets=None, fixed_length=0):
         """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],

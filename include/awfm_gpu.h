@@ -88,6 +88,7 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   affine_group=32|64      awfmGpuAlignChainsAffine: lanes per read, in the same way
  *   score_group=32|64       awfmGpuScoreChainsAffine: lanes per slot, in the same way
  *   window_q=4|8|12         awfmGpuScoreWindowsAffine: columns per lane for every read (narrower column blocks)
+ *   pair_group=64           awfmGpuPairMates: a wave per pair also where 16 lanes hold the candidates
  *   second_window=0|1   the lookup kernel's second table window (a survivor's leftmost characters): 0 never, 1 on every trip;
  *                       unset, the kernel's own gate decides trip by trip (the results are the same either way)
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
@@ -839,7 +840,7 @@ enum AwFmReturnCode awfmGpuAlignChainsAffine(AwFmGpuIndex *g, const struct AwFmV
  *      none: exact in unsigned 32 bits, since best < 2^24 and mapqCap <= AWFM_SCORE_MAX_MAPQ = 254 (255 is SAM's "unavailable":
  *      AwFmIllegalPositionError).
  * This rule is the library's OWN, not BWA's and not minimap2's; nothing on the path is floating-point.  A caller with another
- * rule takes bestScores and secondScores.  Duplicates are told by their end cell only; mates are not paired.
+ * rule takes bestScores and secondScores.  Duplicates are told by their end cell only; mates are paired by "pair mates" below.
  * *numUnscored: the slots that got MALFORMED, TOO_WIDE or TOO_LONG; *numMapped: the reads with a best slot.
  *
  * awfmScoreChainsAffine (csrc/awfm_score_affine.c): on the host over `threads` threads of the pool, a read at a time, three rows
@@ -874,7 +875,7 @@ enum AwFmReturnCode awfmGpuScoreChainsAffine(AwFmGpuIndex *g, const struct AwFmV
  * The stage for reads WITHOUT a chain: a mate with a burst of errors, a read across a divergent stretch, a read shorter than a
  * seed, whose place the caller knows to within some hundred positions (from its mate, from an earlier pass).  No seeds, no
  * chain, no band: every cell of read x window.  The result is the score with its begin and end cell, and a chain slot that
- * affine alignment and slot scores take as it is.  It does not pair mates, choose an insert size or handle strands: one window
+ * affine alignment and slot scores take as it is.  Which window a mate gets is the caller's or "pair mates"' business: one window
  * per read and call, no second best inside a window.  Read buffer, scoring and its ranges, the letter rule (an ambiguity
  * letter matches nothing), text, record table, alphabet, the NULL rules, "every output may be NULL", "counters are added to",
  * "numReads == 0 touches nothing" and numReads < 2^32 are affine alignment's.  slotStride 1..16 and slotColumn < slotStride,
@@ -953,6 +954,114 @@ enum AwFmReturnCode awfmGpuScoreWindowsAffine(AwFmGpuIndex *g, const struct AwFm
                                               const struct AwFmAlignScoring *scoring, uint32_t minScore, uint32_t slotStride,
                                               uint32_t slotColumn, uint32_t maxLength, const struct AwFmWindowOutputs *dOut, void *dScratch,
                                               void *stream);
+
+/* ---- pair mates: reverse complement of reads, proper pairs, pair mapping quality and rescue windows ----
+ * The stage for PAIRED reads, between slot scores and affine alignment: reads 2p (mate A) and 2p + 1 (mate B) are a pair, both
+ * GIVEN ON THE SAME STRAND.  For the usual inward-facing library the caller reverse-complements mate 2 where the reads lie
+ * (awfmGpuReverseComplementReads, below) and a two-strand index finds fragments of either strand, each in its own record; with a
+ * one-strand index the caller submits (m1, rc m2) and (m2, rc m1) and compares pairScores itself.  The call knows no strands
+ * and ESTIMATES no insert size: minInsert and maxInsert are the caller's and signed, so other library geometries are a matter
+ * of sign and of which mate is complemented.  The loop runs without a host wait: chains, awfmGpuScoreChainsAffine, awfmGpuPairMates,
+ * awfmGpuScoreWindowsAffine on the windows the pairing names, awfmGpuScoreChainsAffine and awfmGpuPairMates again,
+ * awfmGpuAlignChainsAffine with pairSlots.  "every output may be NULL", "counters are added to", "numPairs == 0 touches nothing"
+ * are slot scores'.  One definition on both sides, the host twin (csrc/awfm_pair_mates.c) being the definition and the checker.
+ *
+ * Inputs, C = maxCandidates (1..16), numReads = 2 numPairs < 2^32: readOffsets [numReads + 1]; sequences [numReads * C], the
+ * slot table's column of that name; slotScores, slotReadEnds, slotTextEnds [numReads * C] exactly as awfmGpuScoreChainsAffine
+ * wrote them; mappingQualities [numReads], slot scores' (may be NULL: 0 everywhere).  params: minScore; minInsert <= maxInsert,
+ * both within +-2^40; unpairedPenalty; windowPad; mapqCap 0..AWFM_SCORE_MAX_MAPQ.  C or numPairs outside their range, or params
+ * outside theirs: AwFmIllegalPositionError; in, out, params or a required array NULL: AwFmNullPtrError.  All sums of positions
+ * below are 64-bit two's complement (exact for whatever slot scores wrote: text ends < 2^63, read ends < 2^32), values and
+ * qualities are computed in 64 bits, and pairScores / pairSecondScores keep the low 32 bits (exact: a score is < 2^24).
+ *
+ * Per pair p, in this order (A = 2p, B = 2p + 1, n_r the length of read r):
+ *   1. a slot (r, j) COUNTS when its score is not one of the four status values and is >= max(minScore, 1) (slot scores' rule
+ *      1); a read whose offsets are inverted has no counting slot.  Its START is S(r, j) = (int64) slotTextEnds - slotReadEnds,
+ *      the end cell's diagonal (it may be negative).  best(r) is slot scores' rule 2: the largest score, ties to the lowest slot.
+ *   2. (a, b) is CONCORDANT when both slots count, they name the same sequence and minInsert <= T <= maxInsert with
+ *      T = S(B, b) + n_B - S(A, a).  Its value is the sum of the two scores.
+ *   3. the DISCORDANT candidate exists when both mates have a best slot and (best(A), best(B)) is not concordant; its value is
+ *      max(0, score + score - unpairedPenalty).
+ *   4. the WINNER is the candidate of the largest value; at equal value a concordant one goes first, then the lowest a, then
+ *      the lowest b.  properPairs[p] = 1 when the winner is concordant, else 0; pairSlots[A], pairSlots[B] = the winner's slots
+ *      (with one mate placed: its best slot, and AWFM_CHAINS_NO_SLOT for the other; with none: both AWFM_CHAINS_NO_SLOT);
+ *      pairSlots has the shape of bestSlots and goes into awfmGpuAlignChainsAffine as it is.  pairScores[p] = the winner's
+ *      value, or the single placed mate's score, or 0.  templateLengths[p] = T for a proper pair, else 0.
+ *   5. slot j' is THE SAME as slot j of a read when j' = j, or when both count, name one sequence and have one (readEnd,
+ *      textEnd) (slot scores' rule 3); a candidate (a', b') DUPLICATES the winner when a' is the same as a and b' the same as b.
+ *      pairSecondScores[p] = the largest value among the other candidates that do not duplicate the winner (the discordant
+ *      one included unless it is the winner), 0 without one.
+ *   6. pairQualities[p] = floor(mapqCap * (win - second) / win) for a proper pair, else 0.  For the reads of a proper pair the
+ *      output mappingQualities[r] = max(pairQualities[p], q), q being the input mappingQualities[r] when pairSlots[r] ==
+ *      best(r), else 0; otherwise the input quality passes through, or 0 when the read has no best slot.  The output array may
+ *      be the input array.  This integer rule is the library's OWN, like slot scores': not BWA's and not minimap2's.
+ *   7. RESCUE WINDOWS, in the shape of struct AwFmWindowInputs: read r gets a window when its pair is not proper and its mate m
+ *      has a best slot: windowSequences[r] = that slot's sequence and, with S = S(m, best(m)),
+ *        r = B: [S + minInsert - n_B - windowPad, S + maxInsert + windowPad);
+ *        r = A: with E = S + n_B, [E - maxInsert - windowPad, E - minInsert + n_A + windowPad),
+ *      each bound computed signed and then raised to 0 (clipping to the record and the width limit are the window call's).
+ *      Every other read gets AWFM_CANDIDATES_NONE, 0, 0, so that the window call leaves its slot alone.
+ *   8. *numProper: proper pairs; *numWindows: reads that got a window.
+ * THE WINDOW CALL AND THE SLOT TABLE are the caller's business: awfmGpuScoreWindowsAffine overwrites column slotColumn of every
+ * read it looks at, also with the unused slot, so the caller keeps a column free for it -- for one, chains with C - 1 slots in
+ * a table of stride C.
+ *
+ * awfmPairMates (csrc/awfm_pair_mates.c): on the host over `threads` threads of the pool, a pair at a time, the rules as written.
+ * awfmGpuPairMates (csrc/awfm_pair_mates_kernel.h): the same on device arrays; it reads no text and nothing of the image, g
+ * gives the device.  ONE launch, asynchronous on `stream`, no host wait, no allocation, no scratch: two streams may run it on
+ * one image at once.  A group of 16 lanes per pair for C <= 4 (a lane per (a, b)), a wave per pair up to C = 16 (four
+ * candidates a lane); the winner and the second are one packed-key maximum over the group each.  $AWFM_GPU_DIAG pair_group=64
+ * forces the wave per pair at small C (tests; the result does not depend on it).
+ *
+ * REVERSE COMPLEMENT, DNA only (no alphabet argument).  out has numReadChars bytes and the same offsets.  `which` selects the
+ * reads: AWFM_COMPLEMENT_ALL, AWFM_COMPLEMENT_ODD (mate 2 of interleaved pairs) or AWFM_COMPLEMENT_EVEN, anything else
+ * AwFmIllegalPositionError; a read that is not selected is copied.  Per selected read of length n, byte i of the output is the
+ * complement of byte n - 1 - i: A<->T and C<->G in either letter case, the case kept, every other byte as it is (an ambiguity
+ * letter matches nothing on either strand under the library's letter rule).  A read with inverted offsets or offsets beyond
+ * numReadChars is neither read nor written and counts in *numMalformed (added to, may be NULL); bytes of the buffer that no
+ * read owns are not written, and where two reads share bytes the output holds either's.  Input and output may not overlap as
+ * pointer ranges of numReadChars bytes: AwFmIllegalPositionError.  numReads == 0 touches nothing.  awfmReverseComplementReads:
+ * on the host over `threads` threads.  awfmGpuReverseComplementReads: one launch, asynchronous on `stream`, a wave per read,
+ * a lane per aligned word of the output; g gives the device only. */
+#define AWFM_COMPLEMENT_ALL 0u
+#define AWFM_COMPLEMENT_ODD 1u
+#define AWFM_COMPLEMENT_EVEN 2u
+#define AWFM_PAIR_MAX_INSERT (1ll << 40) /* |minInsert|, |maxInsert| <= this */
+struct AwFmPairInputs {
+  const uint64_t *readOffsets;     /* [2 numPairs + 1] */
+  const uint32_t *sequences;       /* [numReads * C]  the slot table's */
+  const uint32_t *slotScores;      /* [numReads * C]  struct AwFmSlotScoreOutputs' */
+  const uint32_t *slotReadEnds;    /* [numReads * C] */
+  const uint64_t *slotTextEnds;    /* [numReads * C] */
+  const uint8_t *mappingQualities; /* [numReads]  may be NULL: 0 everywhere */
+};
+struct AwFmPairParams {
+  int64_t minInsert, maxInsert; /* minInsert <= T <= maxInsert makes a pair proper */
+  uint32_t minScore, unpairedPenalty, windowPad, mapqCap;
+};
+struct AwFmPairOutputs {
+  uint8_t *properPairs;       /* [numPairs]  1: the winner is concordant */
+  uint32_t *pairSlots;        /* [numReads]  the shape of bestSlots; AWFM_CHAINS_NO_SLOT for a read that is not placed */
+  uint32_t *pairScores;       /* [numPairs] */
+  uint32_t *pairSecondScores; /* [numPairs] */
+  int64_t *templateLengths;   /* [numPairs]  T of a proper pair, else 0 */
+  uint8_t *pairQualities;     /* [numPairs] */
+  uint8_t *mappingQualities;  /* [numReads]  may be the input array */
+  uint32_t *windowSequences;  /* [numReads]  struct AwFmWindowInputs'; AWFM_CANDIDATES_NONE: no window */
+  uint64_t *windowBegins;     /* [numReads] */
+  uint64_t *windowEnds;       /* [numReads] */
+  uint64_t *numProper;        /* one counter, added to: proper pairs */
+  uint64_t *numWindows;       /* one counter, added to: reads with a window */
+};
+enum AwFmReturnCode awfmPairMates(const struct AwFmPairInputs *in, uint64_t numPairs, uint32_t maxCandidates,
+                                  const struct AwFmPairParams *params, const struct AwFmPairOutputs *out, unsigned threads);
+enum AwFmReturnCode awfmGpuPairMates(AwFmGpuIndex *g, const struct AwFmPairInputs *dIn, uint64_t numPairs, uint32_t maxCandidates,
+                                     const struct AwFmPairParams *params, const struct AwFmPairOutputs *dOut, void *stream);
+enum AwFmReturnCode awfmReverseComplementReads(const uint8_t *readChars, uint64_t numReadChars, const uint64_t *readOffsets,
+                                               uint64_t numReads, uint32_t which, uint8_t *out, uint64_t *numMalformed, unsigned threads);
+enum AwFmReturnCode awfmGpuReverseComplementReads(AwFmGpuIndex *g, const uint8_t *dReadChars, uint64_t numReadChars,
+                                                  const uint64_t *dReadOffsets, uint64_t numReads, uint32_t which, uint8_t *dOut,
+                                                  uint64_t *dNumMalformed, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
