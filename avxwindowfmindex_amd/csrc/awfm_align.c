@@ -1,14 +1,14 @@
 /*
  * awfm_align.c -- awfmAlignChains (include/awfm_gpu.h, "chain alignment"): the banded fitting alignment of every read against the
  * record its chosen slot names, with the edit script.  The host twin of awfmGpuAlignChains and its checker: a read at a time,
- * the recurrence as the header states it with a direction byte per cell in an n x band table, then the walk back.  Exact and
- * readable rather than fast.  The reference has no analogue (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
+ * the recurrence as the header states it with a direction byte per cell in an n x band table, then the walk back.  The
+ * classification of the slot, the letter comparison and the argument checks are awfm_band.h's.  Exact and readable rather than
+ * fast.  The reference has no analogue (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
  */
 #include <stdlib.h>
 #include <string.h>
 
-#include "awfm_gpu.h"
-#include "awfm_internal.h"
+#include "awfm_band.h"
 
 #define AWFM_ALIGN_INF 0x3FFFFFFFu /* a cell that does not exist */
 enum { AWFM_DIR_DIAGONAL = 0, AWFM_DIR_UP = 1, AWFM_DIR_LEFT = 2 };
@@ -21,7 +21,7 @@ struct awfmAlignCtx {
   const uint8_t *text;
   const uint64_t *ends;
   uint64_t length, numRecords;
-  uint32_t slots, pad, drift, proper, maxOps;
+  uint32_t slots, pad, drift, maxOps;
   int amino, failed;
   uint64_t unaligned[64], truncated[64]; /* per thread of the loop */
 };
@@ -30,12 +30,6 @@ struct awfmAlignment {
   uint32_t distance, numOps;
   uint64_t textBegin, textEnd;
 };
-
-static uint32_t awfmAlignSub(const struct awfmAlignCtx *c, uint8_t a, uint8_t b) {
-  const uint8_t x = c->amino ? awfmAminoAsciiToIndex(a) : awfmNucAsciiToIndex(a);
-  const uint8_t y = c->amino ? awfmAminoAsciiToIndex(b) : awfmNucAsciiToIndex(b);
-  return x == y && x < c->proper ? 0u : 1u;
-}
 
 /* R[0 .. n) against the record T[0 .. L) inside the diagonals [lo, hi] (hi >= 0, lo + n <= L, hi - lo + 1 <= 64); the runs go to
  * ops[0 .. numOps) when numOps <= maxOps.  *table holds n x width direction bytes and grows as the thread meets longer reads. */
@@ -65,7 +59,7 @@ static int awfmAlignRead(const struct awfmAlignCtx *c, const uint8_t *R, int64_t
       uint8_t direction = AWFM_DIR_LEFT;
       if (t >= 0 && t <= L) {
         /* (i-1, t-1) lies on the same diagonal, (i-1, t) on the next one up, (i, t-1) on the one below */
-        const uint32_t diagonal = t >= 1 && prev[k] != AWFM_ALIGN_INF ? prev[k] + awfmAlignSub(c, R[i - 1], T[t - 1]) : AWFM_ALIGN_INF;
+        const uint32_t diagonal = t >= 1 && prev[k] != AWFM_ALIGN_INF ? prev[k] + awfmBandSub(c->amino, R[i - 1], T[t - 1]) : AWFM_ALIGN_INF;
         const uint32_t up = k + 1 < width && prev[k + 1] != AWFM_ALIGN_INF ? prev[k + 1] + 1u : AWFM_ALIGN_INF;
         const uint32_t left = k >= 1 && cur[k - 1] != AWFM_ALIGN_INF ? cur[k - 1] + 1u : AWFM_ALIGN_INF;
         best = diagonal < up ? diagonal : up;
@@ -93,7 +87,7 @@ static int awfmAlignRead(const struct awfmAlignCtx *c, const uint8_t *R, int64_t
     const uint8_t direction = directions[(i - 1) * width + k];
     uint32_t now;
     if (direction == AWFM_DIR_DIAGONAL) {
-      now = awfmAlignSub(c, R[i - 1], T[t - 1]) ? AWFM_OP_X : AWFM_OP_EQ;
+      now = awfmBandSub(c->amino, R[i - 1], T[t - 1]) ? AWFM_OP_X : AWFM_OP_EQ;
       i--;
     } else if (direction == AWFM_DIR_UP) {
       now = AWFM_OP_I;
@@ -132,29 +126,16 @@ static uint32_t awfmAlignOne(struct awfmAlignCtx *c, uint64_t r, uint8_t **table
   const uint32_t j = c->chosen[r];
   if (j == AWFM_CHAINS_NO_SLOT) return AWFM_VERIFY_NONE;
   if (j >= c->slots) return AWFM_VERIFY_MALFORMED;
-  const uint64_t at = r * c->slots + j;
-  const uint32_t s = in->sequences[at];
-  if (s == AWFM_CANDIDATES_NONE || in->chainAnchors[at] == 0) return AWFM_VERIFY_NONE;
-  const uint64_t readBegin = in->readOffsets[r], readEnd = in->readOffsets[r + 1];
-  if (readBegin > readEnd || readEnd > in->numReadChars) return AWFM_VERIFY_MALFORMED;
-  const uint64_t rb = in->chainReadBegins[at], re = in->chainReadEnds[at], n = readEnd - readBegin;
-  if (rb > re || re > n) return AWFM_VERIFY_MALFORMED;
-  if (s >= (c->numRecords ? c->numRecords : 1u)) return AWFM_VERIFY_MALFORMED;
-  const uint64_t S = c->numRecords && s ? c->ends[s - 1] + 1u : 0u, E = c->numRecords ? c->ends[s] : c->length;
-  if (c->numRecords && s && S == 0) return AWFM_VERIFY_MALFORMED; /* (an end of 2^64 - 1) */
-  if (E < S || E > c->length) return AWFM_VERIFY_MALFORMED;
-  const int64_t bD = in->chainBeginDiagonals[at], eD = in->chainEndDiagonals[at];
-  const __int128 tb = (__int128)rb + bD, te = (__int128)re + eD;
-  if (tb < 0 || tb > te || te > (__int128)(E - S)) return AWFM_VERIFY_MALFORMED;
-  /* 0 <= tb <= te <= L < 2^63 and rb, re < 2^32: both diagonals lie in (-2^32, 2^63) and their difference is exact */
-  const __int128 delta = (__int128)eD - bD;
-  if (delta > (__int128)c->drift || delta < -(__int128)c->drift) return AWFM_VERIFY_TOO_WIDE;
+  const uint64_t readBegin = in->readOffsets[r], readEnd = in->readOffsets[r + 1], n = readEnd - readBegin;
+  struct awfmSlotBand b;
+  const uint32_t status = awfmClassifySlot(in, c->ends, c->numRecords, c->length, c->drift, r * c->slots + j, n,
+                                           readBegin <= readEnd && readEnd <= in->numReadChars, &b);
+  if (status != AWFM_SLOT_HAS_BAND) return status;
   if (n > AWFM_ALIGN_MAX_LENGTH) return AWFM_VERIFY_TOO_LONG;
-  const int64_t L = (int64_t)(E - S);
-  const __int128 lo = (bD < eD ? bD : eD) - (__int128)c->pad, hi = (bD > eD ? bD : eD) + (__int128)c->pad;
-  if (hi < 0 || lo + (__int128)n > (__int128)L) return AWFM_ALIGN_OVERHANG;
+  const __int128 lo = (b.bD < b.eD ? b.bD : b.eD) - (__int128)c->pad, hi = (b.bD > b.eD ? b.bD : b.eD) + (__int128)c->pad;
+  if (hi < 0 || lo + (__int128)n > (__int128)b.L) return AWFM_ALIGN_OVERHANG;
   uint32_t *ops = c->out->ops ? c->out->ops + r * c->maxOps : NULL;
-  if (!awfmAlignRead(c, in->readChars + readBegin, (int64_t)n, c->text + S, L, (int64_t)lo, (int64_t)hi, table, tableBytes, ops, a)) {
+  if (!awfmAlignRead(c, in->readChars + readBegin, (int64_t)n, c->text + b.S, b.L, (int64_t)lo, (int64_t)hi, table, tableBytes, ops, a)) {
     c->failed = 1;
     return AWFM_VERIFY_NONE;
   }
@@ -190,12 +171,8 @@ enum AwFmReturnCode awfmAlignChains(const struct AwFmVerifyInputs *in, const uin
                                     const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
                                     const struct AwFmAlignOutputs *out, unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
-  if (!in || !out || !slots || !in->readOffsets || !in->sequences || !in->chainAnchors || !in->chainReadBegins || !in->chainReadEnds ||
-      !in->chainBeginDiagonals || !in->chainEndDiagonals)
-    return AwFmNullPtrError;
-  if ((!in->readChars && in->numReadChars != 0) || (!text && length != 0) || (!sequenceEnds && numRecords != 0)) return AwFmNullPtrError;
-  if (numReads >= (1ull << 32) || maxCandidates < 1 || maxCandidates > AWFM_CANDIDATES_MAX_SLOTS) return AwFmIllegalPositionError;
-  if ((uint64_t)maxDrift + 2ull * bandPad + 1ull > AWFM_VERIFY_MAX_BAND) return AwFmIllegalPositionError;
+  const enum AwFmReturnCode rc = awfmBandCheckArguments(in, out && slots, text, length, sequenceEnds, numRecords, numReads, maxCandidates, bandPad, maxDrift);
+  if (rc != AwFmSuccess) return rc;
   if (maxOps < 1 || maxOps > AWFM_ALIGN_MAX_OPS) return AwFmIllegalPositionError;
   struct awfmAlignCtx ctx;
   memset(&ctx, 0, sizeof ctx);
@@ -211,7 +188,6 @@ enum AwFmReturnCode awfmAlignChains(const struct AwFmVerifyInputs *in, const uin
   ctx.drift = maxDrift;
   ctx.maxOps = maxOps;
   ctx.amino = alphabet == AwFmAlphabetAmino;
-  ctx.proper = ctx.amino ? 20u : 4u;
   awfmParallelFor(threads ? threads : 1, numReads, awfmAlignRange, &ctx);
   if (ctx.failed) return AwFmAllocationFailure;
   uint64_t unaligned = 0, truncated = 0;

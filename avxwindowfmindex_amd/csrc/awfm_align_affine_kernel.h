@@ -3,15 +3,12 @@
  * alignment with affine gap costs of every read against the record its chosen slot names, with soft clipping and the walk back
  * that emits the edit script.  The definition is the header's; the host twin and checker is awfm_align_affine.c.
  *
- * The layout is alignChainsKernel<G>'s (awfm_align_kernel.h): a group of G lanes per read (persistent grid over reads), lane k is
- * diagonal lo + k of the band in sequence-local coordinates, the rows go in chunks of kVerifyChunk whose read characters and
- * text characters the group stages into its own words of LDS through stageBytes -- EVERY LOAD OF TEXT OR READ is an aligned
- * dword that holds a byte the slot owns, and the record is checked against the text's length before anything is read; only
- * aligned reads load text.  A lane carries H and F of the previous row; M comes from the lane itself, F from lane k + 1.  The
- * horizontal value is one exclusive max-prefix-scan per row over the group: E[k] = max over k' < k of (H~[k'] + k' e) - o - k e
- * with H~ = max(0, M, F) -- a gap that extends from a cell whose H came from E pays o twice and is dominated, so
- * the scan's E is the recurrence's.  Lanes and rows without a cell carry kAffineNeg and need no other case: max(0, ...) is
- * taken for existing cells only, and their trace code is "stop".
+ * A group of G lanes per read (persistent grid over reads), lane k is diagonal lo + k of the band in sequence-local
+ * coordinates, the rows go in chunks of kVerifyChunk.  The classification of the slot, the band, the staging of a chunk's read
+ * and text characters into the group's words of LDS, the row and the end cell are awfm_band_kernel.h's (classifySlot, readBand,
+ * stageChunk, affineRow, affineEndCell) -- EVERY LOAD OF TEXT OR READ is an aligned dword that holds a byte the slot owns, and
+ * the record is checked against the text's length before anything is read; only aligned reads load text.  Lanes and rows
+ * without a cell carry kBandNeg, and their trace code is "stop".
  *
  * THE TRACE.  Five wave-wide ballots give a row: three bits of the source of H (0 stop, 1 diagonal with equal letters, 2
  * diagonal with a substitution, 3 F, 4 E), "F of this cell opens its gap above" and "E of this cell opens its gap on the
@@ -26,7 +23,7 @@
 #ifndef AWFM_ALIGN_AFFINE_KERNEL_H
 #define AWFM_ALIGN_AFFINE_KERNEL_H
 
-#include "awfm_verify_kernel.h"
+#include "awfm_band_kernel.h"
 
 namespace {
 
@@ -35,7 +32,6 @@ constexpr unsigned kAffineLdsBytes = 3360;  /* static LDS at G = 16, the most gr
 constexpr unsigned kAffineBlocksPerCU = 4;  /* up to 128 VGPRs: four waves per SIMD, i.e. four workgroups of four waves per CU */
 constexpr unsigned kAffineRowBytes = 40;    /* of trace per row and wave: five ballots of 64 lanes, whatever G */
 static_assert(kAffineLdsBytes == (kAffineThreads / 16u) * kVerifyGroupWords * 4u + 32u, "the staging words of sixteen groups and the letter table");
-constexpr int kAffineNeg = -0x40000000; /* minus infinity: a lane resets it every row, so it only has to survive o + 64 e */
 
 struct DevAffineParams {
   struct AwFmVerifyInputs in;
@@ -116,105 +112,55 @@ __device__ __forceinline__ unsigned alignReadAffine(const DevAffineParams &p, co
   if (j == AWFM_CHAINS_NO_SLOT) return AWFM_VERIFY_NONE;
   if (j >= p.slots) return AWFM_VERIFY_MALFORMED;
   const unsigned long long at = r * p.slots + j;
-  const unsigned s = p.in.sequences[at];
-  if (s == AWFM_CANDIDATES_NONE || p.in.chainAnchors[at] == 0u) return AWFM_VERIFY_NONE;
-  const unsigned long long readBegin = p.in.readOffsets[r], readEnd = p.in.readOffsets[r + 1ull];
-  if (readBegin > readEnd || readEnd > p.in.numReadChars) return AWFM_VERIFY_MALFORMED;
-  const unsigned long long rb = p.in.chainReadBegins[at], re = p.in.chainReadEnds[at], n64 = readEnd - readBegin;
-  if (rb > re || re > n64) return AWFM_VERIFY_MALFORMED;
-  if (s >= (p.numRecords ? p.numRecords : 1u)) return AWFM_VERIFY_MALFORMED;
-  const unsigned long long S = p.numRecords && s ? p.ends[s - 1u] + 1ull : 0ull, E = p.numRecords ? p.ends[s] : p.length;
-  if (E < S || E > p.length) return AWFM_VERIFY_MALFORMED;
-  const long long bD = p.in.chainBeginDiagonals[at], eD = p.in.chainEndDiagonals[at];
-  /* E - S < 2^62 and rb, re < 2^32: a diagonal outside [-2^33, 2^62] makes tb < 0, tb > te or te > E - S whatever the other is,
-   * and inside it the sums are exact in 64 bits */
-  if (bD < -(1ll << 33) || eD < -(1ll << 33) || bD > (1ll << 62) || eD > (1ll << 62)) return AWFM_VERIFY_MALFORMED;
-  const long long tb = (long long)rb + bD, te = (long long)re + eD, L = (long long)(E - S);
-  if (tb < 0 || tb > te || te > L) return AWFM_VERIFY_MALFORMED;
-  const long long delta = eD - bD;
-  if (delta > (long long)p.drift || delta < -(long long)p.drift) return AWFM_VERIFY_TOO_WIDE;
+  const unsigned long long readBegin = p.in.readOffsets[r], readEnd = p.in.readOffsets[r + 1ull], n64 = readEnd - readBegin;
+  SlotBand slot;
+  const unsigned status = classifySlot(p, at, p.in.sequences[at], n64, readBegin <= readEnd && readEnd <= p.in.numReadChars, slot);
+  if (status != kSlotHasBand) return status;
   if (n64 > (unsigned long long)p.maxRows) return AWFM_VERIFY_TOO_LONG;
   const int n = (int)n64; /* <= 2^16 */
-  const long long lo = (bD < eD ? bD : eD) - (long long)p.pad, hi = (bD > eD ? bD : eD) + (long long)p.pad;
-  if (n == 0 || (long long)n + hi < 0 || lo + 1 > L) return 0u; /* no existing cell with i >= 1: nothing is aligned, nothing is read */
-  /* columns counted from lo: lane k's cell of row i is u = i + k, t = lo + u; it exists for uMin <= u <= uMax inside the band.
-   * Here -n - 63 <= lo <= L - 1, so uMin <= n + 63 and uMax >= 1; what lies beyond 2^30 is beyond every row */
-  const int width = (int)(hi - lo) + 1;
-  const int uMin = lo < 0 ? (int)-lo : 0, uMax = L - lo < (1ll << 30) ? (int)(L - lo) : 1 << 30;
-  const int uOne = lo < 1 ? (int)(1 - lo) : 0; /* t >= 1 from here on: the cell has a diagonal predecessor */
-  const bool inBand = (int)k < width;
-  const unsigned char *R = p.in.readChars + readBegin, *T = p.text + S;
-  const unsigned char *sReadBytes = (const unsigned char *)sRead, *sTextBytes = (const unsigned char *)sText;
-  const unsigned proper = p.amino ? 20u : 4u;
+  const ReadBand band = readBand(slot, p.pad);
+  const long long lo = band.lo;
+  if (n == 0 || (long long)n + band.hi < 0 || lo + 1 > slot.L) return 0u; /* no existing cell with i >= 1: nothing is aligned, nothing is read */
+  /* here -n - 63 <= lo <= L - 1, so uMin <= n + 63 and uMax >= 1 */
+  const int uMin = band.uMin, uMax = band.uMax;
+  const bool inBand = (int)k < band.width;
+  const unsigned char *R = p.in.readChars + readBegin, *T = p.text + slot.S;
   const int kExtend = (int)k * p.extend;
-  int prevH = inBand && (int)k >= uMin && (int)k <= uMax ? 0 : kAffineNeg, prevF = kAffineNeg; /* row 0: H(0, t) = 0 */
+  int prevH = inBand && (int)k >= uMin && (int)k <= uMax ? 0 : kBandNeg, prevF = kBandNeg; /* row 0: H(0, t) = 0 */
   int bestH = 0, bestI = 0;
   for (int i0 = 0; i0 < n; i0 += (int)kVerifyChunk) {
     const int rows = n - i0 < (int)kVerifyChunk ? n - i0 : (int)kVerifyChunk;
-    /* the text characters T[t - 1] of the chunk's rows i0 + 1 .. i0 + rows: u - 1 = i0 .. i0 + rows + width - 2, cut to the record */
-    const int uFrom = i0 > uMin ? i0 : uMin, uTo = i0 + rows + width - 1 < uMax ? i0 + rows + width - 1 : uMax;
-    __builtin_amdgcn_wave_barrier(); /* (the rows of the chunk before have read their bytes) */
-    const unsigned rOff = stageBytes<G>(R, (unsigned long long)i0, (unsigned long long)(i0 + rows), sRead, k);
-    const unsigned tOff = uTo > uFrom ? stageBytes<G>(T, (unsigned long long)(lo + uFrom), (unsigned long long)(lo + uTo), sText, k) : 0u;
-    __builtin_amdgcn_wave_barrier();
+    const StagedChunk chunk = stageChunk<G>(R, T, band, i0, rows, sRead, sText, k);
     for (int q = 0; q < rows; q++) {
       const int u = i0 + q + 1 + (int)k;
       const bool inMatrix = inBand && u >= uMin && u <= uMax;
-      const unsigned rLetter = verifyLetter(sAmino, p.amino, sReadBytes[rOff + (unsigned)q]);
-      unsigned tLetter = 0xFFu;
-      if (inMatrix && u >= uOne) tLetter = verifyLetter(sAmino, p.amino, sTextBytes[tOff + (unsigned)(u - 1 - uFrom)]);
-      const bool sub = !(rLetter == tLetter && rLetter < proper);
-      int upH = __shfl_down(prevH, 1, G), upF = __shfl_down(prevF, 1, G);
-      upH = k == (unsigned)(G - 1) ? kAffineNeg : upH;
-      upF = k == (unsigned)(G - 1) ? kAffineNeg : upF;
-      const int M = prevH + (sub ? -p.mismatch : p.match); /* (prevH is kAffineNeg when t = 0) */
-      const int fOpens = upH - p.open, fExtends = upF - p.extend;
-      const int F = fOpens > fExtends ? fOpens : fExtends;
-      int tilde = M > F ? M : F;
-      tilde = tilde > 0 ? tilde : 0;
-      tilde = inMatrix ? tilde : kAffineNeg;
-      /* E[k] + o + k e = max over k' < k of H~[k'] + k' e: shifted by a lane, then the inclusive scan */
-      int v = __shfl_up(tilde + kExtend, 1, G);
-      v = k == 0u ? kAffineNeg : v;
-#pragma unroll
-      for (int step = 1; step < G; step <<= 1) {
-        const int other = __shfl_up(v, step, G);
-        v = (int)k >= step && other > v ? other : v;
-      }
-      const int e = v - (p.open - p.extend) - kExtend;
-      const int h = inMatrix ? (tilde > e ? tilde : e) : kAffineNeg;
-      int leftH = __shfl_up(h, 1, G);
-      leftH = k == 0u ? kAffineNeg : leftH;
-      const unsigned source = !inMatrix || h == 0 ? 0u : M == h ? (sub ? 2u : 1u) : F == h ? 3u : 4u;
+      const bool sub = stagedSub(chunk, band, sRead, sText, sAmino, p.amino, q, u, inMatrix);
+      const AffineCell c = affineRow<G>(p, prevH, prevF, sub, inMatrix, kExtend, k);
+      int leftH = __shfl_up(c.h, 1, G);
+      leftH = k == 0u ? kBandNeg : leftH;
+      const unsigned source = !inMatrix || c.h == 0 ? 0u : c.M == c.h ? (sub ? 2u : 1u) : c.F == c.h ? 3u : 4u;
       /* the five ballots, each out of the scalar registers and into the arena at once */
-      const bool bit[5] = {(source & 1u) != 0u, (source & 2u) != 0u, (source & 4u) != 0u, fOpens >= fExtends,
-                           e == leftH - p.open /* e = max(leftH - o - e, E[k - 1] - e) */};
+      const bool bit[5] = {(source & 1u) != 0u, (source & 2u) != 0u, (source & 4u) != 0u, c.fOpens >= c.fExtends,
+                           c.e == leftH - p.open /* e = max(leftH - o - e, E[k - 1] - e) */};
 #pragma unroll
       for (unsigned b = 0; b < 5u; b++) {
         unsigned long long bits = __builtin_amdgcn_ballot_w64(bit[b]) >> groupShift;
         asm volatile("" : "+v"(bits));
         if (k == 0u) storeAffineBits<G>(trace, (unsigned)(i0 + q), b, bits);
       }
-      if (h > bestH) { /* (strictly: the smallest i of the lane's largest H) */
-        bestH = h;
+      if (c.h > bestH) { /* (strictly: the smallest i of the lane's largest H) */
+        bestH = c.h;
         bestI = i0 + q + 1;
       }
-      prevH = h;
-      prevF = inMatrix ? F : kAffineNeg;
+      prevH = c.h;
+      prevF = inMatrix ? c.F : kBandNeg;
     }
   }
-  /* the end cell: the largest H, then the smallest i, then the smallest k.  H < 2^24, i <= 2^16 */
-  unsigned long long key = ((unsigned long long)(unsigned)bestH << 32) | ((unsigned long long)(0x1FFFFu - (unsigned)bestI) << 6) | (63u - k);
-#pragma unroll
-  for (int step = 1; step < G; step <<= 1) {
-    const unsigned otherLow = (unsigned)__shfl_xor((int)(unsigned)key, step, G), otherHigh = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), step, G);
-    const unsigned long long other = ((unsigned long long)otherHigh << 32) | otherLow;
-    key = other > key ? other : key;
-  }
-  const unsigned score = (unsigned)(key >> 32);
+  const AffineEnd end = affineEndCell<G>(bestH, bestI, k);
+  const unsigned score = end.score;
   if (score == 0u) return 0u;
-  int i = (int)(0x1FFFFu - ((unsigned)(key >> 6) & 0x1FFFFu));
-  unsigned at2 = 63u - ((unsigned)key & 63u);
+  int i = (int)end.i;
+  unsigned at2 = end.k;
   a.readEnd = (unsigned)i;
   a.textEnd = (unsigned long long)(lo + (long long)i + (long long)at2);
   __threadfence_block(); /* the rows lane 0 stored are read by every lane of the group */

@@ -3,11 +3,11 @@
  * of every read against the record its chosen slot names, with the walk back that emits the edit script.  The definition is
  * the header's; the host twin and checker is awfm_align.c.
  *
- * The layout is verifyChainsKernel<G>'s (awfm_verify_kernel.h) with a read where that kernel has a slot: a group of G lanes per
- * read (persistent grid over reads), lane k is diagonal lo + k of the band in sequence-local coordinates, the rows go in chunks
- * of kVerifyChunk whose read characters and text characters (at most 64 + 63, cut to [0, L) of the record) the group stages
- * into its own words of LDS through stageBytes -- EVERY LOAD OF TEXT OR READ is an aligned dword that holds a byte the slot
- * owns, and the record is checked against the text's length before anything is read; only aligned reads load text.  Per row a
+ * A group of G lanes per read (persistent grid over reads), lane k is diagonal lo + k of the band in sequence-local coordinates,
+ * the rows go in chunks of kVerifyChunk.  The classification of the slot, the band and the staging of a chunk's read characters
+ * and text characters (at most 64 + 63, cut to [0, L) of the record) into the group's words of LDS are awfm_band_kernel.h's
+ * (classifySlot, readBand, stageChunk) -- EVERY LOAD OF TEXT OR READ is an aligned dword that holds a byte the slot owns, and
+ * the record is checked against the text's length before anything is read; only aligned reads load text.  Per row a
  * lane forms the diagonal and the upper candidate, the horizontal dependency is the min-prefix-scan, and the lane derives the
  * cell's 2-bit code from the three candidates: 0 diagonal with equal letters, 1 diagonal with a substitution, 2 up, 3 left.
  *
@@ -21,7 +21,7 @@
 #ifndef AWFM_ALIGN_KERNEL_H
 #define AWFM_ALIGN_KERNEL_H
 
-#include "awfm_verify_kernel.h"
+#include "awfm_band_kernel.h"
 
 namespace {
 
@@ -86,52 +86,27 @@ __device__ __forceinline__ unsigned alignRead(const DevAlignParams &p, const uns
   if (j == AWFM_CHAINS_NO_SLOT) return AWFM_VERIFY_NONE;
   if (j >= p.slots) return AWFM_VERIFY_MALFORMED;
   const unsigned long long at = r * p.slots + j;
-  const unsigned s = p.in.sequences[at];
-  if (s == AWFM_CANDIDATES_NONE || p.in.chainAnchors[at] == 0u) return AWFM_VERIFY_NONE;
-  const unsigned long long readBegin = p.in.readOffsets[r], readEnd = p.in.readOffsets[r + 1ull];
-  if (readBegin > readEnd || readEnd > p.in.numReadChars) return AWFM_VERIFY_MALFORMED;
-  const unsigned long long rb = p.in.chainReadBegins[at], re = p.in.chainReadEnds[at], n64 = readEnd - readBegin;
-  if (rb > re || re > n64) return AWFM_VERIFY_MALFORMED;
-  if (s >= (p.numRecords ? p.numRecords : 1u)) return AWFM_VERIFY_MALFORMED;
-  const unsigned long long S = p.numRecords && s ? p.ends[s - 1u] + 1ull : 0ull, E = p.numRecords ? p.ends[s] : p.length;
-  if (E < S || E > p.length) return AWFM_VERIFY_MALFORMED;
-  const long long bD = p.in.chainBeginDiagonals[at], eD = p.in.chainEndDiagonals[at];
-  /* E - S < 2^62 and rb, re < 2^32: a diagonal outside [-2^33, 2^62] makes tb < 0, tb > te or te > E - S whatever the other is,
-   * and inside it the sums are exact in 64 bits */
-  if (bD < -(1ll << 33) || eD < -(1ll << 33) || bD > (1ll << 62) || eD > (1ll << 62)) return AWFM_VERIFY_MALFORMED;
-  const long long tb = (long long)rb + bD, te = (long long)re + eD, L = (long long)(E - S);
-  if (tb < 0 || tb > te || te > L) return AWFM_VERIFY_MALFORMED;
-  const long long delta = eD - bD;
-  if (delta > (long long)p.drift || delta < -(long long)p.drift) return AWFM_VERIFY_TOO_WIDE;
+  const unsigned long long readBegin = p.in.readOffsets[r], readEnd = p.in.readOffsets[r + 1ull], n64 = readEnd - readBegin;
+  SlotBand b;
+  const unsigned status = classifySlot(p, at, p.in.sequences[at], n64, readBegin <= readEnd && readEnd <= p.in.numReadChars, b);
+  if (status != kSlotHasBand) return status;
   if (n64 > (unsigned long long)p.maxRows) return AWFM_VERIFY_TOO_LONG;
   const int n = (int)n64; /* <= 2^16 */
-  const long long lo = (bD < eD ? bD : eD) - (long long)p.pad, hi = (bD > eD ? bD : eD) + (long long)p.pad;
-  if (hi < 0 || lo + (long long)n > L) return AWFM_ALIGN_OVERHANG;
-  /* columns counted from lo: lane k's cell of row i is u = i + k, t = lo + u; it exists for uMin <= u <= uMax inside the band.
-   * lo >= -63 here (hi >= 0 and the band holds at most 64 diagonals), and what lies beyond 2^30 is beyond every row */
-  const int width = (int)(hi - lo) + 1;
-  const int uMin = lo < 0 ? (int)-lo : 0, uMax = L - lo < (1ll << 30) ? (int)(L - lo) : 1 << 30;
-  const int uOne = lo < 1 ? (int)(1 - lo) : 0; /* t >= 1 from here on: the cell has a diagonal predecessor */
-  const bool inBand = (int)k < width;
-  const unsigned char *R = p.in.readChars + readBegin, *T = p.text + S;
-  const unsigned char *sReadBytes = (const unsigned char *)sRead, *sTextBytes = (const unsigned char *)sText;
-  const unsigned proper = p.amino ? 20u : 4u;
+  const ReadBand band = readBand(b, p.pad);
+  const long long lo = band.lo;
+  if (band.hi < 0 || lo + (long long)n > b.L) return AWFM_ALIGN_OVERHANG;
+  /* lo >= -63 here: hi >= 0 and the band holds at most 64 diagonals */
+  const int uMin = band.uMin, uMax = band.uMax;
+  const bool inBand = (int)k < band.width;
+  const unsigned char *R = p.in.readChars + readBegin, *T = p.text + b.S;
   int prev = inBand && (int)k >= uMin && (int)k <= uMax ? 0 : kVerifyInf; /* row 0: H(0, t) = 0 */
   for (int i0 = 0; i0 < n; i0 += (int)kVerifyChunk) {
     const int rows = n - i0 < (int)kVerifyChunk ? n - i0 : (int)kVerifyChunk;
-    /* the text characters T[t - 1] of the chunk's rows i0 + 1 .. i0 + rows: u - 1 = i0 .. i0 + rows + width - 2, cut to the record */
-    const int uFrom = i0 > uMin ? i0 : uMin, uTo = i0 + rows + width - 1 < uMax ? i0 + rows + width - 1 : uMax;
-    __builtin_amdgcn_wave_barrier(); /* (the rows of the chunk before have read their bytes) */
-    const unsigned rOff = stageBytes<G>(R, (unsigned long long)i0, (unsigned long long)(i0 + rows), sRead, k);
-    const unsigned tOff = uTo > uFrom ? stageBytes<G>(T, (unsigned long long)(lo + uFrom), (unsigned long long)(lo + uTo), sText, k) : 0u;
-    __builtin_amdgcn_wave_barrier();
+    const StagedChunk chunk = stageChunk<G>(R, T, band, i0, rows, sRead, sText, k);
     for (int q = 0; q < rows; q++) {
       const int u = i0 + q + 1 + (int)k;
       const bool inMatrix = inBand && u >= uMin && u <= uMax;
-      const unsigned rLetter = verifyLetter(sAmino, p.amino, sReadBytes[rOff + (unsigned)q]);
-      unsigned tLetter = 0xFFu;
-      if (inMatrix && u >= uOne) tLetter = verifyLetter(sAmino, p.amino, sTextBytes[tOff + (unsigned)(u - 1 - uFrom)]);
-      const int sub = rLetter == tLetter && rLetter < proper ? 0 : 1;
+      const int sub = stagedSub(chunk, band, sRead, sText, sAmino, p.amino, q, u, inMatrix) ? 1 : 0;
       int up = __shfl_down(prev, 1, G);
       up = k == (unsigned)(G - 1) ? kVerifyInf : up;
       const int diagonal = prev + sub;

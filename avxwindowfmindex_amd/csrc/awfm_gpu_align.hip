@@ -28,35 +28,22 @@ enum AwFmReturnCode awfmGpuAlignChains(AwFmGpuIndex *g, const struct AwFmVerifyI
     return AwFmNullPtrError;
   }
   if (numReads == 0) return AwFmSuccess;
-  if (!dIn || !dOut || !dSlots || !dScratch || !dIn->readOffsets || !dIn->sequences || !dIn->chainAnchors || !dIn->chainReadBegins ||
-      !dIn->chainReadEnds || !dIn->chainBeginDiagonals || !dIn->chainEndDiagonals || (!dIn->readChars && dIn->numReadChars != 0)) {
-    setError("awfmGpuAlignChains: null argument");
-    return AwFmNullPtrError;
-  }
-  if (numReads >= (1ull << 32) || maxCandidates < 1 || maxCandidates > AWFM_CANDIDATES_MAX_SLOTS) {
-    setError("awfmGpuAlignChains: read numbers are 32-bit, and a read has 1 to 16 slots");
-    return AwFmIllegalPositionError;
-  }
+  const char *name = "awfmGpuAlignChains";
   const uint64_t band = (uint64_t)maxDrift + 2ull * bandPad + 1ull;
-  if (band > AWFM_VERIFY_MAX_BAND) {
-    setError("awfmGpuAlignChains: the band, maxDrift + 2 bandPad + 1 diagonals, holds 64 at the most");
-    return AwFmIllegalPositionError;
-  }
+  enum AwFmReturnCode rc = chainArgumentsRefused(name, dIn, dOut && dSlots && dScratch, numReads, maxCandidates, band);
+  if (rc != AwFmSuccess) return rc;
   if (maxOps < 1 || maxOps > AWFM_ALIGN_MAX_OPS || maxRows < 1 || maxRows > AWFM_ALIGN_MAX_LENGTH) {
-    setError("awfmGpuAlignChains: maxOps is 1 to 4096 and maxRows 1 to 65536");
+    setCallError(name, "maxOps is 1 to 4096 and maxRows 1 to 65536");
     return AwFmIllegalPositionError;
   }
   if ((uintptr_t)dScratch & 15u) {
-    setError("awfmGpuAlignChains: the scratch is aligned to 16 bytes");
+    setCallError(name, "the scratch is aligned to 16 bytes");
     return AwFmIllegalPositionError;
   }
   DeviceGuard guard(g->device);
   AwFmGpuImage *image = g->image;
   std::shared_lock<std::shared_mutex> lock(image->recordMutex); /* neither text nor record table is replaced before the launch */
-  if (!image->dText) {
-    setError("awfmGpuAlignChains: the image has no text (awfmGpuIndexSetText uploads it)");
-    return AwFmUnsupportedVersionError;
-  }
+  if ((rc = textMissing(name, image)) != AwFmSuccess) return rc;
   DevAlignParams p{};
   p.in = *dIn;
   p.out = *dOut;
@@ -73,19 +60,12 @@ enum AwFmReturnCode awfmGpuAlignChains(AwFmGpuIndex *g, const struct AwFmVerifyI
   p.amino = g->amino ? 1u : 0u;
   p.maxOps = maxOps;
   p.maxRows = maxRows;
-  unsigned group = band <= 16u ? 16u : band <= 32u ? 32u : 64u;
-  if (const char *env = awfmGpuDiag("align_group")) { /* tests: more lanes per read than the band needs */
-    const unsigned forced = (unsigned)atoi(env);
-    if ((forced == 32u || forced == 64u) && forced > group) group = forced;
-  }
+  const unsigned group = bandGroup(band, "align_group");
   /* persistent grid over reads, a group each: never more waves than the arena has room for */
   const uint64_t perBlock = (uint64_t)(kAlignThreads / group), blocks = (numReads + perBlock - 1u) / perBlock;
   const uint64_t resident = alignGridWaves(g) / (kAlignThreads / 64u);
   const dim3 grid((unsigned)(blocks < resident ? blocks : resident)), block(kAlignThreads);
-  hipStream_t s = (hipStream_t)stream;
-  if (group == 16u) hipLaunchKernelGGL(alignChainsKernel<16>, grid, block, 0, s, p);
-  else if (group == 32u) hipLaunchKernelGGL(alignChainsKernel<32>, grid, block, 0, s, p);
-  else hipLaunchKernelGGL(alignChainsKernel<64>, grid, block, 0, s, p);
+  AWFM_LAUNCH_BAND_KERNEL(alignChainsKernel, group, grid, block, stream, p);
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
   return AwFmSuccess;
 }

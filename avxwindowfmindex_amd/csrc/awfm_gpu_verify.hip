@@ -93,10 +93,7 @@ enum AwFmReturnCode awfmGpuTextWindows(AwFmGpuIndex *g, const uint64_t *dPositio
   DeviceGuard guard(g->device);
   AwFmGpuImage *image = g->image;
   std::shared_lock<std::shared_mutex> lock(image->recordMutex); /* the text is not replaced between reading its view and the launch */
-  if (!image->dText) {
-    setError("awfmGpuTextWindows: the image has no text (awfmGpuIndexSetText uploads it)");
-    return AwFmUnsupportedVersionError;
-  }
+  if (textMissing("awfmGpuTextWindows", image) != AwFmSuccess) return AwFmUnsupportedVersionError;
   if (capacity == 0) return AwFmSuccess;
   /* the grid from the capacity (a thread per output dword), trimmed by the count on the device */
   const uint64_t blocks = (capacity * width / 4u + 2u + kWindowThreads - 1u) / kWindowThreads, resident = (uint64_t)g->numCUs * 8u;
@@ -115,27 +112,14 @@ enum AwFmReturnCode awfmGpuVerifyChains(AwFmGpuIndex *g, const struct AwFmVerify
     return AwFmNullPtrError;
   }
   if (numReads == 0) return AwFmSuccess;
-  if (!dIn || !dOut || !dIn->readOffsets || !dIn->sequences || !dIn->chainAnchors || !dIn->chainReadBegins || !dIn->chainReadEnds ||
-      !dIn->chainBeginDiagonals || !dIn->chainEndDiagonals || (!dIn->readChars && dIn->numReadChars != 0)) {
-    setError("awfmGpuVerifyChains: null argument");
-    return AwFmNullPtrError;
-  }
-  if (numReads >= (1ull << 32) || maxCandidates < 1 || maxCandidates > AWFM_CANDIDATES_MAX_SLOTS) {
-    setError("awfmGpuVerifyChains: read numbers are 32-bit, and a read has 1 to 16 slots");
-    return AwFmIllegalPositionError;
-  }
+  const char *name = "awfmGpuVerifyChains";
   const uint64_t band = (uint64_t)maxDrift + 2ull * bandPad + 1ull;
-  if (band > AWFM_VERIFY_MAX_BAND) {
-    setError("awfmGpuVerifyChains: the band, maxDrift + 2 bandPad + 1 diagonals, holds 64 at the most");
-    return AwFmIllegalPositionError;
-  }
+  enum AwFmReturnCode rc = chainArgumentsRefused(name, dIn, dOut != nullptr, numReads, maxCandidates, band);
+  if (rc != AwFmSuccess) return rc;
   DeviceGuard guard(g->device);
   AwFmGpuImage *image = g->image;
   std::shared_lock<std::shared_mutex> lock(image->recordMutex); /* neither text nor record table is replaced before the launch */
-  if (!image->dText) {
-    setError("awfmGpuVerifyChains: the image has no text (awfmGpuIndexSetText uploads it)");
-    return AwFmUnsupportedVersionError;
-  }
+  if ((rc = textMissing(name, image)) != AwFmSuccess) return rc;
   DevVerifyParams p{};
   p.in = *dIn;
   p.out = *dOut;
@@ -148,18 +132,11 @@ enum AwFmReturnCode awfmGpuVerifyChains(AwFmGpuIndex *g, const struct AwFmVerify
   p.pad = bandPad;
   p.drift = maxDrift;
   p.amino = g->amino ? 1u : 0u;
-  unsigned group = band <= 16u ? 16u : band <= 32u ? 32u : 64u;
-  if (const char *env = awfmGpuDiag("verify_group")) { /* tests: more lanes per slot than the band needs */
-    const unsigned forced = (unsigned)atoi(env);
-    if ((forced == 32u || forced == 64u) && forced > group) group = forced;
-  }
+  const unsigned group = bandGroup(band, "verify_group");
   /* persistent grid over reads, a wave each: the six workgroups of four waves per CU that the kernel's registers leave room for */
   const uint64_t waves = kVerifyThreads / 64u, blocks = (numReads + waves - 1u) / waves, resident = (uint64_t)g->numCUs * kVerifyBlocksPerCU;
   const dim3 grid((unsigned)(blocks < resident ? blocks : resident)), block(kVerifyThreads);
-  hipStream_t s = (hipStream_t)stream;
-  if (group == 16u) hipLaunchKernelGGL(verifyChainsKernel<16>, grid, block, 0, s, p);
-  else if (group == 32u) hipLaunchKernelGGL(verifyChainsKernel<32>, grid, block, 0, s, p);
-  else hipLaunchKernelGGL(verifyChainsKernel<64>, grid, block, 0, s, p);
+  AWFM_LAUNCH_BAND_KERNEL(verifyChainsKernel, group, grid, block, stream, p);
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
   return AwFmSuccess;
 }

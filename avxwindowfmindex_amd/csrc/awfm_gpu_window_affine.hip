@@ -43,11 +43,7 @@ enum AwFmReturnCode awfmGpuScoreWindowsAffine(AwFmGpuIndex *g, const struct AwFm
     setError("awfmGpuScoreWindowsAffine: maxLength is 1 to 4096, and the scratch is aligned to 16 bytes");
     return AwFmIllegalPositionError;
   }
-  if (scoring->match < 1 || scoring->match > 255 || scoring->mismatch > 255 || scoring->gapOpen > 255 || scoring->gapExtend < 1 ||
-      scoring->gapExtend > 255) {
-    setError("awfmGpuScoreWindowsAffine: match and gapExtend are 1 to 255, mismatch and gapOpen 0 to 255");
-    return AwFmIllegalPositionError;
-  }
+  if (scoringRefused("awfmGpuScoreWindowsAffine", scoring) != AwFmSuccess) return AwFmIllegalPositionError;
   DeviceGuard guard(g->device);
   AwFmGpuImage *image = g->image;
   std::shared_lock<std::shared_mutex> lock(image->recordMutex); /* neither text nor record table is replaced before the launch */

@@ -1,19 +1,16 @@
 /*
  * awfm_score_affine.c -- awfmScoreChainsAffine (include/awfm_gpu.h, "slot scores and mapping quality"): the banded local affine
  * score and end cell of EVERY slot of every read, and per read the best slot, the runner-up and a mapping quality.  The host twin
- * of awfmGpuScoreChainsAffine and its checker: a read at a time, the recurrence of "affine alignment" as the header states it with
- * three rows of at most 64 cells, no trace table and no walk; then the per-read rules, written plainly over the read's C results.
+ * of awfmGpuScoreChainsAffine and its checker: a read at a time, the classification of a slot and the rows of "affine alignment"
+ * from awfm_band.h, without a trace table and without the walk; then the per-read rules, written plainly over the read's C results.
  * A slot gets what awfmAlignChainsAffine (awfm_align_affine.c) puts into scores, readEnds and textEnds when slots[r] names it:
- * tests/test_score_chains.py holds the two files to that.  Exact and readable rather than fast.  The reference has no analogue
+ * both files call the same rows, and tests/test_score_chains.py checks it.  Exact and readable rather than fast.  The reference has no analogue
  * (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
  */
 #include <stdlib.h>
 #include <string.h>
 
-#include "awfm_gpu.h"
-#include "awfm_internal.h"
-
-#define AWFM_SCORE_NEG INT32_MIN /* minus infinity: awfmScoreMinus keeps it what it is */
+#include "awfm_band.h"
 
 struct awfmScoreCtx {
   const struct AwFmVerifyInputs *in;
@@ -21,9 +18,8 @@ struct awfmScoreCtx {
   const uint8_t *text;
   const uint64_t *ends;
   uint64_t length, numRecords;
-  uint32_t slots, pad, drift, proper, minScore, cap;
-  int32_t match, mismatch, open, extend;
-  int amino;
+  uint32_t slots, pad, drift, minScore, cap;
+  struct awfmAffineCosts costs;
   uint64_t unscored[64], mapped[64]; /* per thread of the loop */
 };
 
@@ -32,104 +28,29 @@ struct awfmSlotScore {
   uint64_t textEnd;
 };
 
-static uint32_t awfmScoreSub(const struct awfmScoreCtx *c, uint8_t a, uint8_t b) {
-  const uint8_t x = c->amino ? awfmAminoAsciiToIndex(a) : awfmNucAsciiToIndex(a);
-  const uint8_t y = c->amino ? awfmAminoAsciiToIndex(b) : awfmNucAsciiToIndex(b);
-  return x == y && x < c->proper ? 0u : 1u;
-}
-
-static int32_t awfmScoreMinus(int32_t value, int32_t cost) { return value == AWFM_SCORE_NEG ? AWFM_SCORE_NEG : value - cost; }
-static int32_t awfmScoreMax(int32_t a, int32_t b) { return a > b ? a : b; }
-
-/* R[0 .. n) against the record T[0 .. L) inside the diagonals [lo, hi] (hi - lo + 1 <= 64, anywhere relative to the record): the
- * largest H over existing cells with i >= 1, then the smallest i, then the smallest t; a score of 0 comes with zeros */
-static void awfmScoreRead(const struct awfmScoreCtx *c, const uint8_t *R, int64_t n, const uint8_t *T, int64_t L, int64_t lo, int64_t hi,
-                          struct awfmSlotScore *a) {
-  int32_t rowsH[2][AWFM_VERIFY_MAX_BAND], rowsF[2][AWFM_VERIFY_MAX_BAND], E[AWFM_VERIFY_MAX_BAND];
-  const int64_t width = hi - lo + 1;
-  a->value = 0;
-  a->readEnd = 0;
-  a->textEnd = 0;
-  if (n == 0 || n + hi < 0 || lo + 1 > L) return; /* no existing cell with i >= 1: nothing is read */
-  int32_t *prevH = rowsH[0], *curH = rowsH[1], *prevF = rowsF[0], *curF = rowsF[1];
-  const int32_t open = c->open + c->extend, extend = c->extend;
-  for (int64_t k = 0; k < width; k++) { /* row 0 */
-    const int64_t t = lo + k;
-    prevH[k] = t >= 0 && t <= L ? 0 : AWFM_SCORE_NEG;
-    prevF[k] = AWFM_SCORE_NEG;
-  }
-  int32_t best = 0;
-  int64_t bestI = 0, bestK = 0;
-  for (int64_t i = 1; i <= n; i++) {
-    for (int64_t k = 0; k < width; k++) {
-      const int64_t t = i + lo + k;
-      curH[k] = curF[k] = E[k] = AWFM_SCORE_NEG;
-      if (t < 0 || t > L) continue;
-      /* (i-1, t-1) lies on the same diagonal, (i-1, t) on the next one up, (i, t-1) on the one below */
-      const int32_t M = t >= 1 ? awfmScoreMinus(prevH[k], awfmScoreSub(c, R[i - 1], T[t - 1]) ? c->mismatch : -c->match) : AWFM_SCORE_NEG;
-      const int32_t F = awfmScoreMax(awfmScoreMinus(k + 1 < width ? prevH[k + 1] : AWFM_SCORE_NEG, open),
-                                     awfmScoreMinus(k + 1 < width ? prevF[k + 1] : AWFM_SCORE_NEG, extend));
-      const int32_t e = awfmScoreMax(awfmScoreMinus(k >= 1 ? curH[k - 1] : AWFM_SCORE_NEG, open),
-                                     awfmScoreMinus(k >= 1 ? E[k - 1] : AWFM_SCORE_NEG, extend));
-      const int32_t H = awfmScoreMax(awfmScoreMax(0, M), awfmScoreMax(F, e));
-      curH[k] = H;
-      curF[k] = F;
-      E[k] = e;
-      if (H > best) { /* rows in ascending order, then columns: the smallest i, then the smallest t of the largest H */
-        best = H;
-        bestI = i;
-        bestK = k;
-      }
-    }
-    int32_t *swap = prevH;
-    prevH = curH;
-    curH = swap;
-    swap = prevF;
-    prevF = curF;
-    curF = swap;
-  }
-  if (best == 0) return;
-  a->value = (uint32_t)best;
-  a->readEnd = (uint32_t)bestI;
-  a->textEnd = (uint64_t)(bestI + lo + bestK);
-}
-
-/* slot j of read r: the order of the checks is awfmAlignChainsAffine's with slots[r] = j < C */
+/* slot j of read r: a status, or the score and end cell of the rows of "affine alignment"; a score of 0 comes with zeros */
 static void awfmScoreSlot(const struct awfmScoreCtx *c, uint64_t r, uint32_t j, struct awfmSlotScore *a) {
   const struct AwFmVerifyInputs *in = c->in;
   const uint64_t at = r * c->slots + j;
-  const uint32_t s = in->sequences[at];
+  const uint64_t readBegin = in->readOffsets[r], readEnd = in->readOffsets[r + 1], n = readEnd - readBegin;
+  struct awfmSlotBand b;
   a->readEnd = 0;
   a->textEnd = 0;
-  a->sequence = s;
-  a->value = AWFM_VERIFY_MALFORMED;
-  if (s == AWFM_CANDIDATES_NONE || in->chainAnchors[at] == 0) {
-    a->value = AWFM_VERIFY_NONE;
-    return;
-  }
-  const uint64_t readBegin = in->readOffsets[r], readEnd = in->readOffsets[r + 1];
-  if (readBegin > readEnd || readEnd > in->numReadChars) return;
-  const uint64_t rb = in->chainReadBegins[at], re = in->chainReadEnds[at], n = readEnd - readBegin;
-  if (rb > re || re > n) return;
-  if (s >= (c->numRecords ? c->numRecords : 1u)) return;
-  const uint64_t S = c->numRecords && s ? c->ends[s - 1] + 1u : 0u, E = c->numRecords ? c->ends[s] : c->length;
-  if (c->numRecords && s && S == 0) return; /* (an end of 2^64 - 1) */
-  if (E < S || E > c->length) return;
-  const int64_t bD = in->chainBeginDiagonals[at], eD = in->chainEndDiagonals[at];
-  const __int128 tb = (__int128)rb + bD, te = (__int128)re + eD;
-  if (tb < 0 || tb > te || te > (__int128)(E - S)) return;
-  /* 0 <= tb <= te <= L < 2^63 and rb, re < 2^32: both diagonals lie in (-2^32, 2^63) and their difference is exact */
-  const __int128 delta = (__int128)eD - bD;
-  if (delta > (__int128)c->drift || delta < -(__int128)c->drift) {
-    a->value = AWFM_VERIFY_TOO_WIDE;
-    return;
-  }
+  a->sequence = in->sequences[at];
+  a->value = awfmClassifySlot(in, c->ends, c->numRecords, c->length, c->drift, at, n, readBegin <= readEnd && readEnd <= in->numReadChars, &b);
+  if (a->value != AWFM_SLOT_HAS_BAND) return;
   if (n > AWFM_ALIGN_MAX_LENGTH) {
     a->value = AWFM_VERIFY_TOO_LONG;
     return;
   }
-  const __int128 lo = (bD < eD ? bD : eD) - (__int128)c->pad, hi = (bD > eD ? bD : eD) + (__int128)c->pad;
-  awfmScoreRead(c, in->readChars + readBegin, (int64_t)n, c->text + S, (int64_t)(E - S), (int64_t)lo, (int64_t)hi, a);
+  const __int128 lo = (b.bD < b.eD ? b.bD : b.eD) - (__int128)c->pad, hi = (b.bD > b.eD ? b.bD : b.eD) + (__int128)c->pad;
+  a->value = 0;
+  if (awfmAffineNoCell((int64_t)n, b.L, (int64_t)lo, (int64_t)hi)) return;
+  const struct awfmAffineEnd end = awfmAffineRows(&c->costs, in->readChars + readBegin, (int64_t)n, c->text + b.S, b.L, (int64_t)lo, (int64_t)hi, NULL);
+  if (end.score == 0) return;
+  a->value = (uint32_t)end.score;
+  a->readEnd = (uint32_t)end.i;
+  a->textEnd = (uint64_t)(end.i + (int64_t)lo + end.k);
 }
 
 static void awfmScoreRange(void *p, uint64_t begin, uint64_t end, unsigned tid) {
@@ -184,16 +105,11 @@ enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uin
                                           const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
                                           enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
-  if (!in || !out || !scoring || !in->readOffsets || !in->sequences || !in->chainAnchors || !in->chainReadBegins || !in->chainReadEnds ||
-      !in->chainBeginDiagonals || !in->chainEndDiagonals)
-    return AwFmNullPtrError;
-  if ((!in->readChars && in->numReadChars != 0) || (!text && length != 0) || (!sequenceEnds && numRecords != 0)) return AwFmNullPtrError;
-  if (numReads >= (1ull << 32) || maxCandidates < 1 || maxCandidates > AWFM_CANDIDATES_MAX_SLOTS) return AwFmIllegalPositionError;
-  if ((uint64_t)maxDrift + 2ull * bandPad + 1ull > AWFM_VERIFY_MAX_BAND) return AwFmIllegalPositionError;
+  const enum AwFmReturnCode rc =
+      awfmBandCheckArguments(in, out && scoring, text, length, sequenceEnds, numRecords, numReads, maxCandidates, bandPad, maxDrift);
+  if (rc != AwFmSuccess) return rc;
   if (mapqCap > AWFM_SCORE_MAX_MAPQ) return AwFmIllegalPositionError;
-  if (scoring->match < 1 || scoring->match > 255 || scoring->mismatch > 255 || scoring->gapOpen > 255 || scoring->gapExtend < 1 ||
-      scoring->gapExtend > 255)
-    return AwFmIllegalPositionError;
+  if (!awfmScoringOk(scoring)) return AwFmIllegalPositionError;
   struct awfmScoreCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.in = in;
@@ -207,12 +123,7 @@ enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uin
   ctx.drift = maxDrift;
   ctx.minScore = minScore;
   ctx.cap = mapqCap;
-  ctx.match = (int32_t)scoring->match;
-  ctx.mismatch = (int32_t)scoring->mismatch;
-  ctx.open = (int32_t)scoring->gapOpen;
-  ctx.extend = (int32_t)scoring->gapExtend;
-  ctx.amino = alphabet == AwFmAlphabetAmino;
-  ctx.proper = ctx.amino ? 20u : 4u;
+  ctx.costs = awfmAffineCostsOf(scoring, alphabet);
   awfmParallelFor(threads ? threads : 1, numReads, awfmScoreRange, &ctx);
   uint64_t unscored = 0, mapped = 0;
   for (unsigned t = 0; t < 64; t++) {

@@ -3,17 +3,14 @@
  * the banded local affine score and end cell of every slot of every read, and per read the best slot, the runner-up and the
  * mapping quality.  The definition is the header's; the host twin and checker is awfm_score_affine.c.
  *
- * The layout is verifyChainsKernel<G>'s (awfm_verify_kernel.h): a wave takes a read (persistent grid over reads), its 64 / G
- * groups of G lanes take the read's slots in turn, lane k of a group is diagonal lo + k of the band in sequence-local
- * coordinates.  The rows go in chunks of kVerifyChunk whose read characters and text characters the group stages into its own
- * words of LDS through stageBytes -- EVERY LOAD OF TEXT OR READ is an aligned dword that holds a byte the slot owns, and the
- * record is checked against the text's length before anything is read; a slot with a status or without an existing cell loads
- * no text.  The row is alignChainsAffineKernel's (awfm_align_affine_kernel.h) without its trace: a lane carries H and F of the
- * previous row, M comes from the lane itself, F from lane k + 1, and E is one exclusive max-prefix-scan per row over the group,
- * E[k] = max over k' < k of (H~[k'] + k' e) - o - k e with H~ = max(0, M, F) (a gap that extends from a cell whose H
- * came from E pays o twice and is dominated).  No ballot, no store and no other shuffle per row.  Lanes and rows without a cell
- * carry kScoreNeg.  The end cell -- largest H, then smallest i, then smallest k -- is each lane's own best (strict-greater
- * update) and one butterfly over the group.
+ * A wave takes a read (persistent grid over reads), its 64 / G groups of G lanes take the read's slots in turn, lane k of a
+ * group is diagonal lo + k of the band in sequence-local coordinates, the rows go in chunks of kVerifyChunk.  The classification
+ * of a slot, the band, the staging of a chunk's read and text characters into the group's words of LDS, the row and the end
+ * cell are awfm_band_kernel.h's (classifySlot, readBand, stageChunk, affineRow, affineEndCell), the same calls as in
+ * alignChainsAffineKernel -- EVERY LOAD OF TEXT OR READ is an aligned dword that holds a byte the slot owns, and the record is
+ * checked against the text's length before anything is read; a slot with a status or without an existing cell loads no text.
+ * Of the row this kernel keeps nothing but the call: no ballot, no store and no other shuffle per row.  The end cell -- largest
+ * H, then smallest i, then smallest k -- is each lane's own best (strict-greater update) and one butterfly over the group.
  *
  * THE READ'S RULES.  Lane 0 of a group leaves the slot's value, readEnd, textEnd and sequence in the wave's kScoreSlotWords words
  * of LDS; behind a wave barrier lane j < C holds slot j, stores the three per-slot outputs (one coalesced store each) and
@@ -24,7 +21,7 @@
 #ifndef AWFM_SCORE_AFFINE_KERNEL_H
 #define AWFM_SCORE_AFFINE_KERNEL_H
 
-#include "awfm_verify_kernel.h"
+#include "awfm_band_kernel.h"
 
 namespace {
 
@@ -35,7 +32,6 @@ constexpr unsigned kScoreBlocksPerCU = 7;  /* up to 72 VGPRs: seven waves per SI
 static_assert(kScoreSlotWords == 5u * AWFM_CANDIDATES_MAX_SLOTS, "five words a slot");
 static_assert(kScoreLdsBytes == (kScoreThreads / 16u) * kVerifyGroupWords * 4u + 32u + (kScoreThreads / 64u) * kScoreSlotWords * 4u,
               "the staging words of sixteen groups, the letter table and the slot words of four waves");
-constexpr int kScoreNeg = -0x40000000; /* minus infinity: a lane resets it every row, so it only has to survive o + 64 e */
 
 struct DevScoreParams {
   struct AwFmVerifyInputs in;
@@ -62,93 +58,39 @@ __device__ __forceinline__ unsigned scoreSlot(const ScoreParamsRef p, const unsi
                                               unsigned &endRead, unsigned long long &endText) {
   endRead = 0u;
   endText = 0ull;
-  if (s == AWFM_CANDIDATES_NONE || p->in.chainAnchors[at] == 0u) return AWFM_VERIFY_NONE;
-  if (!readOk) return AWFM_VERIFY_MALFORMED;
-  const unsigned long long rb = p->in.chainReadBegins[at], re = p->in.chainReadEnds[at];
-  if (rb > re || re > n64) return AWFM_VERIFY_MALFORMED;
-  if (s >= (p->numRecords ? p->numRecords : 1u)) return AWFM_VERIFY_MALFORMED;
-  const unsigned long long S = p->numRecords && s ? p->ends[s - 1u] + 1ull : 0ull, E = p->numRecords ? p->ends[s] : p->length;
-  if (E < S || E > p->length) return AWFM_VERIFY_MALFORMED;
-  const long long bD = p->in.chainBeginDiagonals[at], eD = p->in.chainEndDiagonals[at];
-  /* E - S < 2^62 and rb, re < 2^32: a diagonal outside [-2^33, 2^62] makes tb < 0, tb > te or te > E - S whatever the other is,
-   * and inside it the sums are exact in 64 bits */
-  if (bD < -(1ll << 33) || eD < -(1ll << 33) || bD > (1ll << 62) || eD > (1ll << 62)) return AWFM_VERIFY_MALFORMED;
-  const long long tb = (long long)rb + bD, te = (long long)re + eD, L = (long long)(E - S);
-  if (tb < 0 || tb > te || te > L) return AWFM_VERIFY_MALFORMED;
-  const long long delta = eD - bD;
-  if (delta > (long long)p->drift || delta < -(long long)p->drift) return AWFM_VERIFY_TOO_WIDE;
+  SlotBand slot;
+  const unsigned status = classifySlot(*p, at, s, n64, readOk, slot);
+  if (status != kSlotHasBand) return status;
   if (n64 > (unsigned long long)AWFM_ALIGN_MAX_LENGTH) return AWFM_VERIFY_TOO_LONG;
   const int n = (int)n64; /* <= 2^16 */
-  const long long lo = (bD < eD ? bD : eD) - (long long)p->pad, hi = (bD > eD ? bD : eD) + (long long)p->pad;
-  if (n == 0 || (long long)n + hi < 0 || lo + 1 > L) return 0u; /* no existing cell with i >= 1: nothing is aligned, nothing is read */
-  /* columns counted from lo: lane k's cell of row i is u = i + k, t = lo + u; it exists for uMin <= u <= uMax inside the band.
-   * Here -n - 63 <= lo <= L - 1, so uMin <= n + 63 and uMax >= 1; what lies beyond 2^30 is beyond every row */
-  const int width = (int)(hi - lo) + 1;
-  const int uMin = lo < 0 ? (int)-lo : 0, uMax = L - lo < (1ll << 30) ? (int)(L - lo) : 1 << 30;
-  const int uOne = lo < 1 ? (int)(1 - lo) : 0; /* t >= 1 from here on: the cell has a diagonal predecessor */
-  const bool inBand = (int)k < width;
-  const unsigned char *R = p->in.readChars + readBegin, *T = p->text + S;
-  const unsigned char *sReadBytes = (const unsigned char *)sRead, *sTextBytes = (const unsigned char *)sText;
-  const unsigned proper = p->amino ? 20u : 4u;
+  const ReadBand band = readBand(slot, p->pad);
+  if (n == 0 || (long long)n + band.hi < 0 || band.lo + 1 > slot.L) return 0u; /* no existing cell with i >= 1: nothing is aligned, nothing is read */
+  /* here -n - 63 <= lo <= L - 1, so uMin <= n + 63 and uMax >= 1 */
+  const bool inBand = (int)k < band.width;
+  const unsigned char *R = p->in.readChars + readBegin, *T = p->text + slot.S;
   const int kExtend = (int)k * p->extend;
-  int prevH = inBand && (int)k >= uMin && (int)k <= uMax ? 0 : kScoreNeg, prevF = kScoreNeg; /* row 0: H(0, t) = 0 */
+  int prevH = inBand && (int)k >= band.uMin && (int)k <= band.uMax ? 0 : kBandNeg, prevF = kBandNeg; /* row 0: H(0, t) = 0 */
   int bestH = 0, bestI = 0;
   for (int i0 = 0; i0 < n; i0 += (int)kVerifyChunk) {
     const int rows = n - i0 < (int)kVerifyChunk ? n - i0 : (int)kVerifyChunk;
-    /* the text characters T[t - 1] of the chunk's rows i0 + 1 .. i0 + rows: u - 1 = i0 .. i0 + rows + width - 2, cut to the record */
-    const int uFrom = i0 > uMin ? i0 : uMin, uTo = i0 + rows + width - 1 < uMax ? i0 + rows + width - 1 : uMax;
-    __builtin_amdgcn_wave_barrier(); /* (the rows of the chunk before have read their bytes) */
-    const unsigned rOff = stageBytes<G>(R, (unsigned long long)i0, (unsigned long long)(i0 + rows), sRead, k);
-    const unsigned tOff = uTo > uFrom ? stageBytes<G>(T, (unsigned long long)(lo + uFrom), (unsigned long long)(lo + uTo), sText, k) : 0u;
-    __builtin_amdgcn_wave_barrier();
+    const StagedChunk chunk = stageChunk<G>(R, T, band, i0, rows, sRead, sText, k);
     for (int q = 0; q < rows; q++) {
       const int u = i0 + q + 1 + (int)k;
-      const bool inMatrix = inBand && u >= uMin && u <= uMax;
-      const unsigned rLetter = verifyLetter(sAmino, p->amino, sReadBytes[rOff + (unsigned)q]);
-      unsigned tLetter = 0xFFu;
-      if (inMatrix && u >= uOne) tLetter = verifyLetter(sAmino, p->amino, sTextBytes[tOff + (unsigned)(u - 1 - uFrom)]);
-      const bool sub = !(rLetter == tLetter && rLetter < proper);
-      int upH = __shfl_down(prevH, 1, G), upF = __shfl_down(prevF, 1, G);
-      upH = k == (unsigned)(G - 1) ? kScoreNeg : upH;
-      upF = k == (unsigned)(G - 1) ? kScoreNeg : upF;
-      const int M = prevH + (sub ? -p->mismatch : p->match); /* (prevH is kScoreNeg when t = 0) */
-      const int fOpens = upH - p->open, fExtends = upF - p->extend;
-      const int F = fOpens > fExtends ? fOpens : fExtends;
-      int tilde = M > F ? M : F;
-      tilde = tilde > 0 ? tilde : 0;
-      tilde = inMatrix ? tilde : kScoreNeg;
-      /* E[k] + o + k e = max over k' < k of H~[k'] + k' e: shifted by a lane, then the inclusive scan */
-      int v = __shfl_up(tilde + kExtend, 1, G);
-      v = k == 0u ? kScoreNeg : v;
-#pragma unroll
-      for (int step = 1; step < G; step <<= 1) {
-        const int other = __shfl_up(v, step, G);
-        v = (int)k >= step && other > v ? other : v;
-      }
-      const int e = v - (p->open - p->extend) - kExtend;
-      const int h = inMatrix ? (tilde > e ? tilde : e) : kScoreNeg;
-      if (h > bestH) { /* (strictly: the smallest i of the lane's largest H) */
-        bestH = h;
+      const bool inMatrix = inBand && u >= band.uMin && u <= band.uMax;
+      const AffineCell c = affineRow<G>(*p, prevH, prevF, stagedSub(chunk, band, sRead, sText, sAmino, p->amino, q, u, inMatrix), inMatrix, kExtend, k);
+      if (c.h > bestH) { /* (strictly: the smallest i of the lane's largest H) */
+        bestH = c.h;
         bestI = i0 + q + 1;
       }
-      prevH = h;
-      prevF = inMatrix ? F : kScoreNeg;
+      prevH = c.h;
+      prevF = inMatrix ? c.F : kBandNeg;
     }
   }
-  /* the end cell: the largest H, then the smallest i, then the smallest k.  H < 2^24, i <= 2^16 */
-  unsigned long long key = ((unsigned long long)(unsigned)bestH << 32) | ((unsigned long long)(0x1FFFFu - (unsigned)bestI) << 6) | (63u - k);
-#pragma unroll
-  for (int step = 1; step < G; step <<= 1) {
-    const unsigned otherLow = (unsigned)__shfl_xor((int)(unsigned)key, step, G), otherHigh = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), step, G);
-    const unsigned long long other = ((unsigned long long)otherHigh << 32) | otherLow;
-    key = other > key ? other : key;
-  }
-  const unsigned score = (unsigned)(key >> 32);
-  if (score == 0u) return 0u;
-  const unsigned i = 0x1FFFFu - ((unsigned)(key >> 6) & 0x1FFFFu), at2 = 63u - ((unsigned)key & 63u);
-  endRead = i;
-  endText = (unsigned long long)(lo + (long long)i + (long long)at2);
-  return score;
+  const AffineEnd end = affineEndCell<G>(bestH, bestI, k);
+  if (end.score == 0u) return 0u;
+  endRead = end.i;
+  endText = (unsigned long long)(band.lo + (long long)end.i + (long long)end.k);
+  return end.score;
 }
 
 /* the largest key of the wave's first sixteen lanes, in each of them */

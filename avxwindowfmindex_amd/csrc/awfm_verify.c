@@ -2,13 +2,13 @@
  * awfm_verify.c -- awfmTextWindows and awfmVerifyChains (include/awfm_gpu.h, "chain verification"): batched recall of the indexed
  * text, and the banded global edit distance of every chain against the text it names.  The host twins of awfmGpuTextWindows and
  * awfmGpuVerifyChains and their checkers: a read at a time, two rows of at most 64 cells, the recurrence as the header states it.
- * Nothing here is clever.  ref src/AwFmFile.c (awFmReadSequenceFromFile: one segment per call); the reference has no analogue of
+ * Nothing here is clever; the classification of a slot, the letter comparison and the argument checks are awfm_band.h's, shared
+ * with the other twins of the read path.  ref src/AwFmFile.c (awFmReadSequenceFromFile: one segment per call); the reference has no analogue of
  * the verification (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
  */
 #include <string.h>
 
-#include "awfm_gpu.h"
-#include "awfm_internal.h"
+#include "awfm_band.h"
 
 #define AWFM_VERIFY_INF 0x3FFFFFFFu /* a cell outside the matrix */
 
@@ -52,17 +52,10 @@ struct awfmVerifyCtx {
   const uint8_t *text;
   const uint64_t *ends;
   uint64_t length, numRecords;
-  uint32_t slots, pad, drift, proper;
+  uint32_t slots, pad, drift;
   int amino;
   uint64_t unverified[64]; /* per thread of the loop */
 };
-
-/* 0 when both characters map to the same proper letter */
-static uint32_t awfmVerifySub(const struct awfmVerifyCtx *c, uint8_t a, uint8_t b) {
-  const uint8_t x = c->amino ? awfmAminoAsciiToIndex(a) : awfmNucAsciiToIndex(a);
-  const uint8_t y = c->amino ? awfmAminoAsciiToIndex(b) : awfmNucAsciiToIndex(b);
-  return x == y && x < c->proper ? 0u : 1u;
-}
 
 /* H(n, m) of R[0 .. n) against T[0 .. m) inside the band [lo, hi] of diagonals j - i (hi - lo + 1 <= 64) */
 static uint32_t awfmBandedDistance(const struct awfmVerifyCtx *c, const uint8_t *R, int64_t n, const uint8_t *T, int64_t m, int64_t lo,
@@ -80,7 +73,7 @@ static uint32_t awfmBandedDistance(const struct awfmVerifyCtx *c, const uint8_t 
       uint32_t best = AWFM_VERIFY_INF;
       if (j >= 0 && j <= m) {
         /* (i-1, j-1) lies on the same diagonal, (i-1, j) on the next one up, (i, j-1) on the one below */
-        if (j >= 1 && prev[k] != AWFM_VERIFY_INF) best = prev[k] + awfmVerifySub(c, R[i - 1], T[j - 1]);
+        if (j >= 1 && prev[k] != AWFM_VERIFY_INF) best = prev[k] + awfmBandSub(c->amino, R[i - 1], T[j - 1]);
         if (k + 1 < width && prev[k + 1] != AWFM_VERIFY_INF && prev[k + 1] + 1u < best) best = prev[k + 1] + 1u;
         if (k >= 1 && cur[k - 1] != AWFM_VERIFY_INF && cur[k - 1] + 1u < best) best = cur[k - 1] + 1u;
       }
@@ -95,23 +88,16 @@ static uint32_t awfmBandedDistance(const struct awfmVerifyCtx *c, const uint8_t 
 
 static uint32_t awfmVerifySlot(const struct awfmVerifyCtx *c, uint64_t r, uint64_t at) {
   const struct AwFmVerifyInputs *in = c->in;
-  const uint32_t s = in->sequences[at];
-  if (s == AWFM_CANDIDATES_NONE || in->chainAnchors[at] == 0) return AWFM_VERIFY_NONE;
   const uint64_t readBegin = in->readOffsets[r], readEnd = in->readOffsets[r + 1];
-  if (readBegin > readEnd || readEnd > in->numReadChars) return AWFM_VERIFY_MALFORMED;
-  const uint64_t rb = in->chainReadBegins[at], re = in->chainReadEnds[at];
-  if (rb > re || re > readEnd - readBegin) return AWFM_VERIFY_MALFORMED;
-  if (s >= (c->numRecords ? c->numRecords : 1u)) return AWFM_VERIFY_MALFORMED;
-  const uint64_t S = c->numRecords && s ? c->ends[s - 1] + 1u : 0u, E = c->numRecords ? c->ends[s] : c->length;
-  if (c->numRecords && s && S == 0) return AWFM_VERIFY_MALFORMED; /* (an end of 2^64 - 1) */
-  if (E < S || E > c->length) return AWFM_VERIFY_MALFORMED;
-  const __int128 tb = (__int128)rb + in->chainBeginDiagonals[at], te = (__int128)re + in->chainEndDiagonals[at];
-  if (tb < 0 || tb > te || te > (__int128)(E - S)) return AWFM_VERIFY_MALFORMED;
-  const int64_t n = (int64_t)(re - rb), m = (int64_t)(te - tb), delta = m - n; /* m <= length < 2^63, n < 2^32 */
-  if (delta > (int64_t)c->drift || delta < -(int64_t)c->drift) return AWFM_VERIFY_TOO_WIDE;
+  struct awfmSlotBand b;
+  const uint32_t status = awfmClassifySlot(in, c->ends, c->numRecords, c->length, c->drift, at, readEnd - readBegin,
+                                           readBegin <= readEnd && readEnd <= in->numReadChars, &b);
+  if (status != AWFM_SLOT_HAS_BAND) return status;
+  /* the span alone, and the band relative to it: diagonal 0 is the span's first cell, the drift its last one's */
+  const int64_t n = (int64_t)(b.re - b.rb), delta = b.eD - b.bD, m = n + delta;
   if (n > (int64_t)AWFM_VERIFY_MAX_LENGTH) return AWFM_VERIFY_TOO_LONG;
   const int64_t lo = (delta < 0 ? delta : 0) - (int64_t)c->pad, hi = (delta > 0 ? delta : 0) + (int64_t)c->pad;
-  return awfmBandedDistance(c, in->readChars + readBegin + rb, n, c->text + S + (uint64_t)tb, m, lo, hi);
+  return awfmBandedDistance(c, in->readChars + readBegin + b.rb, n, c->text + b.S + (uint64_t)b.tb, m, lo, hi);
 }
 
 static void awfmVerifyRange(void *p, uint64_t begin, uint64_t end, unsigned tid) {
@@ -140,12 +126,8 @@ enum AwFmReturnCode awfmVerifyChains(const struct AwFmVerifyInputs *in, uint64_t
                                      uint64_t numRecords, enum AwFmAlphabetType alphabet, const struct AwFmVerifyOutputs *out,
                                      unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
-  if (!in || !out || !in->readOffsets || !in->sequences || !in->chainAnchors || !in->chainReadBegins || !in->chainReadEnds ||
-      !in->chainBeginDiagonals || !in->chainEndDiagonals)
-    return AwFmNullPtrError;
-  if ((!in->readChars && in->numReadChars != 0) || (!text && length != 0) || (!sequenceEnds && numRecords != 0)) return AwFmNullPtrError;
-  if (numReads >= (1ull << 32) || maxCandidates < 1 || maxCandidates > AWFM_CANDIDATES_MAX_SLOTS) return AwFmIllegalPositionError;
-  if ((uint64_t)maxDrift + 2ull * bandPad + 1ull > AWFM_VERIFY_MAX_BAND) return AwFmIllegalPositionError;
+  const enum AwFmReturnCode rc = awfmBandCheckArguments(in, out != NULL, text, length, sequenceEnds, numRecords, numReads, maxCandidates, bandPad, maxDrift);
+  if (rc != AwFmSuccess) return rc;
   struct awfmVerifyCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.in = in;
@@ -158,7 +140,6 @@ enum AwFmReturnCode awfmVerifyChains(const struct AwFmVerifyInputs *in, uint64_t
   ctx.pad = bandPad;
   ctx.drift = maxDrift;
   ctx.amino = alphabet == AwFmAlphabetAmino;
-  ctx.proper = ctx.amino ? 20u : 4u;
   awfmParallelFor(threads ? threads : 1, numReads, awfmVerifyRange, &ctx);
   uint64_t unverified = 0;
   for (unsigned t = 0; t < 64; t++) unverified += ctx.unverified[t];

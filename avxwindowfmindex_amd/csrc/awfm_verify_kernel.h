@@ -1,16 +1,17 @@
 /*
  * awfm_verify_kernel.h -- the kernels of "chain verification" (include/awfm_gpu.h): textWindowsKernel, the batched recall of the
  * image's text, and verifyChainsKernel<G>, the banded global edit distance of every chain slot against the text it names.  The
- * definition is the header's; the host twin and checker is awfm_verify.c.
+ * definition is the header's; the host twin and checker is awfm_verify.c.  The classification of a slot, the staging and the
+ * letters are awfm_band_kernel.h's.
  *
  * EVERY READ OF THE TEXT AND OF THE READ BUFFER is an aligned dword that holds at least one byte of the interval the slot (or
- * the window) owns: stageBytes and textDwordAt are the only two places that form such an address.  The text's allocation ends
- * on a 16-byte boundary beyond its last byte and begins on one, so such a dword lies inside it; a dword of the read buffer that
- * holds a byte of the buffer lies in that byte's page.
+ * the window) owns: stageBytes (awfm_band_kernel.h) and textDwordAt are the only two places that form such an address.  The
+ * text's allocation ends on a 16-byte boundary beyond its last byte and begins on one, so such a dword lies inside it; a dword
+ * of the read buffer that holds a byte of the buffer lies in that byte's page.
  *
  * verifyChainsKernel<G>: a wave takes a read (persistent grid over reads), its 64 / G groups of G lanes take the read's slots in
  * turn, lane k of a group is diagonal lo + k of the band.  Unused, malformed, too wide and too long slots are classified from
- * the slot arrays and two reads of the record ends and cost no row.  The rows of a slot go in chunks of kVerifyChunk: the
+ * the slot arrays and two reads of the record ends (classifySlot) and cost no row.  The rows of a slot go in chunks of kVerifyChunk: the
  * group stages the chunk's read characters and the text characters its band can touch (at most 64 + 63) into its own words of
  * LDS with aligned dword loads, then runs the rows from LDS bytes -- per row a lane forms t = min(prev[k] + sub, prev[k + 1] + 1)
  * and the horizontal dependency H[k] = min over k' <= k of t[k'] + (k - k') is a min-prefix-scan of t[k'] - k' over the group:
@@ -21,20 +22,14 @@
 #ifndef AWFM_VERIFY_KERNEL_H
 #define AWFM_VERIFY_KERNEL_H
 
-#include "awfm_device.h"
+#include "awfm_band_kernel.h"
 
 namespace {
 
 constexpr unsigned kVerifyThreads = 256;    /* per workgroup: four waves, each with reads of its own */
-constexpr unsigned kVerifyChunk = 64;       /* rows per staging */
-constexpr unsigned kVerifyReadWords = 18;   /* 64 characters at any skew: 17 aligned dwords */
-constexpr unsigned kVerifyTextWords = 34;   /* 64 + 63 characters at any skew: 33 aligned dwords */
-constexpr unsigned kVerifyGroupWords = 52;  /* a group's staging words: read, then text */
-static_assert(kVerifyGroupWords == kVerifyReadWords + kVerifyTextWords, "read words, then text words");
 constexpr unsigned kVerifyLdsBytes = 3360;  /* static LDS at G = 16, the most groups: 16 x 52 words and the amino letter table */
 constexpr unsigned kVerifyBlocksPerCU = 6;  /* up to 80 VGPRs: six waves per SIMD, i.e. six workgroups of four waves per CU */
 static_assert(kVerifyLdsBytes == (kVerifyThreads / 16u) * kVerifyGroupWords * 4u + 32u, "the staging words of sixteen groups and the letter table");
-constexpr int kVerifyInf = 0x3FFFFFFF;
 constexpr unsigned kWindowThreads = 256;
 
 struct DevVerifyParams {
@@ -111,49 +106,22 @@ textWindowsKernel(const unsigned char *__restrict__ text, const unsigned long lo
   }
 }
 
-/* bytes [from, to) of `base`, to > from, to - from <= the words given, into the group's LDS words with aligned dword loads
- * of dwords that hold one of those bytes; returns where byte `from` lies in them */
-template <int G>
-__device__ __forceinline__ unsigned stageBytes(const unsigned char *base, unsigned long long from, unsigned long long to, unsigned *words,
-                                               unsigned k) {
-  const unsigned long long a = (unsigned long long)(base + from), first = a & ~3ull, last = ((unsigned long long)(base + to) + 3ull) & ~3ull;
-  const unsigned count = (unsigned)((last - first) >> 2);
-  const unsigned *src = (const unsigned *)first;
-  for (unsigned w = k; w < count; w += (unsigned)G) words[w] = src[w];
-  return (unsigned)(a - first);
-}
-
-__device__ __forceinline__ unsigned verifyLetter(const unsigned char *sAmino, unsigned amino, unsigned c) {
-  return amino ? (c == '$' ? 21u : (unsigned)sAmino[c & 31u]) : nucLetterIndex(c);
-}
-
 /* the value of slot `at` of read r (header: UNUSED .. TOO LONG, else H(n, m)); every lane of the group returns it */
 template <int G>
 __device__ __forceinline__ unsigned verifySlot(const DevVerifyParams &p, const unsigned long long at, const unsigned long long readBegin,
                                                const unsigned long long readLength, const bool readOk, unsigned *sRead, unsigned *sText,
                                                const unsigned char *sAmino, const unsigned k) {
-  const unsigned s = p.in.sequences[at];
-  if (s == AWFM_CANDIDATES_NONE || p.in.chainAnchors[at] == 0u) return AWFM_VERIFY_NONE;
-  if (!readOk) return AWFM_VERIFY_MALFORMED;
-  const unsigned long long rb = p.in.chainReadBegins[at], re = p.in.chainReadEnds[at];
-  if (rb > re || re > readLength) return AWFM_VERIFY_MALFORMED;
-  if (s >= (p.numRecords ? p.numRecords : 1u)) return AWFM_VERIFY_MALFORMED;
-  const unsigned long long S = p.numRecords && s ? p.ends[s - 1u] + 1ull : 0ull, E = p.numRecords ? p.ends[s] : p.length;
-  if (E < S || E > p.length) return AWFM_VERIFY_MALFORMED;
-  const long long bD = p.in.chainBeginDiagonals[at], eD = p.in.chainEndDiagonals[at];
-  /* E - S < 2^62 and rb, re < 2^32: a diagonal outside [-2^33, 2^62] makes tb < 0, tb > te or te > E - S whatever the other is,
-   * and inside it the sums are exact in 64 bits */
-  if (bD < -(1ll << 33) || eD < -(1ll << 33) || bD > (1ll << 62) || eD > (1ll << 62)) return AWFM_VERIFY_MALFORMED;
-  const long long tb = (long long)rb + bD, te = (long long)re + eD;
-  if (tb < 0 || tb > te || (unsigned long long)te > E - S) return AWFM_VERIFY_MALFORMED;
-  const long long n64 = (long long)(re - rb), delta64 = (te - tb) - n64;
-  if (delta64 > (long long)p.drift || delta64 < -(long long)p.drift) return AWFM_VERIFY_TOO_WIDE;
+  SlotBand b;
+  const unsigned status = classifySlot(p, at, p.in.sequences[at], readLength, readOk, b);
+  if (status != kSlotHasBand) return status;
+  /* the span alone, and the band relative to it: diagonal 0 is the span's first cell, the drift its last one's */
+  const long long n64 = (long long)(b.re - b.rb);
   if (n64 > (long long)AWFM_VERIFY_MAX_LENGTH) return AWFM_VERIFY_TOO_LONG;
-  const int n = (int)n64, delta = (int)delta64, m = n + delta; /* n <= 2^20, |delta| <= 63 */
+  const int n = (int)n64, delta = (int)(b.eD - b.bD), m = n + delta; /* n <= 2^20, |delta| <= 63 */
   const int lo = (delta < 0 ? delta : 0) - (int)p.pad, hi = (delta > 0 ? delta : 0) + (int)p.pad;
   const int d = lo + (int)k;
   const bool inBand = d <= hi;
-  const unsigned char *R = p.in.readChars + readBegin + rb, *T = p.text + S + (unsigned long long)tb;
+  const unsigned char *R = p.in.readChars + readBegin + b.rb, *T = p.text + b.S + (unsigned long long)b.tb;
   const unsigned char *sReadBytes = (const unsigned char *)sRead, *sTextBytes = (const unsigned char *)sText;
   int prev = inBand && d >= 0 && d <= m ? d : kVerifyInf; /* row 0: H(0, j) = j */
   for (int i0 = 0; i0 < n; i0 += (int)kVerifyChunk) {

@@ -8,10 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "awfm_gpu.h"
-#include "awfm_internal.h"
-
-#define AWFM_WINDOW_NEG INT32_MIN /* minus infinity: awfmWindowMinus keeps it what it is */
+#include "awfm_band.h"
 
 struct awfmWindowCtx {
   const struct AwFmWindowInputs *in;
@@ -19,7 +16,7 @@ struct awfmWindowCtx {
   const uint8_t *text;
   const uint64_t *ends;
   uint64_t length, numRecords;
-  uint32_t stride, column, floor, proper;
+  uint32_t stride, column, floor;
   int32_t match, mismatch, open, extend;
   int amino, failed;
   uint64_t unscored[64], found[64]; /* per thread of the loop */
@@ -36,21 +33,13 @@ struct awfmWindowResult {
   uint64_t textBegin, textEnd;        /* window-local until the caller adds b */
 };
 
-static uint32_t awfmWindowSub(const struct awfmWindowCtx *c, uint8_t a, uint8_t b) {
-  const uint8_t x = c->amino ? awfmAminoAsciiToIndex(a) : awfmNucAsciiToIndex(a);
-  const uint8_t y = c->amino ? awfmAminoAsciiToIndex(b) : awfmNucAsciiToIndex(b);
-  return x == y && x < c->proper ? 0u : 1u;
-}
-
-static int32_t awfmWindowMinus(int32_t value, int32_t cost) { return value == AWFM_WINDOW_NEG ? AWFM_WINDOW_NEG : value - cost; }
-
 /* R[0 .. n) against T[0 .. W), every cell: the largest H with i >= 1, then the smallest i, then the smallest t, and its origin */
 static void awfmWindowRead(const struct awfmWindowCtx *c, const uint8_t *R, uint32_t n, const uint8_t *T, uint32_t W,
                            struct awfmWindowCell *prev, struct awfmWindowCell *cur, struct awfmWindowResult *a) {
   const int32_t open = c->open + c->extend, extend = c->extend;
   for (uint32_t t = 0; t <= W; t++) { /* row 0 */
     prev[t].H = 0;
-    prev[t].E = prev[t].F = AWFM_WINDOW_NEG;
+    prev[t].E = prev[t].F = AWFM_BAND_NEG;
     prev[t].hI = 0;
     prev[t].hT = t;
     prev[t].eI = prev[t].eT = prev[t].fI = prev[t].fT = 0;
@@ -60,16 +49,16 @@ static void awfmWindowRead(const struct awfmWindowCtx *c, const uint8_t *R, uint
     for (uint32_t t = 0; t <= W; t++) {
       struct awfmWindowCell *x = &cur[t];
       const struct awfmWindowCell *up = &prev[t];
-      const int32_t M = t >= 1 ? prev[t - 1].H + (awfmWindowSub(c, R[i - 1], T[t - 1]) ? -c->mismatch : c->match) : AWFM_WINDOW_NEG;
-      const int32_t fOpens = up->H - open, fExtends = awfmWindowMinus(up->F, extend);
+      const int32_t M = t >= 1 ? prev[t - 1].H + (awfmBandSub(c->amino, R[i - 1], T[t - 1]) ? -c->mismatch : c->match) : AWFM_BAND_NEG;
+      const int32_t fOpens = up->H - open, fExtends = awfmBandMinus(up->F, extend);
       x->F = fOpens >= fExtends ? fOpens : fExtends;
       x->fI = fOpens >= fExtends ? up->hI : up->fI;
       x->fT = fOpens >= fExtends ? up->hT : up->fT;
-      x->E = AWFM_WINDOW_NEG;
+      x->E = AWFM_BAND_NEG;
       x->eI = x->eT = 0;
       if (t >= 1) {
         const struct awfmWindowCell *left = &cur[t - 1];
-        const int32_t eOpens = left->H - open, eExtends = awfmWindowMinus(left->E, extend);
+        const int32_t eOpens = left->H - open, eExtends = awfmBandMinus(left->E, extend);
         x->E = eOpens >= eExtends ? eOpens : eExtends;
         x->eI = eOpens >= eExtends ? left->hI : left->eI;
         x->eT = eOpens >= eExtends ? left->hT : left->eT;
@@ -124,9 +113,8 @@ static int awfmWindowOne(const struct awfmWindowCtx *c, uint64_t r, struct awfmW
   if (begin > end) return 1;
   const uint64_t readBegin = in->readOffsets[r], readEnd = in->readOffsets[r + 1];
   if (readBegin > readEnd || readEnd > in->numReadChars) return 1;
-  const uint64_t S = c->numRecords && s ? c->ends[s - 1] + 1u : 0u, E = c->numRecords ? c->ends[s] : c->length;
-  if (c->numRecords && s && S == 0) return 1; /* (an end of 2^64 - 1) */
-  if (E < S || E > c->length) return 1;
+  uint64_t S, E;
+  if (!awfmRecordBounds(c->ends, c->numRecords, c->length, s, &S, &E)) return 1;
   const uint64_t L = E - S, b = begin < L ? begin : L, e = end < L ? end : L, W = e - b, n = readEnd - readBegin;
   if (W > AWFM_WINDOW_MAX_WIDTH) {
     a->value = AWFM_VERIFY_TOO_WIDE;
@@ -199,9 +187,7 @@ enum AwFmReturnCode awfmScoreWindowsAffine(const struct AwFmWindowInputs *in, ui
   if ((!in->readChars && in->numReadChars != 0) || (!text && length != 0) || (!sequenceEnds && numRecords != 0)) return AwFmNullPtrError;
   if (numReads >= (1ull << 32) || slotStride < 1 || slotStride > AWFM_CANDIDATES_MAX_SLOTS || slotColumn >= slotStride)
     return AwFmIllegalPositionError;
-  if (scoring->match < 1 || scoring->match > 255 || scoring->mismatch > 255 || scoring->gapOpen > 255 || scoring->gapExtend < 1 ||
-      scoring->gapExtend > 255)
-    return AwFmIllegalPositionError;
+  if (!awfmScoringOk(scoring)) return AwFmIllegalPositionError;
   struct awfmWindowCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.in = in;
@@ -218,7 +204,6 @@ enum AwFmReturnCode awfmScoreWindowsAffine(const struct AwFmWindowInputs *in, ui
   ctx.open = (int32_t)scoring->gapOpen;
   ctx.extend = (int32_t)scoring->gapExtend;
   ctx.amino = alphabet == AwFmAlphabetAmino;
-  ctx.proper = ctx.amino ? 20u : 4u;
   awfmParallelFor(threads ? threads : 1, numReads, awfmWindowRange, &ctx);
   if (ctx.failed) return AwFmAllocationFailure;
   uint64_t unscored = 0, found = 0;

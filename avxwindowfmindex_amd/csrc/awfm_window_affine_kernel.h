@@ -27,7 +27,7 @@
 #ifndef AWFM_WINDOW_AFFINE_KERNEL_H
 #define AWFM_WINDOW_AFFINE_KERNEL_H
 
-#include "awfm_verify_kernel.h"
+#include "awfm_band_kernel.h"
 
 namespace {
 

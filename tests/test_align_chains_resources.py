@@ -6,37 +6,24 @@ registers so that no scalar register spills) and kAlignLdsBytes of static LDS (t
 lanes and the amino letter table: LDS never limits the occupancy).  The grid and the trace arena are sized from the same
 waves per CU."""
 import os
-import re
-import subprocess
+import sys
 
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_metadata_common as km  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "avxwindowfmindex_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 ALIGN_VGPRS = 128
 
 
 @pytest.fixture(scope="module")
-def metadata(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    out = tmp_path_factory.mktemp("isa") / "awfm_gpu_align.s"
-    subprocess.check_call([HIPCC, "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + CSRC, "-Wno-unused-function", "-S", "--cuda-device-only", "-o", str(out),
-                           os.path.join(CSRC, "awfm_gpu_align.hip")], stderr=subprocess.DEVNULL)
-    meta = {}
-    for m in re.finditer(r"- \.agpr_count:.*\n\s+\.args:\n((?:.*\n)*?)\s+\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.max_flat_workgroup_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?"
-                         r"\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n)*?"
-                         r"\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", out.read_text()):
-        meta[m.group(4)] = {"dynamic": "hidden_dynamic_lds_size" in m.group(1), "lds": int(m.group(2)), "threads": int(m.group(3)),
-                            "scratch": int(m.group(5)), "sgpr_spill": int(m.group(6)), "vgpr": int(m.group(7)), "spill": int(m.group(8))}
-    return meta
+def metadata():
+    return km.metadata("awfm_gpu_align.hip")
 
 
 def _constant(name, header="awfm_align_kernel.h"):
-    text = open(os.path.join(CSRC, header)).read()
-    return int(re.search(r"constexpr unsigned " + name + r" = (\d+);", text).group(1))
+    return km.constant(name, header)
 
 
 def test_no_kernel_of_the_unit_spills_or_uses_scratch(metadata):
@@ -52,7 +39,7 @@ def test_alignment_stays_within_the_declared_lds_and_registers(metadata, group):
     threads, lds, per_cu = _constant("kAlignThreads"), _constant("kAlignLdsBytes"), _constant("kAlignBlocksPerCU")
     assert not k["dynamic"] and k["threads"] == threads == 256, k
     assert k["vgpr"] <= ALIGN_VGPRS and 512 // ALIGN_VGPRS * 4 == per_cu * (threads // 64), k  # waves per SIMD x 4 SIMDs = the grid's waves per CU
-    groups, words = threads // group, _constant("kVerifyGroupWords", "awfm_verify_kernel.h")
+    groups, words = threads // group, _constant("kVerifyGroupWords", "awfm_band_kernel.h")
     assert groups * words * 4 <= k["lds"] <= groups * words * 4 + 64 and k["lds"] <= lds, (k, lds)
     assert per_cu * lds <= 160 * 1024
 

@@ -4,37 +4,24 @@ or scalar, or has a private segment; both instantiations of the pairing kernel s
 VGPRs (four waves per SIMD: a workgroup is four waves, four workgroups per CU) and no LDS at all --, the reverse complement within
 64 VGPRs (eight waves per SIMD) and no LDS; and the grids are sized from the constants 4o names."""
 import os
-import re
-import subprocess
+import sys
 
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_metadata_common as km  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "avxwindowfmindex_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 @pytest.fixture(scope="module")
-def metadata(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    out = tmp_path_factory.mktemp("isa") / "awfm_gpu_pair_mates.s"
-    subprocess.check_call([HIPCC, "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + CSRC, "-Wno-unused-function", "-S", "--cuda-device-only", "-o", str(out),
-                           os.path.join(CSRC, "awfm_gpu_pair_mates.hip")], stderr=subprocess.DEVNULL)
-    meta = {}
-    for m in re.finditer(r"- \.agpr_count:\s+(\d+)\n\s+\.args:\n((?:.*\n)*?)\s+\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.max_flat_workgroup_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?"
-                         r"\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n)*?"
-                         r"\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", out.read_text()):
-        meta[m.group(5)] = {"agpr": int(m.group(1)), "dynamic": "hidden_dynamic_lds_size" in m.group(2), "lds": int(m.group(3)),
-                            "threads": int(m.group(4)), "scratch": int(m.group(6)), "sgpr_spill": int(m.group(7)), "vgpr": int(m.group(8)),
-                            "spill": int(m.group(9))}
-    return meta
+def metadata():
+    return km.metadata("awfm_gpu_pair_mates.hip")
 
 
-def _constant(name):
-    text = open(os.path.join(CSRC, "awfm_pair_mates_kernel.h")).read()
-    return int(re.search(r"constexpr unsigned " + name + r" = (\d+);", text).group(1))
+def _constant(name, header="awfm_pair_mates_kernel.h"):
+    return km.constant(name, header)
 
 
 def test_no_kernel_of_the_unit_spills_or_uses_scratch(metadata):

@@ -5,37 +5,24 @@ workgroup is four waves with a read each, six workgroups per CU; the slot arrays
 that no scalar register spills) and kVerifyLdsBytes of static LDS (the staging words of the sixteen groups of 16 lanes and the
 amino letter table: LDS never limits the occupancy); the recall kernel uses no LDS and at most 64 VGPRs."""
 import os
-import re
-import subprocess
+import sys
 
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_metadata_common as km  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "avxwindowfmindex_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 VERIFY_VGPRS, WINDOW_VGPRS = 80, 64
 
 
 @pytest.fixture(scope="module")
-def metadata(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    out = tmp_path_factory.mktemp("isa") / "awfm_gpu_verify.s"
-    subprocess.check_call([HIPCC, "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + CSRC, "-Wno-unused-function", "-S", "--cuda-device-only", "-o", str(out),
-                           os.path.join(CSRC, "awfm_gpu_verify.hip")], stderr=subprocess.DEVNULL)
-    meta = {}
-    for m in re.finditer(r"- \.agpr_count:.*\n\s+\.args:\n((?:.*\n)*?)\s+\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.max_flat_workgroup_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?"
-                         r"\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n)*?"
-                         r"\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", out.read_text()):
-        meta[m.group(4)] = {"dynamic": "hidden_dynamic_lds_size" in m.group(1), "lds": int(m.group(2)), "threads": int(m.group(3)),
-                            "scratch": int(m.group(5)), "sgpr_spill": int(m.group(6)), "vgpr": int(m.group(7)), "spill": int(m.group(8))}
-    return meta
+def metadata():
+    return km.metadata("awfm_gpu_verify.hip")
 
 
-def _constant(name):
-    header = open(os.path.join(CSRC, "awfm_verify_kernel.h")).read()
-    return int(re.search(r"constexpr unsigned " + name + r" = (\d+);", header).group(1))
+def _constant(name, header="awfm_verify_kernel.h"):
+    return km.constant(name, header)
 
 
 def test_no_kernel_of_the_unit_spills_or_uses_scratch(metadata):
@@ -52,7 +39,7 @@ def test_verification_stays_within_the_declared_lds_and_registers(metadata, grou
     assert not k["dynamic"] and k["threads"] == threads == 256, k
     assert k["vgpr"] <= VERIFY_VGPRS and 512 // VERIFY_VGPRS * 4 == per_cu * (threads // 64), k  # waves per SIMD x 4 SIMDs = the grid's waves per CU
     groups = threads // group
-    assert groups * _constant("kVerifyGroupWords") * 4 <= k["lds"] <= groups * _constant("kVerifyGroupWords") * 4 + 64 and k["lds"] <= lds, (k, lds)
+    assert groups * _constant("kVerifyGroupWords", "awfm_band_kernel.h") * 4 <= k["lds"] <= groups * _constant("kVerifyGroupWords", "awfm_band_kernel.h") * 4 + 64 and k["lds"] <= lds, (k, lds)
     assert per_cu * lds <= 160 * 1024
 
 
