@@ -226,7 +226,17 @@ enum AwFmReturnCode awfmGpuCreateIndex(struct AwFmIndex **index, const struct Aw
  * dCounts[numQueries] = range length truncated to u32
  * (ref src/AwFmIndexStruct.c:126-130).  Asynchronous on `stream`; allocates no table: large batches read the image's
  * device-only tables where it has them (the deeper table; the tables per k-mer length once a hits-only mixed-length batch
- * has built them), and scratch of 8 bytes per k-mer in one of the image's two slots. */
+ * has built them), and scratch of 8 bytes per k-mer in one of the image's two slots.
+ *
+ * Which letter a byte is: ref src/AwFmLetter.c over all 256 values (tests/byte_values_common.py states the classes).  An amino
+ * byte that is no letter and no ambiguity letter either (j, o, u, '@', NUL, ...: 90 values of letter index 20 that
+ * awFmLetterIsAmbiguous lets pass) goes through the index's k-mer table as in the reference: its digit 20 carries into the
+ * next digit of the table index (ref src/AwFmKmerTable.c:37-51) and the k-mer starts from the entry that index names.  Where
+ * the index so computed is NOT BELOW THE TABLE'S LENGTH (the seed's leading digits are 19 .. 19, 20) the reference reads past
+ * its table; the product defines the result as the plain letter-by-letter backward search of the whole k-mer (ref
+ * src/AwFmSearch.c:317-358: awFmFindSearchRangeForString), final range included.  The device-only tables are never entered
+ * with such a byte among their characters: those k-mers start from the index's own table.  A byte of the sentinel's letter
+ * index ('$'; nucleotide 0x04 too) in a query is not defined. */
 enum AwFmReturnCode awfmGpuSearch(AwFmGpuIndex *g, const uint8_t *dChars, const uint64_t *dOffsets,
                                   uint32_t fixedLength, uint64_t numQueries, struct AwFmSearchRange *dRanges,
                                   uint32_t *dCounts, void *stream);
