@@ -49,6 +49,7 @@ GPU_SYMBOLS = [
     "awfmScoreChainsAffine", "awfmGpuScoreChainsAffine",
     "awfmScoreWindowsAffine", "awfmGpuScoreWindowsAffineScratchBytes", "awfmGpuScoreWindowsAffine",
     "awfmPairMates", "awfmGpuPairMates", "awfmReverseComplementReads", "awfmGpuReverseComplementReads",
+    "awfmInsertHistogram", "awfmGpuInsertHistogram", "awfmInsertInterval", "awfmGpuInsertInterval", "awfmGpuPairMatesEstimated",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -166,6 +167,18 @@ class AwFmPairOutputs(C.Structure):
                 ("templateLengths", C.c_void_p), ("pairQualities", C.c_void_p), ("mappingQualities", C.c_void_p),
                 ("windowSequences", C.c_void_p), ("windowBegins", C.c_void_p), ("windowEnds", C.c_void_p), ("numProper", C.c_void_p),
                 ("numWindows", C.c_void_p)]
+
+
+class AwFmInsertParams(C.Structure):
+    """struct AwFmInsertParams (include/awfm_gpu.h, "insert size"): the histogram's range, who qualifies, the spread and the fallback"""
+    _fields_ = [("lowTemplate", C.c_int64), ("highTemplate", C.c_int64), ("minScore", C.c_uint32), ("minQuality", C.c_uint32),
+                ("spread", C.c_uint32), ("minSamples", C.c_uint32), ("fallbackMin", C.c_int64), ("fallbackMax", C.c_int64)]
+
+
+class AwFmInsertEstimate(C.Structure):
+    """struct AwFmInsertEstimate (include/awfm_gpu.h): 64 bytes, minInsert and maxInsert first"""
+    _fields_ = [("minInsert", C.c_int64), ("maxInsert", C.c_int64), ("quartiles", C.c_int64 * 3), ("mean", C.c_int64),
+                ("numSamples", C.c_uint64), ("valid", C.c_uint64)]
 
 
 class AwFmIndex(C.Structure):
@@ -346,6 +359,12 @@ def lib():
         "awfmPairMates": (C.c_int, [C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmPairParams), C.POINTER(AwFmPairOutputs), C.c_uint]),
         "awfmGpuPairMates": (C.c_int, [vp, C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmPairParams), C.POINTER(AwFmPairOutputs), vp]),
         "awfmReverseComplementReads": (C.c_int, [vp, u64, vp, u64, C.c_uint32, vp, vp, C.c_uint]),
+        "awfmInsertHistogram": (C.c_int, [C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmInsertParams), vp, vp, vp, C.c_uint]),
+        "awfmGpuInsertHistogram": (C.c_int, [vp, C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmInsertParams), vp, vp, vp, vp]),
+        "awfmInsertInterval": (C.c_int, [vp, C.POINTER(AwFmInsertParams), C.POINTER(AwFmInsertEstimate)]),
+        "awfmGpuInsertInterval": (C.c_int, [vp, vp, C.POINTER(AwFmInsertParams), vp, vp]),
+        "awfmGpuPairMatesEstimated": (C.c_int, [vp, C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmPairParams), vp,
+                                                C.POINTER(AwFmPairOutputs), vp]),
         "awfmGpuReverseComplementReads": (C.c_int, [vp, vp, u64, vp, u64, C.c_uint32, vp, vp, vp]),
         "awfmGpuScoreWindowsAffine": (C.c_int, [vp, C.POINTER(AwFmWindowInputs), u64, C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32,
                                                 C.c_uint32, C.c_uint32, C.POINTER(AwFmWindowOutputs), vp, vp]),

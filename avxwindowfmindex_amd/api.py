@@ -900,6 +900,76 @@ def reverse_complement_reads_host(read_chars, read_offsets, which=COMPLEMENT_ODD
     return out, int(counter[0])
 
 
+INSERT_MAX_BINS, INSERT_MAX_SPREAD = 65536, 16  # AWFM_INSERT_MAX_BINS, AWFM_INSERT_MAX_SPREAD
+INSERT_ESTIMATE_FIELDS = ("minInsert", "maxInsert", "quartiles", "mean", "numSamples", "valid")
+
+
+def insert_params(low_template, high_template, min_score=0, min_quality=0, spread=2, min_samples=16, fallback_min=0, fallback_max=1000):
+    """struct AwFmInsertParams (include/awfm_gpu.h, "insert size"): the histogram's range [low_template, high_template], who
+    qualifies (min_score, min_quality), the interval's spread in interquartile ranges and the fallback interval of a histogram
+    with fewer than min_samples samples"""
+    return _lib.AwFmInsertParams(low_template, high_template, min_score, min_quality, spread, min_samples, fallback_min, fallback_max)
+
+
+def insert_estimate_dict(estimate):
+    """struct AwFmInsertEstimate (or its 64 bytes as an array) -> a dict of Python integers, quartiles a list of three"""
+    if not isinstance(estimate, _lib.AwFmInsertEstimate):
+        estimate = _lib.AwFmInsertEstimate.from_buffer_copy(np.ascontiguousarray(estimate).tobytes())
+    return dict(minInsert=int(estimate.minInsert), maxInsert=int(estimate.maxInsert), quartiles=[int(q) for q in estimate.quartiles],
+                mean=int(estimate.mean), numSamples=int(estimate.numSamples), valid=int(estimate.valid))
+
+
+def insert_histogram_host(read_offsets, slots, params, mapping_qualities=None, histogram=None, samples_before=0, outside_before=0, threads=4,
+                          counters=("numSamples", "numOutside"), max_candidates=None):
+    """awfmInsertHistogram (include/awfm_gpu.h, "insert size"), the host twin: slots as pair_mates_host takes them, params an
+    insert_params(...) -> (histogram uint64[bins], numSamples, numOutside).  The histogram is ADDED TO: `histogram` (None: zeros)
+    is what it holds before the call and is not changed itself; so are the counters, which start from samples_before and
+    outside_before; a counter not named in `counters` is passed as NULL and comes back as None."""
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    n = max(o.size - 1, 0)
+    if n % 2:
+        raise ValueError("pairs are reads 2p and 2p + 1: an even number of reads")
+    arrays = {name: np.ascontiguousarray(slots[name], dtype=dtype) for name, dtype in PAIR_SLOT_INPUTS}
+    shape = arrays["sequences"].shape
+    if len(shape) != 2 or shape[0] != n or any(a.shape != shape for a in arrays.values()):
+        raise ValueError("the slot arrays are shaped (reads, max_candidates)")
+    given = None if mapping_qualities is None else np.ascontiguousarray(mapping_qualities, dtype=np.uint8)
+    if given is not None and given.shape != (n,):
+        raise ValueError("mapping_qualities is shaped (reads,)")
+    bins = max(min(int(params.highTemplate) - int(params.lowTemplate) + 1, INSERT_MAX_BINS), 1)
+    result = np.zeros(bins, np.uint64) if histogram is None else np.array(histogram, dtype=np.uint64)
+    if result.shape != (bins,):
+        raise ValueError("the histogram has highTemplate - lowTemplate + 1 bins")
+    samples, outside = np.array([samples_before], np.uint64), np.array([outside_before], np.uint64)
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else dummy.ctypes.data
+
+    pin = pair_inputs(address(o), *(address(arrays[name]) for name, _ in PAIR_SLOT_INPUTS), 0 if given is None else address(given))
+    rc = _lib.lib().awfmInsertHistogram(C.byref(pin), n // 2, shape[1] if max_candidates is None else max_candidates, C.byref(params),
+                                        result.ctypes.data, samples.ctypes.data if "numSamples" in counters else None,
+                                        outside.ctypes.data if "numOutside" in counters else None, threads)
+    _check("awfmInsertHistogram", rc)
+    return result, int(samples[0]) if "numSamples" in counters else None, int(outside[0]) if "numOutside" in counters else None
+
+
+def insert_interval_host(histogram, params):
+    """awfmInsertInterval (include/awfm_gpu.h, "insert size"), the host twin: the histogram's quartiles -> a dict of minInsert,
+    maxInsert, quartiles (three), mean, numSamples, valid (0: the fallback interval)"""
+    h = np.ascontiguousarray(histogram, dtype=np.uint64)
+    estimate = _lib.AwFmInsertEstimate()
+    _check("awfmInsertInterval", _lib.lib().awfmInsertInterval(h.ctypes.data if h.size else None, C.byref(params), C.byref(estimate)))
+    return insert_estimate_dict(estimate)
+
+
+def estimate_insert_size_host(read_offsets, slots, params, mapping_qualities=None, threads=4):
+    """insert_histogram_host on a histogram of zeros, then insert_interval_host -> the interval's dict with histogram,
+    numOutside added"""
+    histogram, _, outside = insert_histogram_host(read_offsets, slots, params, mapping_qualities=mapping_qualities, threads=threads)
+    return dict(insert_interval_host(histogram, params), histogram=histogram, numOutside=outside)
+
+
 AWFM_EDIT_NONE = 0xFFFFFFFF  # the edit of a record of the unedited query (include/awfm_gpu.h)
 
 
@@ -1192,6 +1262,32 @@ class GpuIndex:
         params = pair_params(min_insert, max_insert, min_score, unpaired_penalty, window_pad, mapq_cap)
         _check("awfmGpuPairMates", _lib.lib().awfmGpuPairMates(self.handle, C.byref(inputs), num_pairs, max_candidates, C.byref(params),
                                                                C.byref(outputs), stream or None))
+
+    # insert size (include/awfm_gpu.h) --------------------------------------
+    def insert_histogram(self, inputs, num_pairs, params, d_histogram, d_num_samples=0, d_num_outside=0, max_candidates=4, stream=0):
+        """awfmGpuInsertHistogram: inputs pair_inputs(...) of device addresses, params insert_params(...); d_histogram, highTemplate -
+        lowTemplate + 1 uint64 counters the caller zeroed, and the two counters (0: NULL) are added to; one launch, asynchronous on
+        `stream`"""
+        _check("awfmGpuInsertHistogram",
+               _lib.lib().awfmGpuInsertHistogram(self.handle, None if inputs is None else C.byref(inputs), num_pairs, max_candidates,
+                                                 None if params is None else C.byref(params), d_histogram or None, d_num_samples or None,
+                                                 d_num_outside or None, stream or None))
+
+    def insert_interval(self, d_histogram, params, d_estimate, stream=0):
+        """awfmGpuInsertInterval: the 64 bytes of struct AwFmInsertEstimate at d_estimate from the histogram's quartiles (or the
+        fallback); one launch of one workgroup, asynchronous on `stream`"""
+        _check("awfmGpuInsertInterval", _lib.lib().awfmGpuInsertInterval(self.handle, d_histogram or None, None if params is None else C.byref(params),
+                                                                        d_estimate or None, stream or None))
+
+    def pair_mates_estimated(self, inputs, num_pairs, outputs, d_estimate, max_candidates=4, min_score=0, unpaired_penalty=0, window_pad=0,
+                             mapq_cap=60, stream=0):
+        """awfmGpuPairMatesEstimated: pair_mates with the interval read on the device from the struct AwFmInsertEstimate at
+        d_estimate, which insert_interval wrote earlier on the stream; an interval that is not usable makes no pair proper and
+        names no window"""
+        params = pair_params(0, 0, min_score, unpaired_penalty, window_pad, mapq_cap)
+        _check("awfmGpuPairMatesEstimated",
+               _lib.lib().awfmGpuPairMatesEstimated(self.handle, C.byref(inputs), num_pairs, max_candidates, C.byref(params), d_estimate or None,
+                                                    C.byref(outputs), stream or None))
 
     def reverse_complement_reads(self, d_read_chars, num_read_chars, d_read_offsets, num_reads, d_out, which=COMPLEMENT_ODD,
                                  d_num_malformed=0, stream=0):

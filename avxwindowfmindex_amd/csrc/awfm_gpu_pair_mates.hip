@@ -1,9 +1,11 @@
 /*
- * awfm_gpu_pair_mates.hip -- "pair mates" on the device (include/awfm_gpu.h): awfmGpuPairMates and awfmGpuReverseComplementReads.
+ * awfm_gpu_pair_mates.hip -- "pair mates" on the device (include/awfm_gpu.h): awfmGpuPairMates and awfmGpuReverseComplementReads, and
+ * awfmGpuPairMatesEstimated of "insert size", the same launch with the interval in device memory.
  * The kernels are awfm_pair_mates_kernel.h, the host twins and checkers awfm_pair_mates.c.  One launch each, no scratch, none of
  * the handle's scratch slots, nothing of the image but its device.
  */
 #include <hip/hip_runtime.h>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -11,24 +13,33 @@
 
 extern "C" {
 
-enum AwFmReturnCode awfmGpuPairMates(AwFmGpuIndex *g, const struct AwFmPairInputs *dIn, uint64_t numPairs, uint32_t maxCandidates,
-                                     const struct AwFmPairParams *params, const struct AwFmPairOutputs *dOut, void *stream) {
+/* awfmGpuPairMates (dEstimate NULL: the interval is params') and awfmGpuPairMatesEstimated (the interval lies in device memory and
+ * the kernel validates it) */
+static enum AwFmReturnCode pairMatesLaunch(const char *name, AwFmGpuIndex *g, const struct AwFmPairInputs *dIn, uint64_t numPairs,
+                                           uint32_t maxCandidates, const struct AwFmPairParams *params, const struct AwFmInsertEstimate *dEstimate,
+                                           bool estimated, const struct AwFmPairOutputs *dOut, void *stream) {
+  char message[160];
   if (!g) {
-    setError("awfmGpuPairMates: null image");
+    snprintf(message, sizeof message, "%s: null image", name);
+    setError(message);
     return AwFmNullPtrError;
   }
   if (numPairs == 0) return AwFmSuccess;
-  if (!dIn || !dOut || !params || !dIn->readOffsets || !dIn->sequences || !dIn->slotScores || !dIn->slotReadEnds || !dIn->slotTextEnds) {
-    setError("awfmGpuPairMates: null argument");
+  if (!dIn || !dOut || !params || (estimated && !dEstimate) || !dIn->readOffsets || !dIn->sequences || !dIn->slotScores || !dIn->slotReadEnds ||
+      !dIn->slotTextEnds) {
+    snprintf(message, sizeof message, "%s: null argument", name);
+    setError(message);
     return AwFmNullPtrError;
   }
   if (numPairs >= (1ull << 31) || maxCandidates < 1 || maxCandidates > AWFM_CANDIDATES_MAX_SLOTS) {
-    setError("awfmGpuPairMates: read numbers are 32-bit, and a read has 1 to 16 slots");
+    snprintf(message, sizeof message, "%s: read numbers are 32-bit, and a read has 1 to 16 slots", name);
+    setError(message);
     return AwFmIllegalPositionError;
   }
-  if (params->minInsert > params->maxInsert || params->minInsert < -AWFM_PAIR_MAX_INSERT || params->maxInsert > AWFM_PAIR_MAX_INSERT ||
+  if ((!estimated && (params->minInsert > params->maxInsert || params->minInsert < -AWFM_PAIR_MAX_INSERT || params->maxInsert > AWFM_PAIR_MAX_INSERT)) ||
       params->mapqCap > AWFM_SCORE_MAX_MAPQ) {
-    setError("awfmGpuPairMates: minInsert <= maxInsert, both within 2^40 of 0, and mapqCap is 0 to 254");
+    snprintf(message, sizeof message, "%s: minInsert <= maxInsert, both within 2^40 of 0, and mapqCap is 0 to 254", name);
+    setError(message);
     return AwFmIllegalPositionError;
   }
   DeviceGuard guard(g->device);
@@ -36,13 +47,14 @@ enum AwFmReturnCode awfmGpuPairMates(AwFmGpuIndex *g, const struct AwFmPairInput
   p.in = *dIn;
   p.out = *dOut;
   p.numPairs = numPairs;
-  p.minInsert = params->minInsert;
-  p.maxInsert = params->maxInsert;
+  p.minInsert = estimated ? 0 : params->minInsert;
+  p.maxInsert = estimated ? 0 : params->maxInsert;
   p.pad = (long long)params->windowPad;
   p.slots = maxCandidates;
   p.floor = params->minScore > 1u ? params->minScore : 1u;
   p.penalty = params->unpairedPenalty;
   p.cap = params->mapqCap;
+  p.estimate = estimated ? dEstimate : nullptr;
   unsigned group = maxCandidates <= 4u ? 16u : 64u;
   if (const char *env = awfmGpuDiag("pair_group")) { /* tests: a wave per pair where sixteen lanes would do */
     if ((unsigned)atoi(env) == 64u) group = 64u;
@@ -56,6 +68,17 @@ enum AwFmReturnCode awfmGpuPairMates(AwFmGpuIndex *g, const struct AwFmPairInput
   else hipLaunchKernelGGL(pairMatesKernel<64>, grid, block, 0, s, p);
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
   return AwFmSuccess;
+}
+
+enum AwFmReturnCode awfmGpuPairMates(AwFmGpuIndex *g, const struct AwFmPairInputs *dIn, uint64_t numPairs, uint32_t maxCandidates,
+                                     const struct AwFmPairParams *params, const struct AwFmPairOutputs *dOut, void *stream) {
+  return pairMatesLaunch("awfmGpuPairMates", g, dIn, numPairs, maxCandidates, params, nullptr, false, dOut, stream);
+}
+
+enum AwFmReturnCode awfmGpuPairMatesEstimated(AwFmGpuIndex *g, const struct AwFmPairInputs *dIn, uint64_t numPairs, uint32_t maxCandidates,
+                                              const struct AwFmPairParams *params, const struct AwFmInsertEstimate *dEstimate,
+                                              const struct AwFmPairOutputs *dOut, void *stream) {
+  return pairMatesLaunch("awfmGpuPairMatesEstimated", g, dIn, numPairs, maxCandidates, params, dEstimate, true, dOut, stream);
 }
 
 enum AwFmReturnCode awfmGpuReverseComplementReads(AwFmGpuIndex *g, const uint8_t *dReadChars, uint64_t numReadChars,

@@ -18,6 +18,11 @@
  * of a group stores the pair's outputs and read A's, lane 1 read B's.  The quality's division is 32-bit whenever every group of
  * the wave has cap * win below 2^32 (a wave-uniform branch; always, for scores the library wrote), else 64-bit.
  *
+ * THE INTERVAL is the launch's, or -- awfmGpuPairMatesEstimated, "insert size" -- the one an earlier kernel of the stream left in
+ * a struct AwFmInsertEstimate: one uniform pointer in the parameters, read once at the top of the kernel together with a uniform
+ * "usable" flag (the host has not seen that interval, so the kernel validates it), which gates "concordant" and the windows.  The
+ * same two instantiations serve both calls.
+ *
  * REVERSE COMPLEMENT.  A wave per read, a lane per ALIGNED word of the output (aligned as an address, so the read's first and
  * last word may be partial and are stored bytewise).  The four source bytes of a word -- the mirrored ones of a selected read,
  * the same ones of a copied read -- lie anywhere: one or two aligned words of the input, each loaded only when it holds a byte of
@@ -41,6 +46,7 @@ struct DevPairParams {
   unsigned long long numPairs;
   long long minInsert, maxInsert, pad;
   unsigned slots, floor, penalty, cap; /* floor: max(minScore, 1) */
+  const struct AwFmInsertEstimate *estimate; /* awfmGpuPairMatesEstimated: the interval lies there; NULL: minInsert, maxInsert above */
 };
 
 struct DevComplementParams {
@@ -86,6 +92,15 @@ __global__ void __launch_bounds__(kPairThreads, 4) pairMatesKernel(const DevPair
   constexpr unsigned kGroupsPerBlock = kPairThreads / (unsigned)G;
   const unsigned lane = threadIdx.x & 63u, k = lane % (unsigned)G, a = k >> 2;
   const unsigned C = p->slots;
+  /* the interval: the launch's, or the one an earlier kernel of the stream left in device memory ("insert size"), which nobody
+   * has validated: one that is not usable makes no pair concordant and names no window (uniform, like the interval itself) */
+  long long minInsert = p->minInsert, maxInsert = p->maxInsert;
+  bool usable = true;
+  if (p->estimate) {
+    minInsert = p->estimate->minInsert;
+    maxInsert = p->estimate->maxInsert;
+    usable = minInsert <= maxInsert && minInsert >= -AWFM_PAIR_MAX_INSERT && maxInsert <= AWFM_PAIR_MAX_INSERT;
+  }
   const unsigned long long stride = (unsigned long long)gridDim.x * kGroupsPerBlock;
   /* every group of a wave makes the same number of trips: the cross-lane moves want the whole wave */
   const unsigned long long waveFirst = (unsigned long long)blockIdx.x * kGroupsPerBlock + (threadIdx.x / 64u) * (64u / (unsigned)G);
@@ -155,7 +170,7 @@ __global__ void __launch_bounds__(kPairThreads, 4) pairMatesKernel(const DevPair
       const long long startB = (long long)((((unsigned long long)textHighB[t] << 32) | textLowB[t]) - endB[t]);
       const long long T = (long long)((unsigned long long)startB + (unsigned long long)nB - (unsigned long long)startA);
       const bool both = countsA && countsB[t];
-      const bool concordant = both && seqA == seqB[t] && p->minInsert <= T && T <= p->maxInsert;
+      const bool concordant = both && usable && seqA == seqB[t] && minInsert <= T && T <= maxInsert;
       unsigned long long value = (unsigned long long)scoreA + scoreB[t];
       bool exists = concordant;
       if (both && !concordant && hasA && hasB && a == bestA && b == bestB) {
@@ -224,17 +239,17 @@ __global__ void __launch_bounds__(kPairThreads, 4) pairMatesKernel(const DevPair
       /* 7: the mate's best slot is the chosen one whenever the pair is not proper */
       unsigned windowSequence = AWFM_CANDIDATES_NONE;
       long long windowBegin = 0, windowEnd = 0;
-      if (!isProper && matePlaced) {
+      if (!isProper && matePlaced && usable) {
         const unsigned long long textEnd = isB ? ((unsigned long long)chosenHighA << 32) | chosenLowA : ((unsigned long long)chosenHighB << 32) | chosenLowB;
         const unsigned long long S = textEnd - (isB ? chosenEndA : chosenEndB);
         windowSequence = isB ? chosenSeqA : chosenSeqB;
         if (isB) {
-          windowBegin = (long long)(S + (unsigned long long)p->minInsert - (unsigned long long)nB - (unsigned long long)p->pad);
-          windowEnd = (long long)(S + (unsigned long long)p->maxInsert + (unsigned long long)p->pad);
+          windowBegin = (long long)(S + (unsigned long long)minInsert - (unsigned long long)nB - (unsigned long long)p->pad);
+          windowEnd = (long long)(S + (unsigned long long)maxInsert + (unsigned long long)p->pad);
         } else {
           const unsigned long long E = S + (unsigned long long)nB;
-          windowBegin = (long long)(E - (unsigned long long)p->maxInsert - (unsigned long long)p->pad);
-          windowEnd = (long long)(E - (unsigned long long)p->minInsert + (unsigned long long)nA + (unsigned long long)p->pad);
+          windowBegin = (long long)(E - (unsigned long long)maxInsert - (unsigned long long)p->pad);
+          windowEnd = (long long)(E - (unsigned long long)minInsert + (unsigned long long)nA + (unsigned long long)p->pad);
         }
         windowBegin = windowBegin < 0 ? 0 : windowBegin;
         windowEnd = windowEnd < 0 ? 0 : windowEnd;

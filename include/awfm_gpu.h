@@ -89,6 +89,8 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   score_group=32|64       awfmGpuScoreChainsAffine: lanes per slot, in the same way
  *   window_q=4|8|12         awfmGpuScoreWindowsAffine: columns per lane for every read (narrower column blocks)
  *   pair_group=64           awfmGpuPairMates: a wave per pair also where 16 lanes hold the candidates
+ *   insert_tier=global      awfmGpuInsertHistogram: global atomics at any bin count (default: a private histogram in LDS per
+ *                       workgroup up to 8192 bins)
  *   second_window=0|1   the lookup kernel's second table window (a survivor's leftmost characters): 0 never, 1 on every trip;
  *                       unset, the kernel's own gate decides trip by trip (the results are the same either way)
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
@@ -969,12 +971,15 @@ enum AwFmReturnCode awfmGpuScoreWindowsAffine(AwFmGpuIndex *g, const struct AwFm
  * The stage for PAIRED reads, between slot scores and affine alignment: reads 2p (mate A) and 2p + 1 (mate B) are a pair, both
  * GIVEN ON THE SAME STRAND.  For the usual inward-facing library the caller reverse-complements mate 2 where the reads lie
  * (awfmGpuReverseComplementReads, below) and a two-strand index finds fragments of either strand, each in its own record; with a
- * one-strand index the caller submits (m1, rc m2) and (m2, rc m1) and compares pairScores itself.  The call knows no strands
- * and ESTIMATES no insert size: minInsert and maxInsert are the caller's and signed, so other library geometries are a matter
- * of sign and of which mate is complemented.  The loop runs without a host wait: chains, awfmGpuScoreChainsAffine, awfmGpuPairMates,
- * awfmGpuScoreWindowsAffine on the windows the pairing names, awfmGpuScoreChainsAffine and awfmGpuPairMates again,
- * awfmGpuAlignChainsAffine with pairSlots.  "every output may be NULL", "counters are added to", "numPairs == 0 touches nothing"
- * are slot scores'.  One definition on both sides, the host twin (csrc/awfm_pair_mates.c) being the definition and the checker.
+ * one-strand index the caller submits (m1, rc m2) and (m2, rc m1) and compares pairScores itself.  The call knows no strands:
+ * minInsert and maxInsert are signed, so other library geometries are a matter of sign and of which mate is complemented.  They
+ * are the caller's here; a caller who does not know the library's insert distribution takes them from "insert size" below, which
+ * estimates the interval from the batch's confidently placed pairs and hands it to awfmGpuPairMatesEstimated in device memory.
+ * The loop runs without a host wait: chains, awfmGpuScoreChainsAffine, [awfmGpuInsertHistogram, awfmGpuInsertInterval,]
+ * awfmGpuPairMates[Estimated], awfmGpuScoreWindowsAffine on the windows the pairing names, awfmGpuScoreChainsAffine and
+ * awfmGpuPairMates[Estimated] again, awfmGpuAlignChainsAffine with pairSlots.  "every output may be NULL", "counters are added
+ * to", "numPairs == 0 touches nothing" are slot scores'.  One definition on both sides, the host twin (csrc/awfm_pair_mates.c)
+ * being the definition and the checker.
  *
  * Inputs, C = maxCandidates (1..16), numReads = 2 numPairs < 2^32: readOffsets [numReads + 1]; sequences [numReads * C], the
  * slot table's column of that name; slotScores, slotReadEnds, slotTextEnds [numReads * C] exactly as awfmGpuScoreChainsAffine
@@ -1072,6 +1077,83 @@ enum AwFmReturnCode awfmReverseComplementReads(const uint8_t *readChars, uint64_
 enum AwFmReturnCode awfmGpuReverseComplementReads(AwFmGpuIndex *g, const uint8_t *dReadChars, uint64_t numReadChars,
                                                   const uint64_t *dReadOffsets, uint64_t numReads, uint32_t which, uint8_t *dOut,
                                                   uint64_t *dNumMalformed, void *stream);
+
+/* ---- insert size: the insert interval estimated from the confidently placed pairs, and pairing that reads it on the device ----
+ * The stage that gives "pair mates" its minInsert and maxInsert without a host wait: a HISTOGRAM of the template lengths of the
+ * pairs whose two best slots agree, an INTERVAL from its quartiles, and awfmGpuPairMatesEstimated, which is awfmGpuPairMates with
+ * the interval read from device memory.  The loop: slot scores -> awfmGpuInsertHistogram -> awfmGpuInsertInterval ->
+ * awfmGpuPairMatesEstimated -> window scores -> slot scores -> awfmGpuPairMatesEstimated -> affine alignment, all on one stream.
+ * All rules are INTEGER rules -- there is no floating point on this path -- and they are the library's OWN, like the mapping
+ * quality's: not BWA's and not any other mapper's.  ONE interval per call: no per-orientation estimates (the reads are on one
+ * strand, see "pair mates") and no standard deviation.  The host twins (csrc/awfm_insert.c) are the definition and the checker.
+ *
+ * params (struct AwFmInsertParams): lowTemplate <= highTemplate, the histogram's range with both ends included, bins =
+ * highTemplate - lowTemplate + 1 <= AWFM_INSERT_MAX_BINS, both within +-AWFM_PAIR_MAX_INSERT; minScore: pairing's rule 1;
+ * minQuality; spread 0..AWFM_INSERT_MAX_SPREAD; minSamples; fallbackMin <= fallbackMax, both within +-AWFM_PAIR_MAX_INSERT.  All
+ * four calls check all of them: anything outside is AwFmIllegalPositionError, as are maxCandidates outside 1..16 and numPairs
+ * >= 2^31; a NULL image, params, `in`, required input array, histogram or estimate is AwFmNullPtrError.
+ *
+ * HISTOGRAM, per pair p (A = 2p, B = 2p + 1; `in` is struct AwFmPairInputs as pairing takes it).  Slots COUNT and best(r) is as
+ * in pairing's rules 1 and 2, with THIS call's minScore.  The pair QUALIFIES when both mates have a best slot, the two best
+ * slots name one sequence and both INPUT mapping qualities are >= minQuality (mappingQualities NULL: 0 everywhere).  Its
+ * T = S(B, best(B)) + n_B - S(A, best(A)) in 64-bit two's complement, pairing's rule 2.  A qualifying pair with lowTemplate <= T
+ * <= highTemplate is a SAMPLE: histogram[T - lowTemplate] += 1 and *numSamples += 1; a qualifying pair outside the range adds
+ * 1 to *numOutside.  The histogram has `bins` 64-bit counters and is ADDED TO, like the two counters: the caller zeroes it
+ * and may accumulate over batches.  Either counter may be NULL.  numPairs == 0 touches nothing.
+ *
+ * INTERVAL.  N = the sum of the histogram.  N < max(minSamples, 1): valid = 0, minInsert / maxInsert = fallbackMin /
+ * fallbackMax, the quartiles and the mean 0, numSamples = N.  Otherwise rank_k = (k N + 3) / 4 for k = 1, 2, 3 (integer
+ * division: the smallest rank that has at least k quarters of the samples at or below it); q_k = lowTemplate + the smallest
+ * bin i whose inclusive prefix sum reaches rank_k; w = spread * max(q_3 - q_1, 1); minInsert = q_1 - w and maxInsert = q_3 + w,
+ * each clamped to +-AWFM_PAIR_MAX_INSERT; mean = lowTemplate + floor(sum of i h[i] / sum of h[i]) over the bins whose T lies in
+ * [minInsert, maxInsert] (they hold at least half of the samples: never empty); valid = 1; numSamples = N.  Sums are 64-bit and
+ * exact for N < 2^47.  All eight fields are written every time.
+ *
+ * ESTIMATED PAIRING.  awfmGpuPairMatesEstimated is awfmGpuPairMates to the bit -- rule 7's windows included -- with the
+ * interval read from dEstimate->minInsert / maxInsert on the device; params->minInsert and maxInsert are not looked at.  What
+ * the host cannot see the kernel validates: the interval is NOT USABLE when minInsert > maxInsert, minInsert <
+ * -AWFM_PAIR_MAX_INSERT or maxInsert > AWFM_PAIR_MAX_INSERT.  Then no slot pair is concordant and no read gets a window (every
+ * read's window outputs are AWFM_CANDIDATES_NONE, 0, 0 and *numWindows stays); everything else follows from the rules as
+ * written: the discordant candidate, bests and qualities as for improper pairs.  There is no host twin: the host reads the
+ * struct and calls awfmPairMates.
+ *
+ * awfmInsertHistogram: over `threads` threads of the pool, atomic adds into the histogram.  awfmInsertInterval: one thread.
+ * awfmGpuInsertHistogram (csrc/awfm_insert_kernel.h): ONE launch, a thread per pair over a persistent grid; up to 8192 bins a
+ * workgroup counts in a private histogram in LDS and adds only its nonzero bins to the caller's, above that (or with
+ * $AWFM_GPU_DIAG insert_tier=global: tests, the result is the same) it adds to the caller's directly, one atomic per wave and
+ * distinct bin; the two counters take one atomic per wave.  awfmGpuInsertInterval: ONE launch of one workgroup.  Every device
+ * call is asynchronous on `stream`, with no host wait, no allocation and no scratch of the image (g gives the device only):
+ * two streams may run them on one image at once. */
+#define AWFM_INSERT_MAX_BINS 65536u
+#define AWFM_INSERT_MAX_SPREAD 16u
+struct AwFmInsertParams {
+  int64_t lowTemplate, highTemplate; /* histogram range, both ends included; bins = high - low + 1 <= AWFM_INSERT_MAX_BINS;
+                                        both within +-AWFM_PAIR_MAX_INSERT */
+  uint32_t minScore;                 /* pairing's rule 1 */
+  uint32_t minQuality;               /* both mates' INPUT mapping quality >= this (qualities NULL: 0 everywhere) */
+  uint32_t spread;                   /* 0..AWFM_INSERT_MAX_SPREAD */
+  uint32_t minSamples;               /* fewer samples in the histogram: the fallback interval */
+  int64_t fallbackMin, fallbackMax;  /* fallbackMin <= fallbackMax, within +-AWFM_PAIR_MAX_INSERT */
+};
+struct AwFmInsertEstimate { /* 64 bytes; minInsert, maxInsert FIRST: what pairing reads */
+  int64_t minInsert, maxInsert;
+  int64_t quartiles[3];
+  int64_t mean;
+  uint64_t numSamples;
+  uint64_t valid; /* 1: estimated, 0: the fallback */
+};
+enum AwFmReturnCode awfmInsertHistogram(const struct AwFmPairInputs *in, uint64_t numPairs, uint32_t maxCandidates,
+                                        const struct AwFmInsertParams *params, uint64_t *histogram, uint64_t *numSamples,
+                                        uint64_t *numOutside, unsigned threads);
+enum AwFmReturnCode awfmGpuInsertHistogram(AwFmGpuIndex *g, const struct AwFmPairInputs *dIn, uint64_t numPairs, uint32_t maxCandidates,
+                                           const struct AwFmInsertParams *params, uint64_t *dHistogram, uint64_t *dNumSamples,
+                                           uint64_t *dNumOutside, void *stream);
+enum AwFmReturnCode awfmInsertInterval(const uint64_t *histogram, const struct AwFmInsertParams *params, struct AwFmInsertEstimate *estimate);
+enum AwFmReturnCode awfmGpuInsertInterval(AwFmGpuIndex *g, const uint64_t *dHistogram, const struct AwFmInsertParams *params,
+                                          struct AwFmInsertEstimate *dEstimate, void *stream);
+enum AwFmReturnCode awfmGpuPairMatesEstimated(AwFmGpuIndex *g, const struct AwFmPairInputs *dIn, uint64_t numPairs, uint32_t maxCandidates,
+                                              const struct AwFmPairParams *params, const struct AwFmInsertEstimate *dEstimate,
+                                              const struct AwFmPairOutputs *dOut, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);

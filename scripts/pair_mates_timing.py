@@ -24,6 +24,7 @@ import json
 import os
 import sys
 import time
+import types
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -94,7 +95,7 @@ def broadcast_pairing(torch, slot_scores, slot_sequences, slot_read_ends, slot_t
     return old
 
 
-def main():
+def arguments(out):
     p = argparse.ArgumentParser()
     p.add_argument("--text-len", type=count, default=3_100_000_000)
     p.add_argument("--reads", type=count, default=1 << 20)
@@ -104,9 +105,13 @@ def main():
     p.add_argument("--sa-ratio", type=int, default=8)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--out", default=os.path.join("profiles", "pair_mates", "timing.json"))
-    args = p.parse_args()
+    p.add_argument("--out", default=out)
+    return p
 
+
+def prepare(args):
+    """the index, the pairs, their seeds, located, mapped, chained and scored, all resident on the device: what the timed calls
+    of this script and of scripts/insert_size_timing.py start from -> a namespace of them, `result` and `timed` among them"""
     import numpy as np
     import torch
     from avxwindowfmindex_amd import _lib, api
@@ -226,6 +231,14 @@ def main():
     g.score_chains_affine(vin, R, api.slot_score_outputs(**{name: t.data_ptr() for name, t in scored.items()}), max_candidates=SLOTS,
                           band_pad=BAND_PAD, max_drift=MAX_DRIFT, scoring=costs, min_score=MIN_SCORE, mapq_cap=MAPQ_CAP, stream=stream)
     stream_obj.synchronize()
+    return types.SimpleNamespace(**{k: v for k, v in locals().items() if k != "args"})
+
+
+def main():
+    args = arguments(os.path.join("profiles", "pair_mates", "timing.json")).parse_args()
+    w = prepare(args)
+    np, torch, api, g, dev, stream_obj, stream, timed, result = w.np, w.torch, w.api, w.g, w.dev, w.stream_obj, w.stream, w.timed, w.result
+    R, P, M, d_reads, d_char_offsets, cand, scored = w.R, w.P, w.M, w.d_reads, w.d_char_offsets, w.cand, w.scored
 
     # ---- the new call ----
     pin = api.pair_inputs(d_char_offsets.data_ptr(), cand["sequences"].data_ptr(), scored["slotScores"].data_ptr(), scored["slotReadEnds"].data_ptr(),
