@@ -7,14 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "awfm_gpu.h"
-#include "awfm_internal.h"
-
-struct awfmKeptHit {
-  uint32_t sequence;
-  uint64_t key; /* the diagonal with its sign bit flipped: unsigned order = signed order */
-  uint32_t anchor, end;
-};
+#include "awfm_hits.h"
 
 struct awfmCluster {
   uint32_t sequence, votes, span, begin, end;
@@ -25,7 +18,7 @@ struct awfmCandidatesCtx {
   const struct AwFmCandidateInputs *in;
   const struct AwFmCandidateOutputs *out;
   uint32_t maxHitsPerSeed, band, minVotes, slots;
-  uint64_t overflowed[64]; /* per thread of the loop */
+  uint64_t overflowed[AWFM_HITS_THREADS];
   int failed;
 };
 
@@ -41,31 +34,16 @@ static int awfmClusterBefore(const struct awfmCluster *x, size_t xAt, const stru
   return x->votes != y->votes ? x->votes > y->votes : xAt < yAt;
 }
 
-/* the kept hits of read r into hits[0 .. AWFM_CANDIDATES_MAX_HITS); returns their true number, or UINT64_MAX for a malformed read */
+/* the kept hits of read r (awfm_hits.h) into hits[0 .. AWFM_CANDIDATES_MAX_HITS); returns their true number, or UINT64_MAX for
+ * a malformed read */
 static uint64_t awfmCollectKeptHits(const struct awfmCandidatesCtx *c, uint64_t r, struct awfmKeptHit *hits) {
-  const struct AwFmCandidateInputs *in = c->in;
-  const uint64_t seedBegin = in->readSeedOffsets[r], seedEnd = in->readSeedOffsets[r + 1];
-  if (seedBegin > seedEnd || seedEnd > in->numSeeds || seedEnd - seedBegin >= (1ull << 32)) return UINT64_MAX;
-  for (uint64_t s = seedBegin; s < seedEnd; s++)
-    if (in->hitOffsets[s] > in->hitOffsets[s + 1] || in->hitOffsets[s + 1] > in->numHits) return UINT64_MAX;
-  uint64_t kept = 0;
-  for (uint64_t s = seedBegin; s < seedEnd; s++) {
-    const uint32_t length = in->seedLengths ? in->seedLengths[s] : in->fixedLength, end = in->seedEnds[s];
-    const uint64_t hitBegin = in->hitOffsets[s], hitEnd = in->hitOffsets[s + 1];
-    if (length > end) continue;
-    if (c->maxHitsPerSeed != 0 && hitEnd - hitBegin > c->maxHitsPerSeed) continue;
-    for (uint64_t h = hitBegin; h < hitEnd; h++) {
-      const uint32_t sequence = in->sequenceNumbers ? in->sequenceNumbers[h] : 0;
-      if (sequence == AWFM_CANDIDATES_NONE) continue;
-      if (kept < AWFM_CANDIDATES_MAX_HITS) {
-        struct awfmKeptHit *hit = &hits[kept];
-        hit->sequence = sequence;
-        hit->key = (in->positions[h] - (uint64_t)(end - length)) ^ (1ull << 63);
-        hit->anchor = end - length;
-        hit->end = end;
-      }
-      kept++;
-    }
+  uint64_t seedBegin, seedEnd, kept = 0;
+  if (!awfmReadSeeds(c->in, r, &seedBegin, &seedEnd)) return UINT64_MAX;
+  struct awfmHitCursor cursor = awfmHitCursorOf(c->in, c->maxHitsPerSeed, seedBegin, seedEnd);
+  struct awfmKeptHit hit;
+  while (awfmNextKeptHit(&cursor, &hit)) {
+    if (kept < AWFM_CANDIDATES_MAX_HITS) hits[kept] = hit;
+    kept++;
   }
   return kept;
 }
@@ -108,7 +86,7 @@ static void awfmCandidatesRange(void *p, uint64_t begin, uint64_t end, unsigned 
       for (size_t k = 0; k < numClusters; k++) numCandidates += clusters[k].votes >= c->minVotes;
     }
     if (out->numCandidates) out->numCandidates[r] = (uint32_t)numCandidates;
-    if (out->keptHits) out->keptHits[r] = kept == UINT64_MAX ? 0xFFFFFFFFu : kept > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)kept;
+    if (out->keptHits) out->keptHits[r] = awfmKeptHitsWord(kept);
     size_t last = 0; /* slot j: the best candidate after slot j - 1's */
     for (uint32_t j = 0; j < c->slots; j++) {
       size_t best = numClusters;
@@ -118,11 +96,11 @@ static void awfmCandidatesRange(void *p, uint64_t begin, uint64_t end, unsigned 
           if (j != 0 && !awfmClusterBefore(&clusters[last], last, &clusters[k], k)) continue;
           if (best == numClusters || awfmClusterBefore(&clusters[k], k, &clusters[best], best)) best = k;
         }
-      const struct awfmCluster none = {AWFM_CANDIDATES_NONE, 0, 0, 0, 0, 1ull << 63};
+      const struct awfmCluster none = {AWFM_CANDIDATES_NONE, 0, 0, 0, 0, AWFM_HITS_SIGN};
       const struct awfmCluster *cl = best < numClusters ? &clusters[best] : &none;
       const uint64_t at = r * c->slots + j;
       if (out->sequences) out->sequences[at] = cl->sequence;
-      if (out->diagonals) out->diagonals[at] = (int64_t)(cl->key ^ (1ull << 63));
+      if (out->diagonals) out->diagonals[at] = (int64_t)(cl->key ^ AWFM_HITS_SIGN);
       if (out->votes) out->votes[at] = cl->votes;
       if (out->diagonalSpans) out->diagonalSpans[at] = cl->span;
       if (out->readBegins) out->readBegins[at] = cl->begin;
@@ -132,16 +110,15 @@ static void awfmCandidatesRange(void *p, uint64_t begin, uint64_t end, unsigned 
   }
   free(hits);
   free(clusters);
-  c->overflowed[tid & 63u] += overflowed;
+  c->overflowed[tid % AWFM_HITS_THREADS] += overflowed;
 }
 
 enum AwFmReturnCode awfmReadCandidates(const struct AwFmCandidateInputs *in, uint64_t numReads, uint32_t maxHitsPerSeed, uint32_t band,
                                        uint32_t minVotes, uint32_t maxCandidates, const struct AwFmCandidateOutputs *out,
                                        unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
-  if (!in || !out || !in->readSeedOffsets || !in->seedEnds || !in->hitOffsets || !in->positions) return AwFmNullPtrError;
-  if (!in->seedLengths && in->fixedLength == 0) return AwFmNullPtrError;
-  if (numReads >= (1ull << 32) || maxCandidates < 1 || maxCandidates > AWFM_CANDIDATES_MAX_SLOTS) return AwFmIllegalPositionError;
+  const enum AwFmReturnCode refused = awfmHitsCheckArguments(in, out != NULL, numReads, maxCandidates);
+  if (refused != AwFmSuccess) return refused;
   struct awfmCandidatesCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.in = in;
@@ -152,8 +129,6 @@ enum AwFmReturnCode awfmReadCandidates(const struct AwFmCandidateInputs *in, uin
   ctx.slots = maxCandidates;
   awfmParallelFor(threads ? threads : 1, numReads, awfmCandidatesRange, &ctx);
   if (ctx.failed) return AwFmAllocationFailure;
-  uint64_t overflowed = 0;
-  for (unsigned t = 0; t < 64; t++) overflowed += ctx.overflowed[t];
-  if (out->numOverflowed) *out->numOverflowed += overflowed;
+  awfmAddOverflowed(ctx.overflowed, out->numOverflowed);
   return AwFmSuccess;
 }

@@ -5,13 +5,9 @@
  *
  * One routine, candidatesOfRead<THREADS, CAP>, does a read with a workgroup of THREADS threads and room for CAP kept hits:
  *
- *   check    the read's seed range and the hit range of each of its seeds against the arrays' sizes, before anything is read
- *            through them: a malformed read is reported and read no further.
- *   gather   a read's hits are ONE stretch of positions / sequenceNumbers (its seeds are contiguous, hitOffsets is CSR), so each
- *            wave streams a contiguous part of it, 64 hits per round; a hit finds its seed by a binary search over the read's
- *            few hit offsets (cache hits), and a wave that stands wholly inside a seed above maxHitsPerSeed jumps to that seed's
- *            end.  Kept hits are appended to LDS as (sequence, diagonal ^ 2^63) through one LDS atomic per wave and round; the
- *            counter runs on beyond CAP, so that it ends as the true number of kept hits.
+ *   check    awfm_hits_kernel.h's: a malformed read is reported and read no further.
+ *   gather   awfm_hits_kernel.h's.  Kept hits are appended to LDS as (sequence, diagonal ^ 2^63) through one LDS atomic per wave
+ *            and round; the counter runs on beyond CAP, so that it ends as the true number of kept hits.
  *   sort     bitonic, in LDS, over the next power of two (padding sorts last: no kept hit has sequence 0xFFFFFFFF).
  *   runs     a neighbour compare marks the heads; an inclusive max-scan gives every hit its head, and the last hit of a run
  *            leaves its own number at the head: votes, diagonal and span of a cluster are then read at its head.
@@ -21,21 +17,19 @@
  *            it.  Skipped when neither readBegins nor readEnds is asked for.  The sort so carries no payload: 14 bytes of LDS
  *            per kept hit.
  *
- * Two tiers run it.  readCandidatesWaveKernel: one wave per read (workgroups of one wave, a persistent grid-stride loop over the
- * reads), CAP = kCandidatesWaveLimit; a read with more kept hits, up to AWFM_CANDIDATES_MAX_HITS, is appended to a worklist by
- * one lane (its gather has then only counted).  readCandidatesGroupKernel: a fixed grid that reads the worklist's length on the
- * device and gives each such read a workgroup of kCandidatesGroupThreads with CAP = AWFM_CANDIDATES_MAX_HITS (58 KB of LDS: two
- * workgroups per CU).  Reads beyond that are overflowed: reported by the wave tier, never sorted.
+ * The two tiers of awfm_hits_kernel.h run it.  readCandidatesWaveKernel: CAP = kCandidatesWaveLimit; a read with more kept
+ * hits, up to AWFM_CANDIDATES_MAX_HITS, goes onto the worklist (its gather has then only counted).  readCandidatesGroupKernel:
+ * workgroups of kCandidatesGroupThreads with CAP = AWFM_CANDIDATES_MAX_HITS (58 KB of LDS: two workgroups per CU).  Reads beyond
+ * that are overflowed: reported by the wave tier, never sorted.
  *
  * Vector loads and stores only; outputs are stored per read in whole runs of slots by the first C threads.
  */
 #ifndef AWFM_CANDIDATES_KERNEL_H
 #define AWFM_CANDIDATES_KERNEL_H
 
-#include <cstddef>
 #include <type_traits>
 
-#include "awfm_device.h"
+#include "awfm_hits_kernel.h"
 
 namespace {
 
@@ -47,9 +41,6 @@ constexpr unsigned kCandidatesEntryBytes = 14;    /* LDS per kept hit: sequence 
 constexpr unsigned kCandidatesWaveLdsBytes = 4608;   /* static LDS of the wave tier's kernel at the most (3584 + slots): 4.5 KB */
 constexpr unsigned kCandidatesGroupLdsBytes = 59392; /* ... and of the workgroup tier's (57344 + slots): 58 KB */
 constexpr unsigned kCandidatesSlots = 16;         /* = AWFM_CANDIDATES_MAX_SLOTS */
-constexpr unsigned kCandidatesNone = 0xFFFFFFFFu;
-constexpr unsigned long long kCandidatesSign = 1ull << 63;
-constexpr unsigned kCandidatesMalformed = 0xFFFFFFFFu, kCandidatesSaturated = 0xFFFFFFFEu;
 
 static_assert(kCandidatesGroupLimit == AWFM_CANDIDATES_MAX_HITS && kCandidatesSlots == AWFM_CANDIDATES_MAX_SLOTS, "include/awfm_gpu.h");
 static_assert(kCandidatesGroupLimit <= 4096, "a head's number and 12 bits of votes share 32 bits; heads are stored in 16");
@@ -79,78 +70,17 @@ struct CandidatesLds {
 static_assert(sizeof(CandidatesLds<kCandidatesWaveLimit>) <= kCandidatesWaveLdsBytes, "the wave tier's LDS");
 static_assert(sizeof(CandidatesLds<kCandidatesGroupLimit>) <= kCandidatesGroupLdsBytes, "the workgroup tier's LDS");
 
-/* Calls visit(keep, sequence, key, anchor, end) for every hit of the stretch [hitLow, hitHigh) of a well-formed read, 64 per
- * round and wave, with keep = the hit is a kept hit; all 64 lanes make every call (visit may ballot). */
-template <typename Visit>
-__device__ __forceinline__ void visitHits(const DevCandidateParams &p, unsigned long long seedBegin, unsigned long long seedEnd,
-                                          unsigned long long hitLow, unsigned long long hitHigh, Visit visit) {
-  const AwFmCandidateInputs &in = p.in;
-  const unsigned lane = threadIdx.x & 63u;
-  unsigned long long base = hitLow;
-  while (base < hitHigh) { /* wave-uniform */
-    const unsigned long long h = base + lane;
-    const bool inside = h < hitHigh;
-    const unsigned long long hh = inside ? h : base;
-    unsigned long long lo = seedBegin, hi = seedEnd; /* the last seed whose hits begin at or before hh: hitOffsets[seedBegin] <= hh */
-    while (hi - lo > 1u) {
-      const unsigned long long mid = lo + ((hi - lo) >> 1);
-      const bool before = in.hitOffsets[mid] <= hh;
-      lo = before ? mid : lo;
-      hi = before ? hi : mid;
-    }
-    const unsigned long long seedHitBegin = in.hitOffsets[lo], seedHitEnd = in.hitOffsets[lo + 1u];
-    const unsigned length = in.seedLengths ? in.seedLengths[lo] : in.fixedLength, end = in.seedEnds[lo];
-    const bool seedKept = length <= end && (p.maxHitsPerSeed == 0u || seedHitEnd - seedHitBegin <= p.maxHitsPerSeed);
-    /* lane 0 stands at `base`: when its seed is dropped and holds the whole round, the wave goes on behind that seed */
-    const unsigned long long firstEnd = (unsigned long long)__shfl((long long)seedHitEnd, 0, 64);
-    if (!__shfl((int)seedKept, 0, 64) && firstEnd - base >= 64u) {
-      base = firstEnd < hitHigh ? firstEnd : hitHigh;
-      continue;
-    }
-    bool keep = inside && seedKept;
-    unsigned sequence = 0;
-    if (keep && in.sequenceNumbers) {
-      sequence = in.sequenceNumbers[h];
-      keep = sequence != kCandidatesNone;
-    }
-    const unsigned anchor = end - length;
-    const unsigned long long key = keep ? (in.positions[h] - anchor) ^ kCandidatesSign : 0ull;
-    visit(keep, sequence, key, anchor, end);
-    base += 64u;
-  }
-}
-
-/* the part of the read's stretch of hits that this wave streams: the stretch in equal contiguous parts, one per wave */
-template <unsigned THREADS>
-__device__ __forceinline__ void wavePart(unsigned long long hitBegin, unsigned long long hitEnd, unsigned long long &low,
-                                         unsigned long long &high) {
-  constexpr unsigned kWaves = THREADS / 64u;
-  const unsigned wave = threadIdx.x >> 6;
-  const unsigned long long part = (hitEnd - hitBegin + kWaves - 1u) / kWaves;
-  low = hitBegin + wave * part;
-  low = low < hitEnd ? low : hitEnd;
-  high = hitEnd - low < part ? hitEnd : low + part;
-}
-
-/* The output pointers where they are needed, not before: the kernel's arguments are 26 words and pointers, and the compiler
- * would otherwise load all of them ahead of the loop over the reads and spill scalar registers in the sort.  They are read from
- * the kernel's argument segment, of which DevCandidateParams is the one and only entry in both kernels (a static_assert on their
- * signatures at the end of this file holds that); the empty statement
- * only hides where the pointer comes from, so that the loads stay behind it. */
+/* The output pointers where they are stored through, not before (kernelArguments): the kernel's arguments are 26 words and
+ * pointers, and the sort spills scalar registers when they are loaded ahead of the loop over the reads. */
 typedef const __attribute__((address_space(4))) AwFmCandidateOutputs *KernelOutputs;
-__device__ __forceinline__ KernelOutputs outputsOf() {
-  KernelOutputs out = (KernelOutputs)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() +
-                                      offsetof(DevCandidateParams, out));
-  asm volatile("" : "+s"(out));
-  return out;
-}
+__device__ __forceinline__ KernelOutputs outputsOf() { return &kernelArguments<DevCandidateParams>()->out; }
 
 /* stores read r's slots from `first` on as unused, by the first threads of the workgroup */
 __device__ __forceinline__ void fillSlots(const DevCandidateParams &p, KernelOutputs out, unsigned long long r, unsigned first) {
   const unsigned j = threadIdx.x;
   if (j < first || j >= p.slots) return;
   const unsigned long long at = r * p.slots + j;
-  if (out->sequences) out->sequences[at] = kCandidatesNone;
+  if (out->sequences) out->sequences[at] = kHitsNone;
   if (out->diagonals) out->diagonals[at] = 0;
   if (out->votes) out->votes[at] = 0u;
   if (out->diagonalSpans) out->diagonalSpans[at] = 0u;
@@ -176,7 +106,6 @@ __device__ bool candidatesOfRead(const DevCandidateParams &p, CandidatesLds<CAP>
   constexpr unsigned kPer = CAP / THREADS; /* hits per thread once they are in LDS */
   static_assert(CAP % THREADS == 0 && (CAP & (CAP - 1u)) == 0, "a power of two, whole rounds");
   const unsigned tid = threadIdx.x;
-  const AwFmCandidateInputs &in = p.in;
   __syncthreads(); /* the LDS of the read before */
   if (tid == 0u) {
     s.kept = 0ull;
@@ -187,29 +116,20 @@ __device__ bool candidatesOfRead(const DevCandidateParams &p, CandidatesLds<CAP>
     s.selBegin[tid] = 0xFFFFFFFFu;
     s.selEnd[tid] = 0u;
   }
-  /* check: nothing is read through an offset that was not compared with its array's size first */
-  const unsigned long long seedBegin = in.readSeedOffsets[r], seedEnd = in.readSeedOffsets[r + 1u];
-  bool malformed = seedBegin > seedEnd || seedEnd > in.numSeeds || seedEnd - seedBegin >= (1ull << 32);
-  if (!malformed)
-    for (unsigned long long q = seedBegin + tid; q < seedEnd; q += THREADS)
-      malformed |= in.hitOffsets[q] > in.hitOffsets[q + 1u] || in.hitOffsets[q + 1u] > in.numHits;
-  if (__syncthreads_or(malformed)) {
-    reportUnsorted(p, r, kCandidatesMalformed);
+  /* check */
+  unsigned long long seedBegin, seedEnd;
+  if (__syncthreads_or(readMalformed<THREADS>(p.in, r, seedBegin, seedEnd))) {
+    reportUnsorted(p, r, kHitsMalformed);
     return false;
   }
   /* gather */
-  const unsigned long long hitBegin = seedBegin < seedEnd ? in.hitOffsets[seedBegin] : 0ull;
-  const unsigned long long hitEnd = seedBegin < seedEnd ? in.hitOffsets[seedEnd] : 0ull;
   unsigned long long low, high;
-  wavePart<THREADS>(hitBegin, hitEnd, low, high);
+  wavePart<THREADS>(p.in, seedBegin, seedEnd, low, high);
   const unsigned lane = tid & 63u;
   visitHits(p, seedBegin, seedEnd, low, high, [&](bool keep, unsigned sequence, unsigned long long key, unsigned, unsigned) {
     const unsigned long long mask = __ballot(keep);
     if (mask == 0ull) return;
-    const int leader = __ffsll((long long)mask) - 1;
-    unsigned long long at = 0ull;
-    if ((int)lane == leader) at = atomicAdd(&s.kept, (unsigned long long)__popcll(mask));
-    at = (unsigned long long)__shfl((long long)at, leader, 64) + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+    const unsigned long long at = waveAppend(&s.kept, mask, __ffsll((long long)mask) - 1);
     if (keep && at < CAP) {
       s.sequence[at] = sequence;
       s.key[at] = key;
@@ -218,36 +138,23 @@ __device__ bool candidatesOfRead(const DevCandidateParams &p, CandidatesLds<CAP>
   __syncthreads();
   const unsigned long long kept = s.kept;
   if (kept > kCandidatesGroupLimit) {
-    reportUnsorted(p, r, kept > kCandidatesSaturated ? kCandidatesSaturated : (unsigned)kept);
+    reportUnsorted(p, r, keptHitsWord(kept));
     return false;
   }
   if (kept > limit) return true;
   const unsigned n = (unsigned)kept;
-  /* sort */
-  unsigned padded = 2u;
-  while (padded < n) padded <<= 1;
-  for (unsigned i = n + tid; i < padded; i += THREADS) {
-    s.sequence[i] = kCandidatesNone;
-    s.key[i] = ~0ull;
-  }
-  __syncthreads();
-  if (n > 1u)
-    for (unsigned k = 2u; k <= padded; k <<= 1)
-      for (unsigned j = k >> 1; j != 0u; j >>= 1) {
-        for (unsigned t = tid; t < (padded >> 1); t += THREADS) {
-          const unsigned a = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), b = a | j;
-          const unsigned sa = s.sequence[a], sb = s.sequence[b];
-          const unsigned long long ka = s.key[a], kb = s.key[b];
-          const bool greater = sa != sb ? sa > sb : ka > kb;
-          if (greater == ((a & k) == 0u)) {
-            s.sequence[a] = sb;
-            s.sequence[b] = sa;
-            s.key[a] = kb;
-            s.key[b] = ka;
-          }
-        }
-        __syncthreads();
-      }
+  /* sort: by (sequence, key) */
+  struct Hit {
+    unsigned sequence;
+    unsigned long long key;
+  };
+  sortLds<THREADS>(
+      n, Hit{kHitsNone, ~0ull}, [&](unsigned i) { return Hit{s.sequence[i], s.key[i]}; },
+      [&](unsigned i, const Hit &x) {
+        s.sequence[i] = x.sequence;
+        s.key[i] = x.key;
+      },
+      [](const Hit &x, const Hit &y) { return x.sequence != y.sequence ? x.sequence > y.sequence : x.key > y.key; });
   /* runs: thread tid has the hits tid, tid + THREADS, ... */
   unsigned heads = 0u, lasts = 0u; /* bit e: my hit e begins / ends a run */
 #pragma unroll
@@ -345,7 +252,7 @@ __device__ bool candidatesOfRead(const DevCandidateParams &p, CandidatesLds<CAP>
   if (tid < stored) {
     const unsigned long long at = r * p.slots + tid, span = s.selHigh[tid] - s.selLow[tid];
     if (out->sequences) out->sequences[at] = s.selSequence[tid];
-    if (out->diagonals) out->diagonals[at] = (long long)(s.selLow[tid] ^ kCandidatesSign);
+    if (out->diagonals) out->diagonals[at] = (long long)(s.selLow[tid] ^ kHitsSign);
     if (out->votes) out->votes[at] = s.best[tid] >> 12;
     if (out->diagonalSpans) out->diagonalSpans[at] = span > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)span;
     if (out->readBegins) out->readBegins[at] = s.selBegin[tid];
@@ -359,29 +266,25 @@ __device__ bool candidatesOfRead(const DevCandidateParams &p, CandidatesLds<CAP>
   return false;
 }
 
-/* the wave tier: one wave per read; what it cannot hold goes onto the worklist */
+/* the wave tier: what it cannot hold goes onto the worklist */
 __global__ void __launch_bounds__(kCandidatesWaveThreads) readCandidatesWaveKernel(const DevCandidateParams p) {
   __shared__ CandidatesLds<kCandidatesWaveLimit> s;
-  for (unsigned long long r = blockIdx.x; r < p.numReads; r += gridDim.x)
-    if (candidatesOfRead<kCandidatesWaveThreads, kCandidatesWaveLimit>(p, s, r, p.waveLimit) && threadIdx.x == 0u)
-      p.worklist[atomicAdd(p.counter, 1ull)] = (unsigned)r; /* (at most one entry per read: numReads entries hold them) */
+  waveTier(p, blockIdx.x, gridDim.x, [&](unsigned long long r) { return candidatesOfRead<kCandidatesWaveThreads, kCandidatesWaveLimit>(p, s, r, p.waveLimit); });
 }
 
-/* the workgroup tier: the reads of the worklist, whose length is read here */
+/* the workgroup tier */
 __global__ void __launch_bounds__(kCandidatesGroupThreads) readCandidatesGroupKernel(const DevCandidateParams p) {
   __shared__ CandidatesLds<kCandidatesGroupLimit> s;
-  const unsigned long long have = *p.counter, listed = have < p.numReads ? have : p.numReads;
-  for (unsigned long long w = blockIdx.x; w < listed; w += gridDim.x) {
-    const unsigned long long r = p.worklist[w];
-    if (r < p.numReads) (void)candidatesOfRead<kCandidatesGroupThreads, kCandidatesGroupLimit>(p, s, r, kCandidatesGroupLimit);
-  }
+  groupTier(p, blockIdx.x, gridDim.x, [&](unsigned long long r) {
+    return candidatesOfRead<kCandidatesGroupThreads, kCandidatesGroupLimit>(p, s, r, kCandidatesGroupLimit);
+  });
 }
 
-/* outputsOf() reads the outputs at offsetof(DevCandidateParams, out) of the argument segment: right only while that struct is
- * the one argument of both kernels, by value, hence at offset 0.  A change of either signature stops the build here. */
+/* kernelArguments() reads the argument segment as a DevCandidateParams: right only while that struct is the one argument of both
+ * kernels, by value, hence at offset 0.  A change of either signature stops the build here. */
 static_assert(std::is_same<decltype(&readCandidatesWaveKernel), void (*)(DevCandidateParams)>::value &&
                   std::is_same<decltype(&readCandidatesGroupKernel), void (*)(DevCandidateParams)>::value,
-              "outputsOf() assumes DevCandidateParams is the kernels' only argument");
+              "kernelArguments() assumes DevCandidateParams is the kernels' only argument");
 
 }  // namespace
 

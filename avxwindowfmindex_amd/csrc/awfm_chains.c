@@ -1,18 +1,14 @@
 /*
  * awfm_chains.c -- awfmReadChains (include/awfm_gpu.h, "read chains"): the best colinear chain of the kept hits of every
  * candidate slot.  The host twin of awfmGpuReadChains and its checker: one read at a time, collect the kept hits, give each to
- * the slot whose interval holds it, qsort, run the recurrence.  Nothing here is clever.  The kept hits of a read are restated
- * from awfm_candidates.c rather than shared: an anchor needs the seed's length next to what a cluster needs, and that file stays
- * as it is.  The reference has no analogue (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
+ * the slot whose interval holds it, qsort, run the recurrence.  Nothing here is clever.  The kept hits of a read are awfm_hits.h's.
+ * The reference has no analogue (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
  */
 #include <assert.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "awfm_gpu.h"
-#include "awfm_internal.h"
-
-#define AWFM_CHAINS_SIGN (1ull << 63)
+#include "awfm_hits.h"
 
 struct awfmAnchor {
   uint32_t slot, end, length;
@@ -31,7 +27,7 @@ struct awfmChainsCtx {
   const uint32_t *sequences, *spans;
   const int64_t *diagonals;
   uint32_t maxHitsPerSeed, band, slots, lookback, gapPenalty;
-  uint64_t overflowed[64]; /* per thread of the loop */
+  uint64_t overflowed[AWFM_HITS_THREADS];
   int failed;
 };
 
@@ -53,7 +49,7 @@ static int awfmSlotsIntersect(const struct awfmChainsCtx *c, uint64_t r) {
     for (uint32_t k = j + 1; k < c->slots; k++) {
       const uint64_t a = r * c->slots + j, b = r * c->slots + k;
       if (c->sequences[a] == AWFM_CANDIDATES_NONE || c->sequences[a] != c->sequences[b]) continue;
-      const uint64_t lowA = (uint64_t)c->diagonals[a] ^ AWFM_CHAINS_SIGN, lowB = (uint64_t)c->diagonals[b] ^ AWFM_CHAINS_SIGN;
+      const uint64_t lowA = (uint64_t)c->diagonals[a] ^ AWFM_HITS_SIGN, lowB = (uint64_t)c->diagonals[b] ^ AWFM_HITS_SIGN;
       if (lowA <= awfmSlotHigh(lowB, c->spans[b]) && lowB <= awfmSlotHigh(lowA, c->spans[a])) return 1;
     }
   return 0;
@@ -62,35 +58,23 @@ static int awfmSlotsIntersect(const struct awfmChainsCtx *c, uint64_t r) {
 /* The kept hits of read r that lie in a slot, into anchors[0 .. AWFM_CANDIDATES_MAX_HITS); returns the true number of KEPT HITS
  * (in a slot or not), or UINT64_MAX for a malformed read.  *numAnchors is right when that number is within the limit. */
 static uint64_t awfmCollectAnchors(const struct awfmChainsCtx *c, uint64_t r, struct awfmAnchor *anchors, size_t *numAnchors) {
-  const struct AwFmCandidateInputs *in = c->in;
-  const uint64_t seedBegin = in->readSeedOffsets[r], seedEnd = in->readSeedOffsets[r + 1];
-  *numAnchors = 0;
-  if (seedBegin > seedEnd || seedEnd > in->numSeeds || seedEnd - seedBegin >= (1ull << 32)) return UINT64_MAX;
-  for (uint64_t s = seedBegin; s < seedEnd; s++)
-    if (in->hitOffsets[s] > in->hitOffsets[s + 1] || in->hitOffsets[s + 1] > in->numHits) return UINT64_MAX;
-  if (awfmSlotsIntersect(c, r)) return UINT64_MAX;
-  uint64_t kept = 0;
+  uint64_t seedBegin, seedEnd, kept = 0;
   size_t n = 0;
-  for (uint64_t s = seedBegin; s < seedEnd; s++) {
-    const uint32_t length = in->seedLengths ? in->seedLengths[s] : in->fixedLength, end = in->seedEnds[s];
-    const uint64_t hitBegin = in->hitOffsets[s], hitEnd = in->hitOffsets[s + 1];
-    if (length > end) continue;
-    if (c->maxHitsPerSeed != 0 && hitEnd - hitBegin > c->maxHitsPerSeed) continue;
-    for (uint64_t h = hitBegin; h < hitEnd; h++) {
-      const uint32_t sequence = in->sequenceNumbers ? in->sequenceNumbers[h] : 0;
-      if (sequence == AWFM_CANDIDATES_NONE) continue;
-      if (kept++ >= AWFM_CANDIDATES_MAX_HITS) continue;
-      const uint64_t key = (in->positions[h] - (uint64_t)(end - length)) ^ AWFM_CHAINS_SIGN;
-      for (uint32_t j = 0; j < c->slots; j++) {
-        const uint64_t at = r * c->slots + j, low = (uint64_t)c->diagonals[at] ^ AWFM_CHAINS_SIGN;
-        if (c->sequences[at] != sequence || key < low || key - low > c->spans[at]) continue;
-        anchors[n].slot = j;
-        anchors[n].end = end;
-        anchors[n].length = length;
-        anchors[n].key = key;
-        n++;
-        break; /* (the slots of a well-formed read do not intersect) */
-      }
+  *numAnchors = 0;
+  if (!awfmReadSeeds(c->in, r, &seedBegin, &seedEnd) || awfmSlotsIntersect(c, r)) return UINT64_MAX;
+  struct awfmHitCursor cursor = awfmHitCursorOf(c->in, c->maxHitsPerSeed, seedBegin, seedEnd);
+  struct awfmKeptHit hit;
+  while (awfmNextKeptHit(&cursor, &hit)) {
+    if (kept++ >= AWFM_CANDIDATES_MAX_HITS) continue;
+    for (uint32_t j = 0; j < c->slots; j++) {
+      const uint64_t at = r * c->slots + j, low = (uint64_t)c->diagonals[at] ^ AWFM_HITS_SIGN;
+      if (c->sequences[at] != hit.sequence || hit.key < low || hit.key - low > c->spans[at]) continue;
+      anchors[n].slot = j;
+      anchors[n].end = hit.end;
+      anchors[n].length = hit.length;
+      anchors[n].key = hit.key;
+      n++;
+      break; /* (the slots of a well-formed read do not intersect) */
     }
   }
   *numAnchors = n;
@@ -169,9 +153,9 @@ static void awfmChainsRange(void *p, uint64_t begin, uint64_t end, unsigned tid)
     for (uint32_t j = 0; j < c->slots; j++) {
       const size_t first = k;
       while (k < n && anchors[k].slot == j) k++;
-      struct awfmChainState chain = {0, 0, 0, AWFM_CHAINS_SIGN};
+      struct awfmChainState chain = {0, 0, 0, AWFM_HITS_SIGN};
       uint32_t readEnd = 0;
-      uint64_t endKey = AWFM_CHAINS_SIGN;
+      uint64_t endKey = AWFM_HITS_SIGN;
       if (k > first) {
         const size_t last = awfmChainSlot(c, anchors, state, first, k);
         chain = state[last];
@@ -187,15 +171,15 @@ static void awfmChainsRange(void *p, uint64_t begin, uint64_t end, unsigned tid)
       if (out->chainAnchors) out->chainAnchors[at] = chain.anchors;
       if (out->chainReadBegins) out->chainReadBegins[at] = chain.begin;
       if (out->chainReadEnds) out->chainReadEnds[at] = readEnd;
-      if (out->chainBeginDiagonals) out->chainBeginDiagonals[at] = (int64_t)(chain.beginKey ^ AWFM_CHAINS_SIGN);
-      if (out->chainEndDiagonals) out->chainEndDiagonals[at] = (int64_t)(endKey ^ AWFM_CHAINS_SIGN);
+      if (out->chainBeginDiagonals) out->chainBeginDiagonals[at] = (int64_t)(chain.beginKey ^ AWFM_HITS_SIGN);
+      if (out->chainEndDiagonals) out->chainEndDiagonals[at] = (int64_t)(endKey ^ AWFM_HITS_SIGN);
     }
     if (out->bestSlots) out->bestSlots[r] = bestSlot;
-    if (out->keptHits) out->keptHits[r] = kept == UINT64_MAX ? 0xFFFFFFFFu : kept > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)kept;
+    if (out->keptHits) out->keptHits[r] = awfmKeptHitsWord(kept);
   }
   free(anchors);
   free(state);
-  c->overflowed[tid & 63u] += overflowed;
+  c->overflowed[tid % AWFM_HITS_THREADS] += overflowed;
 }
 
 enum AwFmReturnCode awfmReadChains(const struct AwFmCandidateInputs *in, uint64_t numReads, uint32_t maxHitsPerSeed, uint32_t band,
@@ -203,10 +187,8 @@ enum AwFmReturnCode awfmReadChains(const struct AwFmCandidateInputs *in, uint64_
                                    const uint32_t *diagonalSpans, uint32_t lookback, uint32_t gapPenalty,
                                    const struct AwFmChainOutputs *out, unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
-  if (!in || !out || !in->readSeedOffsets || !in->seedEnds || !in->hitOffsets || !in->positions) return AwFmNullPtrError;
-  if (!sequences || !diagonals || !diagonalSpans) return AwFmNullPtrError;
-  if (!in->seedLengths && in->fixedLength == 0) return AwFmNullPtrError;
-  if (numReads >= (1ull << 32) || maxCandidates < 1 || maxCandidates > AWFM_CANDIDATES_MAX_SLOTS) return AwFmIllegalPositionError;
+  const enum AwFmReturnCode refused = awfmHitsCheckArguments(in, out && sequences && diagonals && diagonalSpans, numReads, maxCandidates);
+  if (refused != AwFmSuccess) return refused;
   if (lookback < 1 || lookback > AWFM_CHAINS_MAX_LOOKBACK) return AwFmIllegalPositionError;
   struct awfmChainsCtx ctx;
   memset(&ctx, 0, sizeof ctx);
@@ -222,8 +204,6 @@ enum AwFmReturnCode awfmReadChains(const struct AwFmCandidateInputs *in, uint64_
   ctx.gapPenalty = gapPenalty;
   awfmParallelFor(threads ? threads : 1, numReads, awfmChainsRange, &ctx);
   if (ctx.failed) return AwFmAllocationFailure;
-  uint64_t overflowed = 0;
-  for (unsigned t = 0; t < 64; t++) overflowed += ctx.overflowed[t];
-  if (out->numOverflowed) *out->numOverflowed += overflowed;
+  awfmAddOverflowed(ctx.overflowed, out->numOverflowed);
   return AwFmSuccess;
 }

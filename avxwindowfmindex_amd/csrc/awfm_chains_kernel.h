@@ -5,14 +5,11 @@
  *
  * One routine, chainsOfRead<THREADS, CAP>, does a read with a workgroup of THREADS threads and room for CAP anchors:
  *
- *   check    the read's seed range and the hit range of each of its seeds against the arrays' sizes before anything is read
- *            through them, and the read's at most 16 slots against each other (256 pairs): a malformed read is reported and
- *            read no further.  The slots (sequence, diagonal ^ 2^63, span) stay in LDS.
- *   gather   as in awfm_candidates_kernel.h: a read's hits are ONE stretch of positions / sequenceNumbers, each wave streams a
- *            contiguous part of it, 64 hits per round, and jumps over dropped seeds that hold whole rounds.  Every kept hit is
- *            counted; the one that lies in a slot is an anchor and is appended to LDS as two 64-bit words,
- *            (slot << 32 | e) and ((D - the slot's diagonal) << 32 | len): a slot's interval is at most 2^32 - 1 wide, so the
- *            diagonal travels as 32 bits and an anchor is 16 bytes, sort key and payload in one.
+ *   check    awfm_hits_kernel.h's, and the read's at most 16 slots against each other (256 pairs): a malformed read is reported
+ *            and read no further.  The slots (sequence, diagonal ^ 2^63, span) stay in LDS.
+ *   gather   awfm_hits_kernel.h's.  Every kept hit is counted; the one that lies in a slot is an anchor and is appended to LDS as
+ *            two 64-bit words, (slot << 32 | e) and ((D - the slot's diagonal) << 32 | len): a slot's interval is at most
+ *            2^32 - 1 wide, so the diagonal travels as 32 bits and an anchor is 16 bytes, sort key and payload in one.
  *   sort     bitonic, in LDS, over the next power of two, by those two words: (slot, e, D, len), the definition's order
  *            (padding sorts last).  A neighbour compare then gives every slot its range.
  *   chain    a WAVE per slot, the slots of a read one after another (wave tier) or eight at a time (workgroup tier).  The
@@ -25,23 +22,20 @@
  *            key would be 64 bits wide and double the reduction; the ballot costs three scalar instructions instead.  The
  *            slot's best chain so far lives in scalars.
  *
- * Two tiers run it.  readChainsWaveKernel: one wave per read (workgroups of one wave, a persistent grid-stride loop over the
- * reads), CAP = kChainsWaveLimit; a read with more anchors (and at most AWFM_CANDIDATES_MAX_HITS kept hits) is appended to a
- * worklist by one lane (its gather has then only counted).  readChainsGroupKernel: a fixed grid that reads the worklist's length
- * on the device and gives each such read a workgroup of kChainsGroupThreads with CAP = AWFM_CANDIDATES_MAX_HITS: 64 KB of anchors
- * and the slots, beyond the 64 KB a launch gets without asking, hence dynamic LDS (the launch sets the kernel's limit for the
- * device at hand each time); two such workgroups share a CU's 160 KB.  Reads with more kept hits are overflowed: reported by
- * the wave tier, never sorted.
+ * The two tiers of awfm_hits_kernel.h run it.  readChainsWaveKernel: CAP = kChainsWaveLimit; a read with more anchors (and at
+ * most AWFM_CANDIDATES_MAX_HITS kept hits) goes onto the worklist (its gather has then only counted).  readChainsGroupKernel:
+ * workgroups of kChainsGroupThreads with CAP = AWFM_CANDIDATES_MAX_HITS: 64 KB of anchors and the slots, beyond the 64 KB a
+ * launch gets without asking, hence dynamic LDS (the launch sets the kernel's limit for the device at hand each time); two such
+ * workgroups share a CU's 160 KB.  Reads with more kept hits are overflowed: reported by the wave tier, never sorted.
  *
  * Vector loads and stores only; outputs are stored per read in whole runs of slots by the first C threads.
  */
 #ifndef AWFM_CHAINS_KERNEL_H
 #define AWFM_CHAINS_KERNEL_H
 
-#include <cstddef>
 #include <type_traits>
 
-#include "awfm_device.h"
+#include "awfm_hits_kernel.h"
 
 namespace {
 
@@ -53,9 +47,6 @@ constexpr unsigned kChainsEntryBytes = 16;    /* LDS per anchor: slot 4, e 4, re
 constexpr unsigned kChainsWaveLdsBytes = 5376;   /* static LDS of the wave tier's kernel at the most (4096 + slots): 5.25 KB */
 constexpr unsigned kChainsGroupLdsBytes = 66560; /* dynamic LDS of the workgroup tier's (65536 + slots): 65 KB, two per CU */
 constexpr unsigned kChainsSlots = 16;         /* = AWFM_CANDIDATES_MAX_SLOTS */
-constexpr unsigned kChainsNone = 0xFFFFFFFFu;
-constexpr unsigned long long kChainsSign = 1ull << 63;
-constexpr unsigned kChainsMalformed = 0xFFFFFFFFu, kChainsSaturated = 0xFFFFFFFEu;
 
 static_assert(kChainsGroupLimit == AWFM_CANDIDATES_MAX_HITS && kChainsSlots == AWFM_CANDIDATES_MAX_SLOTS, "include/awfm_gpu.h");
 static_assert(AWFM_CHAINS_MAX_LOOKBACK == 64u, "the lookback window is the 64 lanes of a wave");
@@ -89,48 +80,6 @@ struct ChainsLds {
 };
 static_assert(sizeof(ChainsLds<kChainsWaveLimit>) <= kChainsWaveLdsBytes, "the wave tier's LDS");
 static_assert(sizeof(ChainsLds<kChainsGroupLimit>) <= kChainsGroupLdsBytes, "the workgroup tier's LDS");
-
-/* Calls visit(keep, sequence, key, anchor, end) for every hit of the stretch [hitLow, hitHigh) of a well-formed read, 64 per
- * round and wave, with keep = the hit is a kept hit; all 64 lanes make every call (visit may ballot).  (The candidate kernels'
- * routine, restated for this unit's parameters.) */
-template <typename Visit>
-__device__ __forceinline__ void visitChainHits(const DevChainParams &p, unsigned long long seedBegin, unsigned long long seedEnd,
-                                               unsigned long long hitLow, unsigned long long hitHigh, Visit visit) {
-  const AwFmCandidateInputs &in = p.in;
-  const unsigned lane = threadIdx.x & 63u;
-  unsigned long long base = hitLow;
-  while (base < hitHigh) { /* wave-uniform */
-    const unsigned long long h = base + lane;
-    const bool inside = h < hitHigh;
-    const unsigned long long hh = inside ? h : base;
-    unsigned long long lo = seedBegin, hi = seedEnd; /* the last seed whose hits begin at or before hh: hitOffsets[seedBegin] <= hh */
-    while (hi - lo > 1u) {
-      const unsigned long long mid = lo + ((hi - lo) >> 1);
-      const bool before = in.hitOffsets[mid] <= hh;
-      lo = before ? mid : lo;
-      hi = before ? hi : mid;
-    }
-    const unsigned long long seedHitBegin = in.hitOffsets[lo], seedHitEnd = in.hitOffsets[lo + 1u];
-    const unsigned length = in.seedLengths ? in.seedLengths[lo] : in.fixedLength, end = in.seedEnds[lo];
-    const bool seedKept = length <= end && (p.maxHitsPerSeed == 0u || seedHitEnd - seedHitBegin <= p.maxHitsPerSeed);
-    /* lane 0 stands at `base`: when its seed is dropped and holds the whole round, the wave goes on behind that seed */
-    const unsigned long long firstEnd = (unsigned long long)__shfl((long long)seedHitEnd, 0, 64);
-    if (!__shfl((int)seedKept, 0, 64) && firstEnd - base >= 64u) {
-      base = firstEnd < hitHigh ? firstEnd : hitHigh;
-      continue;
-    }
-    bool keep = inside && seedKept;
-    unsigned sequence = 0;
-    if (keep && in.sequenceNumbers) {
-      sequence = in.sequenceNumbers[h];
-      keep = sequence != kChainsNone;
-    }
-    const unsigned anchor = end - length;
-    const unsigned long long key = keep ? (in.positions[h] - anchor) ^ kChainsSign : 0ull;
-    visit(keep, sequence, key, anchor, end);
-    base += 64u;
-  }
-}
 
 /* the largest v of the wave's 64 lanes, in every lane: DPP within the rows of 16, the rows' last lanes broadcast onwards */
 __device__ __forceinline__ unsigned waveMax(unsigned v) {
@@ -218,36 +167,13 @@ __device__ __forceinline__ void chainSlot(const DevChainParams &p, ChainsLds<CAP
   }
 }
 
-/* the part of the read's stretch of hits that this wave streams: the stretch in equal contiguous parts, one per wave */
-template <unsigned THREADS>
-__device__ __forceinline__ void chainsWavePart(unsigned long long hitBegin, unsigned long long hitEnd, unsigned long long &low,
-                                               unsigned long long &high) {
-  constexpr unsigned kWaves = THREADS / 64u;
-  const unsigned wave = threadIdx.x >> 6;
-  const unsigned long long part = (hitEnd - hitBegin + kWaves - 1u) / kWaves;
-  low = hitBegin + wave * part;
-  low = low < hitEnd ? low : hitEnd;
-  high = hitEnd - low < part ? hitEnd : low + part;
-}
-
-/* The outputs and the slot arrays where they are needed, not before: the kernels' arguments are 54 words, and the compiler would
- * otherwise load all of them ahead of the loop over the reads and spill scalar registers in the recurrence.  They are read from
- * the kernel's argument segment, of which DevChainParams is the one and only entry in both kernels (a static_assert on their
- * signatures at the end of this file holds that); the empty statement only hides where the pointer comes from, so that the
- * loads stay behind it. */
-typedef const __attribute__((address_space(4))) DevChainParams *KernelChainParams;
-__device__ __forceinline__ KernelChainParams kernelChainParams() {
-  KernelChainParams params = (KernelChainParams)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(params));
-  return params;
-}
-
-/* read r's slots, best slot and kept hits from what LDS holds (all zero and none for a read without chains of its own) */
+/* Read r's slots, best slot and kept hits from what LDS holds (all zero and none for a read without chains of its own).  The
+ * outputs, and the slot arrays in chainsOfRead, where they are used, not before (kernelArguments): the kernels' arguments are 54
+ * words, and the recurrence spills scalar registers when they are loaded ahead of the loop over the reads. */
 template <unsigned CAP>
 __device__ __forceinline__ void storeChains(const DevChainParams &p, const ChainsLds<CAP> &s, unsigned long long r, bool chained,
                                             unsigned keptHits) {
-  const KernelChainParams params = kernelChainParams();
-  const auto &out = params->out;
+  const auto &out = kernelArguments<DevChainParams>()->out;
   const unsigned j = threadIdx.x;
   if (j < p.slots) {
     const unsigned long long at = r * p.slots + j;
@@ -256,14 +182,14 @@ __device__ __forceinline__ void storeChains(const DevChainParams &p, const Chain
     if (out.chainAnchors) out.chainAnchors[at] = has ? s.anchors[j] : 0u;
     if (out.chainReadBegins) out.chainReadBegins[at] = has ? s.readBegin[j] : 0u;
     if (out.chainReadEnds) out.chainReadEnds[at] = has ? s.readEnd[j] : 0u;
-    if (out.chainBeginDiagonals) out.chainBeginDiagonals[at] = has ? (long long)((s.slotLow[j] + s.beginDiagonal[j]) ^ kChainsSign) : 0ll;
-    if (out.chainEndDiagonals) out.chainEndDiagonals[at] = has ? (long long)((s.slotLow[j] + s.endDiagonal[j]) ^ kChainsSign) : 0ll;
+    if (out.chainBeginDiagonals) out.chainBeginDiagonals[at] = has ? (long long)((s.slotLow[j] + s.beginDiagonal[j]) ^ kHitsSign) : 0ll;
+    if (out.chainEndDiagonals) out.chainEndDiagonals[at] = has ? (long long)((s.slotLow[j] + s.endDiagonal[j]) ^ kHitsSign) : 0ll;
   }
   if (j == 0u) {
-    unsigned bestSlot = kChainsNone, bestScore = 0u;
+    unsigned bestSlot = kHitsNone, bestScore = 0u;
     if (chained)
       for (unsigned k = 0; k < p.slots; k++)
-        if (s.anchors[k] != 0u && (bestSlot == kChainsNone || s.score[k] > bestScore)) {
+        if (s.anchors[k] != 0u && (bestSlot == kHitsNone || s.score[k] > bestScore)) {
           bestSlot = k;
           bestScore = s.score[k];
         }
@@ -280,34 +206,29 @@ __device__ bool chainsOfRead(const DevChainParams &p, ChainsLds<CAP> &s, unsigne
   static_assert(CAP % THREADS == 0 && (CAP & (CAP - 1u)) == 0, "a power of two, whole rounds");
   constexpr unsigned kWaves = THREADS / 64u;
   const unsigned tid = threadIdx.x;
-  const AwFmCandidateInputs &in = p.in;
   __syncthreads(); /* the LDS of the read before */
   if (tid == 0u) {
     s.kept = 0ull;
     s.numAnchors = 0u;
   }
   if (tid < kChainsSlots) {
-    const KernelChainParams params = kernelChainParams();
+    const auto params = kernelArguments<DevChainParams>();
     const bool used = tid < p.slots;
-    s.slotSequence[tid] = used ? params->sequences[r * p.slots + tid] : kChainsNone;
-    s.slotLow[tid] = used ? (unsigned long long)params->diagonals[r * p.slots + tid] ^ kChainsSign : 0ull;
+    s.slotSequence[tid] = used ? params->sequences[r * p.slots + tid] : kHitsNone;
+    s.slotLow[tid] = used ? (unsigned long long)params->diagonals[r * p.slots + tid] ^ kHitsSign : 0ull;
     s.slotSpan[tid] = used ? params->spans[r * p.slots + tid] : 0u;
     s.slotBegin[tid] = 0u;
     s.slotEnd[tid] = 0u;
     s.anchors[tid] = 0u;
   }
-  /* check: nothing is read through an offset that was not compared with its array's size first */
-  const unsigned long long seedBegin = in.readSeedOffsets[r], seedEnd = in.readSeedOffsets[r + 1u];
-  bool malformed = seedBegin > seedEnd || seedEnd > in.numSeeds || seedEnd - seedBegin >= (1ull << 32);
-  if (!malformed)
-    for (unsigned long long q = seedBegin + tid; q < seedEnd; q += THREADS)
-      malformed |= in.hitOffsets[q] > in.hitOffsets[q + 1u] || in.hitOffsets[q + 1u] > in.numHits;
-  malformed = __syncthreads_or(malformed);
+  /* check */
+  unsigned long long seedBegin, seedEnd;
+  bool malformed = __syncthreads_or(readMalformed<THREADS>(p.in, r, seedBegin, seedEnd));
   if (!malformed) { /* two slots of one sequence whose intervals intersect */
     bool intersect = false;
     for (unsigned q = tid; q < kChainsSlots * kChainsSlots; q += THREADS) {
       const unsigned a = q / kChainsSlots, b = q % kChainsSlots;
-      if (a >= b || s.slotSequence[a] == kChainsNone || s.slotSequence[a] != s.slotSequence[b]) continue;
+      if (a >= b || s.slotSequence[a] == kHitsNone || s.slotSequence[a] != s.slotSequence[b]) continue;
       const unsigned long long lowA = s.slotLow[a], lowB = s.slotLow[b];
       const unsigned long long highA = lowA + s.slotSpan[a] < lowA ? ~0ull : lowA + s.slotSpan[a];
       const unsigned long long highB = lowB + s.slotSpan[b] < lowB ? ~0ull : lowB + s.slotSpan[b];
@@ -316,31 +237,24 @@ __device__ bool chainsOfRead(const DevChainParams &p, ChainsLds<CAP> &s, unsigne
     malformed = __syncthreads_or(intersect);
   }
   if (malformed) {
-    storeChains(p, s, r, false, kChainsMalformed);
+    storeChains(p, s, r, false, kHitsMalformed);
     return false;
   }
   /* gather */
-  const unsigned long long hitBegin = seedBegin < seedEnd ? in.hitOffsets[seedBegin] : 0ull;
-  const unsigned long long hitEnd = seedBegin < seedEnd ? in.hitOffsets[seedEnd] : 0ull;
   unsigned long long low, high;
-  chainsWavePart<THREADS>(hitBegin, hitEnd, low, high);
-  const unsigned lane = tid & 63u;
-  visitChainHits(p, seedBegin, seedEnd, low, high, [&](bool keep, unsigned sequence, unsigned long long key, unsigned anchor, unsigned end) {
+  wavePart<THREADS>(p.in, seedBegin, seedEnd, low, high);
+  visitHits(p,seedBegin, seedEnd, low, high, [&](bool keep, unsigned sequence, unsigned long long key, unsigned anchor, unsigned end) {
     const unsigned long long keptMask = __ballot(keep);
     if (keptMask == 0ull) return;
-    unsigned slot = kChainsNone;
+    unsigned slot = kHitsNone;
     if (keep)
       for (unsigned j = 0; j < p.slots; j++)
         if (s.slotSequence[j] == sequence && key >= s.slotLow[j] && key - s.slotLow[j] <= s.slotSpan[j]) slot = j; /* (at most one) */
-    const unsigned long long mask = __ballot(slot != kChainsNone);
+    const unsigned long long mask = __ballot(slot != kHitsNone);
     const int leader = __ffsll((long long)keptMask) - 1;
-    unsigned at = 0u;
-    if ((int)lane == leader) {
-      atomicAdd(&s.kept, (unsigned long long)__popcll(keptMask));
-      if (mask != 0ull) at = atomicAdd(&s.numAnchors, (unsigned)__popcll(mask));
-    }
-    at = (unsigned)__shfl((int)at, leader, 64) + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
-    if (slot != kChainsNone && at < CAP) {
+    (void)waveAppend(&s.kept, keptMask, leader);
+    const unsigned at = waveAppend(&s.numAnchors, mask, leader);
+    if (slot != kHitsNone && at < CAP) {
       s.hi[at] = ((unsigned long long)slot << 32) | end;
       s.lo[at] = ((key - s.slotLow[slot]) << 32) | (end - anchor);
     }
@@ -348,35 +262,22 @@ __device__ bool chainsOfRead(const DevChainParams &p, ChainsLds<CAP> &s, unsigne
   __syncthreads();
   const unsigned long long kept = s.kept;
   if (kept > kChainsGroupLimit) {
-    storeChains(p, s, r, false, kept > kChainsSaturated ? kChainsSaturated : (unsigned)kept);
+    storeChains(p, s, r, false, keptHitsWord(kept));
     return false;
   }
   const unsigned n = s.numAnchors; /* <= kept */
   if (n > limit) return true;
-  /* sort */
-  unsigned padded = 2u;
-  while (padded < n) padded <<= 1;
-  for (unsigned i = n + tid; i < padded; i += THREADS) {
-    s.hi[i] = ~0ull;
-    s.lo[i] = ~0ull;
-  }
-  __syncthreads();
-  if (n > 1u)
-    for (unsigned k = 2u; k <= padded; k <<= 1)
-      for (unsigned j = k >> 1; j != 0u; j >>= 1) {
-        for (unsigned t = tid; t < (padded >> 1); t += THREADS) {
-          const unsigned a = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), b = a | j;
-          const unsigned long long ha = s.hi[a], hb = s.hi[b], la = s.lo[a], lb = s.lo[b];
-          const bool greater = ha != hb ? ha > hb : la > lb;
-          if (greater == ((a & k) == 0u)) {
-            s.hi[a] = hb;
-            s.hi[b] = ha;
-            s.lo[a] = lb;
-            s.lo[b] = la;
-          }
-        }
-        __syncthreads();
-      }
+  /* sort: by (hi, lo) */
+  struct Anchor {
+    unsigned long long hi, lo;
+  };
+  sortLds<THREADS>(
+      n, Anchor{~0ull, ~0ull}, [&](unsigned i) { return Anchor{s.hi[i], s.lo[i]}; },
+      [&](unsigned i, const Anchor &x) {
+        s.hi[i] = x.hi;
+        s.lo[i] = x.lo;
+      },
+      [](const Anchor &x, const Anchor &y) { return x.hi != y.hi ? x.hi > y.hi : x.lo > y.lo; });
   /* the slots' ranges */
   for (unsigned i = tid; i < n; i += THREADS) {
     const unsigned slot = (unsigned)(s.hi[i] >> 32);
@@ -391,30 +292,24 @@ __device__ bool chainsOfRead(const DevChainParams &p, ChainsLds<CAP> &s, unsigne
   return false;
 }
 
-/* the wave tier: one wave per read; what it cannot hold goes onto the worklist */
+/* the wave tier: what it cannot hold goes onto the worklist */
 __global__ void __launch_bounds__(kChainsWaveThreads) readChainsWaveKernel(const DevChainParams p) {
   __shared__ ChainsLds<kChainsWaveLimit> s;
-  for (unsigned long long r = blockIdx.x; r < p.numReads; r += gridDim.x)
-    if (chainsOfRead<kChainsWaveThreads, kChainsWaveLimit>(p, s, r, p.waveLimit) && threadIdx.x == 0u)
-      p.worklist[atomicAdd(p.counter, 1ull)] = (unsigned)r; /* (at most one entry per read: numReads entries hold them) */
+  waveTier(p, blockIdx.x, gridDim.x, [&](unsigned long long r) { return chainsOfRead<kChainsWaveThreads, kChainsWaveLimit>(p, s, r, p.waveLimit); });
 }
 
-/* the workgroup tier: the reads of the worklist, whose length is read here; its LDS is dynamic (kChainsGroupLdsBytes) */
+/* the workgroup tier; its LDS is dynamic (kChainsGroupLdsBytes) */
 __global__ void __launch_bounds__(kChainsGroupThreads) readChainsGroupKernel(const DevChainParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char chainsGroupLds[];
   ChainsLds<kChainsGroupLimit> &s = *reinterpret_cast<ChainsLds<kChainsGroupLimit> *>(chainsGroupLds);
-  const unsigned long long have = *p.counter, listed = have < p.numReads ? have : p.numReads;
-  for (unsigned long long w = blockIdx.x; w < listed; w += gridDim.x) {
-    const unsigned long long r = p.worklist[w];
-    if (r < p.numReads) (void)chainsOfRead<kChainsGroupThreads, kChainsGroupLimit>(p, s, r, kChainsGroupLimit);
-  }
+  groupTier(p, blockIdx.x, gridDim.x, [&](unsigned long long r) { return chainsOfRead<kChainsGroupThreads, kChainsGroupLimit>(p, s, r, kChainsGroupLimit); });
 }
 
-/* kernelChainParams() reads the argument segment as a DevChainParams: right only while that struct is the one argument of both
+/* kernelArguments() reads the argument segment as a DevChainParams: right only while that struct is the one argument of both
  * kernels, by value, hence at offset 0.  A change of either signature stops the build here. */
 static_assert(std::is_same<decltype(&readChainsWaveKernel), void (*)(DevChainParams)>::value &&
                   std::is_same<decltype(&readChainsGroupKernel), void (*)(DevChainParams)>::value,
-              "kernelChainParams() assumes DevChainParams is the kernels' only argument");
+              "kernelArguments() assumes DevChainParams is the kernels' only argument");
 
 }  // namespace
 

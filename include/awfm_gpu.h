@@ -450,6 +450,7 @@ enum AwFmReturnCode awfmGpuLocalPositions(AwFmGpuIndex *g, const uint64_t *dPosi
  * AwFmIllegalPositionError.
  *
  * awfmReadCandidates: on the host over `threads` threads of the library's pool, one read at a time: collect, qsort, scan, select.
+ * (What a kept hit is, is written once per side for this call and for "read chains": csrc/awfm_hits.h, csrc/awfm_hits_kernel.h.)
  * awfmGpuReadCandidates (csrc/awfm_candidates_kernel.h): the same on device arrays (both structs live on the host and hold
  * device addresses); asynchronous on `stream`, no host wait, no allocation, none of the handle's scratch slots: two streams may
  * run it on one image at once, each with its own dScratch of awfmGpuReadCandidatesScratchBytes(numReads) bytes.  One wave per read

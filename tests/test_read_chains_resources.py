@@ -5,39 +5,24 @@ has a private segment, and the two tiers stay within the LDS and the registers t
 few static words (<= 80 KB in all: two workgroups per CU) and 128 VGPRs (its two workgroups of eight waves are four waves per
 SIMD)."""
 import os
-import re
-import subprocess
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "avxwindowfmindex_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernel_metadata_common as km  # noqa: E402
 
 DECLARED = {"readChainsWaveKernel": {"lds": "kChainsWaveLdsBytes", "lds_at_most": 8 * 1024, "vgpr": 64, "threads": "kChainsWaveThreads", "dynamic": False},
             "readChainsGroupKernel": {"lds": "kChainsGroupLdsBytes", "lds_at_most": 80 * 1024, "vgpr": 128, "threads": "kChainsGroupThreads", "dynamic": True}}
 
 
 @pytest.fixture(scope="module")
-def metadata(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    out = tmp_path_factory.mktemp("isa") / "awfm_gpu_chains.s"
-    subprocess.check_call([HIPCC, "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + CSRC, "-Wno-unused-function", "-S", "--cuda-device-only", "-o", str(out),
-                           os.path.join(CSRC, "awfm_gpu_chains.hip")], stderr=subprocess.DEVNULL)
-    meta = {}
-    for m in re.finditer(r"- \.agpr_count:.*\n\s+\.args:\n((?:.*\n)*?)\s+\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.max_flat_workgroup_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?"
-                         r"\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n)*?"
-                         r"\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", out.read_text()):
-        meta[m.group(4)] = {"dynamic": "hidden_dynamic_lds_size" in m.group(1), "lds": int(m.group(2)), "threads": int(m.group(3)),
-                            "scratch": int(m.group(5)), "sgpr_spill": int(m.group(6)), "vgpr": int(m.group(7)), "spill": int(m.group(8))}
-    return meta
+def metadata():
+    return km.metadata("awfm_gpu_chains.hip")
 
 
 def _constant(name):
-    header = open(os.path.join(CSRC, "awfm_chains_kernel.h")).read()
-    return int(re.search(r"constexpr unsigned " + name + r" = (\d+);", header).group(1))
+    return km.constant(name, "awfm_chains_kernel.h")
 
 
 def test_no_kernel_of_the_unit_spills_or_uses_scratch(metadata):
