@@ -67,10 +67,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
   __shared__ unsigned long long sLead[4][kAminoSlots];
   __shared__ unsigned sNum[4][kAminoSlots];
   __shared__ pos_t sSp[4][kAminoSlots], sEp[4][kAminoSlots];
-  constexpr unsigned kHitBuffer = 32;
-  __shared__ unsigned sHitKmers[4][kHitBuffer];
-  __shared__ unsigned long long sHitRanges[4][kHitBuffer][2];
-  __shared__ unsigned sHitLeft[4], sWavesDone;
+  __shared__ HitList<4> sHits;
+  __shared__ unsigned sWavesDone;
   if (!lookupChosen(sampleAlive, samples, true)) return; /* this batch is the general kernel's (uniform) */
   const bool LIST = sparse.count != nullptr;
   if (threadIdx.x == 0) sWavesDone = 0u;
@@ -79,49 +77,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
   stageMaskTable(sMask);
   __syncthreads();
   const unsigned DK = ix.deepK;
-  constexpr unsigned kLoads = (K + 1u + 3u) / 4u;
   const unsigned shift = (unsigned)((unsigned long long)chars & 3ull);
-  typedef const Dwords4 __attribute__((address_space(1))) *GlobalDwords4;
   const unsigned lane = threadIdx.x & 63u, gl = threadIdx.x % G;
   const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   unsigned hitFill = 0, keptHere = 0; /* wave-uniform */
-  auto flushHits = [&]() {
-    if (hitFill != 0u) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      unsigned listBase = 0;
-      if (lane == 0) listBase = atomicAdd(sparse.count, hitFill);
-      listBase = (unsigned)__builtin_amdgcn_readfirstlane((int)listBase);
-      if (lane < hitFill && listBase + lane < sparse.cap) {
-        sparse.kmers[listBase + lane] = sHitKmers[w][lane];
-        sparse.ranges[listBase + lane] = make_ulonglong2(sHitRanges[w][lane][0], sHitRanges[w][lane][1]);
-      }
-      __builtin_amdgcn_wave_barrier();
-      hitFill = 0;
-    }
-  };
   const unsigned long long waveStride = 4ull * gridDim.x * 256ull;
   for (unsigned long long tw = 4ull * ((unsigned long long)blockIdx.x * 256ull + (threadIdx.x & ~63u)); tw < numQueries; tw += waveStride) {
     const unsigned long long t = tw + 4ull * lane;
     unsigned idx[4];
     unsigned long long lead[4];
     bool bad[4];
-    if (t * K + 16ull * kLoads <= numQueries * K) { /* the 16-byte loads from the aligned-down start stay inside the batch */
-      const GlobalDwords4 from = (GlobalDwords4)(((unsigned long long)chars + t * K) & ~3ull);
-      unsigned dw[kLoads * 4u + 1u];
-#pragma unroll
-      for (unsigned j = 0; j < kLoads; j++) {
-        const Dwords4 q = from[j];
-        dw[4u * j] = q.x;
-        dw[4u * j + 1u] = q.y;
-        dw[4u * j + 2u] = q.z;
-        dw[4u * j + 3u] = q.w;
-      }
-      dw[kLoads * 4u] = 0u;
+    if (fourAligned<K>(t, numQueries)) {
       unsigned al[K + 1u]; /* the 4 K bytes at dword alignment */
-#pragma unroll
-      for (unsigned j = 0; j < K; j++) al[j] = __builtin_amdgcn_alignbyte(dw[j + 1u], dw[j], shift);
-      al[K] = 0u;
+      alignedFour<K>(chars, shift, t, al);
       auto byteAt = [&](unsigned b) -> unsigned { return (al[b >> 2] >> (8u * (b & 3u))) & 0xFFu; }; /* compile-time b after unrolling */
 #pragma unroll
       for (unsigned i = 0; i < 4u; i++) aminoDecode<K>(sAmino, byteAt, i, DK, idx[i], lead[i], bad[i]);
@@ -205,18 +173,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
         const bool gone = live && (sp > ep || pos < 0);
         const bool hit = gone && gl == 0 && sp <= ep;
         if (LIST) {
-          const unsigned long long hitMask = __ballot(hit);
-          if (hitMask != 0ull) { /* wave-uniform; at most 16 hits an iteration */
-            const unsigned hits = (unsigned)__builtin_amdgcn_readfirstlane((int)__popcll(hitMask));
-            if (hit) {
-              const unsigned at = hitFill + (unsigned)__popcll(hitMask & ((1ull << lane) - 1ull));
-              sHitKmers[w][at] = index;
-              sHitRanges[w][at][0] = (unsigned long long)sp;
-              sHitRanges[w][at][1] = (unsigned long long)ep;
-            }
-            hitFill = (unsigned)__builtin_amdgcn_readfirstlane((int)(hitFill + hits));
-          }
-          if (hitFill + kGroups > kHitBuffer) flushHits();
+          sHits.template append<G>(sparse, w, lane, hitFill, hit, index, (unsigned long long)sp, (unsigned long long)ep);
         } else if (hit) {
           if (ranges) ranges[index] = make_ulonglong2((unsigned long long)sp, (unsigned long long)ep);
           if (counts) counts[index] = (unsigned)(ep - sp + (pos_t)1);
@@ -236,32 +193,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
     }
   }
   if (lane == 0 && keptHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u], keptHere);
-  if (LIST) { /* the waves' leftovers in one reservation, as in orderedSearchKernel */
-    if (lane == 0) sHitLeft[w] = hitFill;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    unsigned arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&sWavesDone, 1u);
-    arrived = (unsigned)__builtin_amdgcn_readfirstlane((int)arrived);
-    if (arrived == 3u) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      unsigned total = 0;
-      for (unsigned v = 0; v < 4u; v++) total += sHitLeft[v];
-      if (total != 0u) {
-        unsigned listBase = 0;
-        if (lane == 0) listBase = atomicAdd(sparse.count, total);
-        listBase = (unsigned)__builtin_amdgcn_readfirstlane((int)listBase);
-        unsigned before = 0;
-        for (unsigned v = 0; v < 4u; v++) {
-          const unsigned n = sHitLeft[v];
-          if (lane < n && listBase + before + lane < sparse.cap) {
-            sparse.kmers[listBase + before + lane] = sHitKmers[v][lane];
-            sparse.ranges[listBase + before + lane] = make_ulonglong2(sHitRanges[v][lane][0], sHitRanges[v][lane][1]);
-          }
-          before += n;
-        }
-      }
-    }
-  }
+  if (LIST) sHits.finish(sparse, w, lane, hitFill, sWavesDone);
 }
 
 }  // namespace

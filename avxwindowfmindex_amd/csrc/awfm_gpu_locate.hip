@@ -14,6 +14,7 @@
 
 #include "awfm_device.h"
 #include "awfm_search_kernel.h"
+#include "awfm_search_parts_kernel.h"
 #include "awfm_locate_kernel.h"
 
 namespace {
@@ -75,18 +76,7 @@ __global__ void __launch_bounds__(kScanThreads)
     vals[k] = base + k < n ? scanInput<SOURCE>(in, base + k) : 0ull;
     sum += vals[k];
   }
-  /* inclusive scan of the per-thread sums inside the wave */
-  unsigned long long incl = sum;
-  const unsigned lane = threadIdx.x & 63u;
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long up = __shfl_up(incl, d, 64);
-    if (lane >= (unsigned)d) incl += up;
-  }
-  if (lane == 63u) sWave[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  unsigned long long waveOffset = 0;
-  for (unsigned w = 0; w < (threadIdx.x >> 6); w++) waveOffset += sWave[w];
-  unsigned long long running = (tileOffsets ? tileOffsets[blockIdx.x] : 0ull) + waveOffset + incl - sum;
+  unsigned long long running = (tileOffsets ? tileOffsets[blockIdx.x] : 0ull) + blockInclusiveScan(sum, sWave) - sum;
   for (int k = 0; k < kScanItems; k++) {
     if (base + k < n) out[base + k] = running;
     running += vals[k];
@@ -110,19 +100,8 @@ __global__ void __launch_bounds__(kScanSmallThreads)
     vals[k] = base + k < n ? scanInput<SOURCE>(in, base + k) : 0ull;
     sum += vals[k];
   }
-  unsigned long long incl = sum;
-  const unsigned lane = threadIdx.x & 63u;
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long up = __shfl_up(incl, d, 64);
-    if (lane >= (unsigned)d) incl += up;
-  }
-  if (lane == 63u) sWave[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  unsigned long long running = incl - sum, total = 0;
-  for (unsigned w = 0; w < kScanSmallThreads / 64; w++) {
-    running += w < (threadIdx.x >> 6) ? sWave[w] : 0ull;
-    total += sWave[w];
-  }
+  unsigned long long running = blockInclusiveScan(sum, sWave) - sum, total = 0;
+  for (unsigned w = 0; w < kScanSmallThreads / 64; w++) total += sWave[w];
 #pragma unroll
   for (int k = 0; k < kScanSmallItems; k++) {
     if (base + k < n) out[base + k] = running;
@@ -364,20 +343,10 @@ __global__ void __launch_bounds__(kListTailThreads)
         range = sRange[j];
         len = range.x <= range.y ? range.y - range.x + 1ull : 0ull;
       }
-      unsigned long long incl = len;
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long up = __shfl_up(incl, d, 64);
-        if (lane >= (unsigned)d) incl += up;
-      }
-      if (lane == 63u) sWave[wave] = incl;
       if (tid == 0) sHugeN = 0u;
-      __syncthreads();
-      unsigned long long before = hitBase, chunk = 0;
-      for (unsigned v = 0; v < kListTailThreads / 64; v++) {
-        before += v < wave ? sWave[v] : 0ull;
-        chunk += sWave[v];
-      }
-      const unsigned long long off = before + incl - len;
+      const unsigned long long off = hitBase + blockInclusiveScan(len, sWave) - len;
+      unsigned long long chunk = 0;
+      for (unsigned v = 0; v < kListTailThreads / 64; v++) chunk += sWave[v];
       if (r < m) {
         outKmers[rankBase + r] = key;
         outRanges[rankBase + r] = range;

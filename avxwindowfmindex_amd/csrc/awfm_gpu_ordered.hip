@@ -2006,18 +2006,10 @@ __global__ void __launch_bounds__(1024) rankBlockScanKernel(unsigned *__restrict
   for (unsigned base = 0; base < numBlocks; base += 1024u) {
     const unsigned e = base + threadIdx.x;
     const unsigned v = e < numBlocks ? blockCount[e] : 0u;
-    unsigned incl = v;
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned up = __shfl_up(incl, off);
-      if ((int)(threadIdx.x & 63u) >= off) incl += up;
-    }
-    if ((threadIdx.x & 63u) == 63u) sWave[threadIdx.x >> 6] = incl;
+    const unsigned incl = sCarry + blockInclusiveScan(v, sWave);
+    if (e < numBlocks) blockCount[e] = incl - v;
     __syncthreads();
-    unsigned before = sCarry;
-    for (unsigned w = 0; w < (threadIdx.x >> 6); w++) before += sWave[w];
-    if (e < numBlocks) blockCount[e] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023u) sCarry = before + incl;
+    if (threadIdx.x == 1023u) sCarry = incl;
     __syncthreads();
   }
 }

@@ -122,10 +122,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80)))
   __shared__ unsigned char sLeft[4][kMixedSlots]; /* characters to go: at most 32 */
   __shared__ unsigned char sOdd[4][kMixedSlots]; /* the slots whose k-mer has one last single step to take */
   static_assert(kMixedSlots <= 256u, "slot numbers are bytes");
-  constexpr unsigned kHitBuffer = 32;
-  __shared__ unsigned sHitKmers[4][kHitBuffer];
-  __shared__ unsigned long long sHitRanges[4][kHitBuffer][2];
-  __shared__ unsigned sHitLeft[4], sWavesDone;
+  __shared__ HitList<4> sHits;
+  __shared__ unsigned sWavesDone;
   if (!lookupChosen(sampleAlive, samples, true)) return; /* this batch is the 16-byte-record path's (uniform) */
   const bool PAIR = ix.pairBlocks != nullptr && (useNext & 2u) == 0u;
   const bool LIST = sparse.count != nullptr;
@@ -146,21 +144,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80)))
   const unsigned lane = threadIdx.x & 63u, gl = threadIdx.x % G, firstSlice = gl;
   const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   unsigned hitFill = 0, keptHere = 0; /* wave-uniform */
-  auto flushHits = [&]() {
-    if (hitFill != 0u) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      unsigned listBase = 0;
-      if (lane == 0) listBase = atomicAdd(sparse.count, hitFill);
-      listBase = (unsigned)__builtin_amdgcn_readfirstlane((int)listBase);
-      if (lane < hitFill && listBase + lane < sparse.cap) {
-        sparse.kmers[listBase + lane] = sHitKmers[w][lane];
-        sparse.ranges[listBase + lane] = make_ulonglong2(sHitRanges[w][lane][0], sHitRanges[w][lane][1]);
-      }
-      __builtin_amdgcn_wave_barrier();
-      hitFill = 0;
-    }
-  };
   const unsigned long long waveStride = 1024ull * gridDim.x;
   for (unsigned long long tw = 1024ull * blockIdx.x + 256ull * w; tw < numQueries; tw += waveStride) {
     unsigned long long codes[4];
@@ -283,18 +266,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80)))
       };
       auto report = [&](const bool hit) { /* wave-uniform call; hit: in lane 0 of the groups that have one */
         if (LIST) {
-          const unsigned long long hitMask = __ballot(hit);
-          if (hitMask != 0ull) { /* wave-uniform; at most 16 hits */
-            const unsigned hits = (unsigned)__builtin_amdgcn_readfirstlane((int)__popcll(hitMask));
-            if (hit) {
-              const unsigned at = hitFill + (unsigned)__popcll(hitMask & ((1ull << lane) - 1ull));
-              sHitKmers[w][at] = index;
-              sHitRanges[w][at][0] = (unsigned long long)sp;
-              sHitRanges[w][at][1] = (unsigned long long)ep;
-            }
-            hitFill = (unsigned)__builtin_amdgcn_readfirstlane((int)(hitFill + hits));
-          }
-          if (hitFill + kGroups > kHitBuffer) flushHits();
+          sHits.template append<G>(sparse, w, lane, hitFill, hit, index, (unsigned long long)sp, (unsigned long long)ep);
         } else if (hit && !WHOLE) {
           if (ranges) ranges[index] = make_ulonglong2((unsigned long long)sp, (unsigned long long)ep);
           if (counts) counts[index] = (unsigned)(ep - sp + (pos_t)1);
@@ -303,21 +275,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80)))
       if (live) take();
       const int stepChars = PAIR ? 2 : 1;
       while (__ballot(live) != 0ull) { /* wave-uniform */
-        if (live && pos >= stepChars - 1) { /* (a k-mer in a group is alive: sp <= ep) */
-          if (PAIR) {
-            const unsigned c2 = (unsigned)rem & 3u, c1 = (unsigned)(rem >> 2) & 3u;
-            if (pairSearchStep<NARROW>(ix, sPairC, sPairSuper, sMask, gl, c1 * 4u + c2, sp, ep) == kPairFlagged) {
-              nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, c2, sp, ep);
-              if (sp <= ep) nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, c1, sp, ep);
-            }
-            pos -= 2;
-            rem >>= 4;
-          } else {
-            nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, (unsigned)rem & 3u, sp, ep);
-            pos--;
-            rem >>= 2;
-          }
-        }
+        /* (a k-mer in a group is alive: sp <= ep) */
+        if (live && pos >= stepChars - 1) hitsStep<G, NARROW>(PAIR, ix, sC, sSuper, sMask, sPairC, sPairSuper, gl, firstSlice, rem, pos, sp, ep);
         /* what the step (or the slot as it was taken) leaves: the group is done with its k-mer when the range is empty, when
          * no character is left (a hit), or when one is left that the pair steps cannot take (parked) */
         const bool gone = live && (sp > ep || pos < stepChars - 1);
@@ -391,32 +350,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80)))
     }
   }
   if (lane == 0 && keptHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u], keptHere);
-  if (LIST) { /* the waves' leftovers in one reservation, as in orderedSearchKernel */
-    if (lane == 0) sHitLeft[w] = hitFill;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    unsigned arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&sWavesDone, 1u);
-    arrived = (unsigned)__builtin_amdgcn_readfirstlane((int)arrived);
-    if (arrived == 3u) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      unsigned total = 0;
-      for (unsigned v = 0; v < 4u; v++) total += sHitLeft[v];
-      if (total != 0u) {
-        unsigned listBase = 0;
-        if (lane == 0) listBase = atomicAdd(sparse.count, total);
-        listBase = (unsigned)__builtin_amdgcn_readfirstlane((int)listBase);
-        unsigned before = 0;
-        for (unsigned v = 0; v < 4u; v++) {
-          const unsigned n = sHitLeft[v];
-          if (lane < n && listBase + before + lane < sparse.cap) {
-            sparse.kmers[listBase + before + lane] = sHitKmers[v][lane];
-            sparse.ranges[listBase + before + lane] = make_ulonglong2(sHitRanges[v][lane][0], sHitRanges[v][lane][1]);
-          }
-          before += n;
-        }
-      }
-    }
-  }
+  if (LIST) sHits.finish(sparse, w, lane, hitFill, sWavesDone);
 }
 
 /* how many of `samples` k-mers at a fixed stride are not settled by their table entry (survivors, and the general kernel's):

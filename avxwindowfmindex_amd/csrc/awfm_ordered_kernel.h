@@ -34,65 +34,9 @@
 #define AWFM_ORDERED_KERNEL_H
 
 #include "awfm_search_kernel.h"
-#include "awfm_pair.h"
+#include "awfm_search_parts_kernel.h"
 
 namespace {
-
-/* 4 characters -> 4 two-bit codes (first character in bits 7..6) and 4 "not a,c,g,t,u" flags (bit i = character i);
- * same SWAR decode as the window decode of searchKernel */
-__device__ __forceinline__ void decodeWord(unsigned word, unsigned &packed, unsigned &badBits) {
-  unsigned t = (word >> 1) & 0x03030303u;
-  t ^= (t >> 1) & 0x01010101u;
-  const unsigned b0 = t & 0x01010101u, b1 = (t >> 1) & 0x01010101u, b01 = b0 & b1;
-  const unsigned expect = 0x61616161u + (b0 << 1) + b1 * 6u + b01 * 11u; /* 'a','c','g','t' */
-  unsigned diff = ((word | 0x20202020u) ^ expect) & ~b01;
-  diff |= diff >> 4;
-  diff |= diff >> 2;
-  diff |= diff >> 1;
-  diff &= 0x01010101u;
-  badBits = (diff & 1u) | ((diff >> 7) & 2u) | ((diff >> 14) & 4u) | ((diff >> 21) & 8u);
-  packed = ((t & 3u) << 6) | ((t >> 4) & 0x30u) | ((t >> 14) & 0x0Cu) | (t >> 24);
-}
-
-/* The same for a kernel that only asks whether ANY character of a k-mer is not a,c,g,t,u: the expected letters come from
- * one byte permute ('a','c','g','t' selected by the codes), and the differences of the characters that count
- * (`countMask`: 0xFF per character of the k-mer in this word) are OR-ed into `diffs` as they are.  decodeWord: 35 VALU
- * instructions per word, this: 19 -- encodeCodes4Kernel was bound by its VALU instructions (94 % of its cycles), not by its
- * 2.9 GB. */
-__device__ __forceinline__ void decodeWordAny(unsigned word, unsigned countMask, unsigned &packed, unsigned &diffs) {
-  unsigned t = (word >> 1) & 0x03030303u;
-  t ^= (t >> 1) & 0x01010101u;
-  const unsigned b01 = t & (t >> 1) & 0x01010101u;                   /* code 3: 't' or 'u' (they differ in bit 0) */
-  const unsigned expect = __builtin_amdgcn_perm(0u, 0x74676361u, t); /* byte i = "acgt"[code i] */
-  diffs |= ((word | 0x20202020u) ^ expect) & ~b01 & countMask;
-  packed = ((t & 3u) << 6) | ((t >> 4) & 0x30u) | ((t >> 14) & 0x0Cu) | (t >> 24);
-}
-
-/* 2-bit codes (last character in bits 1..0) and ambiguity mask (bit i = character i is not a,c,g,t,u) of the `len`
- * (1..32) ASCII characters at chars + start: the aligned dwords that hold them, a dword only read when it contains one */
-__device__ __forceinline__ void decodeKmer(const unsigned char *__restrict__ chars, unsigned long long start, unsigned len,
-                                           unsigned long long &codes, unsigned &bad) {
-  const unsigned long long at = (unsigned long long)chars + start;
-  /* (an integer turned pointer is a generic one, read by FLAT loads: say that it is global memory) */
-  typedef const unsigned __attribute__((address_space(1))) *GlobalWords;
-  const GlobalWords first = (GlobalWords)(at & ~3ull);
-  const unsigned shift = (unsigned)at & 3u;
-  const unsigned numDwords = (shift + len + 3u) >> 2;
-  unsigned dw[9];
-#pragma unroll
-  for (int j = 0; j < 9; j++) dw[j] = (unsigned)j < numDwords ? first[j] : 0u;
-  codes = 0;
-  bad = 0;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    unsigned packed = 0, badBits = 0;
-    if (4u * j < len) decodeWord(__builtin_amdgcn_alignbyte(dw[j + 1], dw[j], shift), packed, badBits);
-    codes = (codes << 8) | packed;
-    bad |= badBits << (4 * j);
-  }
-  codes >>= 2u * (32u - len); /* character 0 was in bits 63..62: now the last character is in bits 1..0 */
-  bad &= len >= 32u ? ~0u : ((1u << len) - 1u);
-}
 
 /* leading 15 bits of the string the search of a k-mer starts from: its last `depth` characters (the table index), or the
  * whole k-mer when it starts from a letter range -- where its search lands in the BWT */
@@ -137,7 +81,6 @@ __host__ __device__ inline unsigned orderStartDepth(unsigned len, unsigned seedK
  * 10^8 21-mers: 2.9 + 1.6 GB of memory traffic instead of 3.1 + 0.2 + 2 x 2.0 GB.
  */
 constexpr unsigned kBucketBitsMax = 11; /* 2048 buckets (+ 1 for the k-mers left to the general kernel) */
-constexpr unsigned kPartitionThreads = 1024, kPartitionItems = 16, kPartitionTile = kPartitionThreads * kPartitionItems;
 constexpr unsigned long long kCodeGeneral = 1ull << 63; /* a code word of a k-mer the ordered kernel does not cover */
 /* counters[bin] += 1 for the lanes with `valid`, returning each one's rank.  A batch that arrives sorted puts every lane of a
  * wave -- every k-mer of a tile -- into the same bin: 64 LDS atomics on one word per instruction, serialised (a sorted
@@ -157,20 +100,9 @@ __device__ __forceinline__ unsigned ldsCountRank(unsigned *counters, unsigned bi
   return valid ? atomicAdd(&counters[bin], 1u) : 0u;
 }
 
-constexpr unsigned long long kCodeNone = 1ull << 62;    /* no k-mer: an unused slot of a block encodeLookupKernel reserved */
-constexpr unsigned kLookupBlock = 64;                   /* slots a wave of encodeLookupKernel reserves at a time */
+constexpr unsigned long long kCodeNone = 1ull << 62;    /* no k-mer: an unused slot of a block lookupSearchKernel reserved */
+constexpr unsigned kLookupBlock = 64;                   /* slots a wave of lookupSearchKernel reserves at a time */
 constexpr unsigned kShareCountStride = 64;              /* words between the shares' slot counters (a line each) */
-/* The batch is cut into 8 SHARES of whole tiles, one per XCD (workgroup b works on share b % 8, the XCD it runs on under
- * round-robin dispatch: for speed only), and every bucket's place in the order into 8 sub-runs, share by share.  The
- * workgroups that append to a sub-run are then on ONE XCD: its L2 sees all the 64-byte runs that make up a line and writes
- * the line once, and the cursor it bumps is not shared with the other seven.  (One run area per bucket for the whole chip:
- * 1.2 GB written for 0.8 GB of records.) */
-constexpr unsigned kShares = 8;
-__host__ __device__ inline unsigned long long shareSize(unsigned long long numQueries) {
-  const unsigned long long perShare = (numQueries + kShares - 1ull) / kShares;
-  return (perShare + kPartitionTile - 1ull) / kPartitionTile * kPartitionTile;
-}
-
 struct BucketFormat {
   unsigned depth;      /* characters the table lookup consumes */
   unsigned bucketBits; /* min(kBucketBitsMax, 2 * depth): leading bits of the table index */
@@ -216,9 +148,7 @@ __global__ void __launch_bounds__(256)
   const unsigned bins = (1u << f.bucketBits) + 1u;
   for (unsigned e = threadIdx.x; e < bins; e += 256u) sHist[e] = 0u;
   __syncthreads();
-  const unsigned share = blockIdx.x % kShares, localBlock = blockIdx.x / kShares, localGrid = gridDim.x / kShares;
-  const unsigned long long size = shareSize(numQueries), first = size * share;
-  const unsigned long long last = first + size < numQueries ? first + size : numQueries;
+  const auto [share, localBlock, localGrid, first, last] = shareRange(numQueries);
   for (unsigned long long t = first + (unsigned long long)localBlock * 256ull + threadIdx.x; t < last; t += (unsigned long long)localGrid * 256ull) {
     unsigned long long codes = 0;
     unsigned bad = 0;
@@ -236,74 +166,24 @@ __global__ void __launch_bounds__(256)
     if (sHist[e]) atomicAdd(&hist[share * binsPad + e], sHist[e]);
 }
 
-/* pass 1 for ASCII k-mers of a length known at compile time: a thread takes FOUR consecutive k-mers -- 4 K bytes, i.e.
- * K whole dwords wherever the batch starts -- with 16-byte loads, brings them to dword alignment once (the misalignment of
- * the batch is the same for every thread), and takes the four k-mers apart at compile-time offsets: K / 4 + 1 load
- * instructions per four k-mers instead of K / 4 + 2 per k-mer (encodeCodesKernel: one k-mer per thread at a 21-byte
- * stride), which is what bounds that kernel, not the bytes.  The last k-mers of a batch (those whose loads would run past its end) go one by one. */
-typedef unsigned Dwords4 __attribute__((ext_vector_type(4), aligned(4))); /* a 16-byte load at dword alignment */
+/* pass 1 for ASCII k-mers of a length known at compile time: a thread takes FOUR consecutive k-mers (decodeFour) where
+ * encodeCodesKernel takes one at a 21-byte stride */
 template <unsigned K>
 __global__ void __launch_bounds__(256)
     encodeCodes4Kernel(const unsigned char *__restrict__ chars, const BucketFormat f, const unsigned long long numQueries,
                        unsigned long long *__restrict__ codesOut, unsigned *__restrict__ hist /* [kShares][binsPad] */,
                        const unsigned binsPad, const unsigned *__restrict__ sampleAlive = nullptr, const unsigned samples = 0u) {
   extern __shared__ unsigned sHist[]; /* 2^bucketBits + 1 */
-  if (lookupChosen(sampleAlive, samples, false)) return; /* this batch is encodeLookupKernel's (uniform) */
+  if (lookupChosen(sampleAlive, samples, false)) return; /* this batch is lookupSearchKernel's (uniform) */
   const unsigned bins = (1u << f.bucketBits) + 1u;
   for (unsigned e = threadIdx.x; e < bins; e += 256u) sHist[e] = 0u;
   __syncthreads();
-  constexpr unsigned kLoads = (K + 1u + 3u) / 4u; /* 16-byte loads that cover K + 1 dwords */
   const unsigned shift = (unsigned)((unsigned long long)chars & 3ull);
-  typedef const Dwords4 __attribute__((address_space(1))) *GlobalDwords4;
-  const unsigned share = blockIdx.x % kShares, localBlock = blockIdx.x / kShares, localGrid = gridDim.x / kShares;
-  const unsigned long long size = shareSize(numQueries), first = size * share; /* a multiple of the tile, hence of 4 */
-  const unsigned long long last = first + size < numQueries ? first + size : numQueries;
+  const auto [share, localBlock, localGrid, first, last] = shareRange(numQueries);
   for (unsigned long long t = first + 4ull * ((unsigned long long)localBlock * 256ull + threadIdx.x); t < last; t += 4ull * localGrid * 256ull) {
     unsigned long long codes[4];
     unsigned bad[4];
-    if (t * K + 16ull * kLoads <= numQueries * K) { /* the 16-byte loads from the aligned-down start stay inside the batch */
-      const GlobalDwords4 first = (GlobalDwords4)(((unsigned long long)chars + t * K) & ~3ull);
-      unsigned dw[kLoads * 4u + 1u];
-#pragma unroll
-      for (unsigned j = 0; j < kLoads; j++) {
-        const Dwords4 q = first[j];
-        dw[4u * j] = q.x;
-        dw[4u * j + 1u] = q.y;
-        dw[4u * j + 2u] = q.z;
-        dw[4u * j + 3u] = q.w;
-      }
-      dw[kLoads * 4u] = 0u;
-      unsigned al[K + 1u]; /* the 4 K bytes at dword alignment */
-#pragma unroll
-      for (unsigned j = 0; j < K; j++) al[j] = __builtin_amdgcn_alignbyte(dw[j + 1u], dw[j], shift);
-      al[K] = 0u;
-#pragma unroll
-      for (unsigned i = 0; i < 4u; i++) {
-        constexpr unsigned kWords = (K + 3u) / 4u; /* groups of four characters */
-        const unsigned at = i * K; /* byte offset of k-mer i: compile time after unrolling */
-        unsigned long long c = 0;
-        unsigned b = 0;
-#pragma unroll
-        for (unsigned w = 0; w < 8u; w++) {
-          unsigned packed = 0;
-          if (w < kWords) {
-            const unsigned lo = al[(at >> 2) + w], hi = (at >> 2) + w + 1u <= K ? al[(at >> 2) + w + 1u] : 0u;
-            const unsigned inKmer = K - 4u * w >= 4u ? 4u : K - 4u * w; /* characters of the k-mer in this word */
-            decodeWordAny(__builtin_amdgcn_alignbyte(hi, lo, at & 3u), inKmer >= 4u ? ~0u : (1u << (8u * inKmer)) - 1u, packed, b);
-          }
-          c = (c << 8) | packed;
-        }
-        codes[i] = c >> (2u * (32u - K));
-        bad[i] = b;
-      }
-    } else {
-#pragma unroll
-      for (unsigned i = 0; i < 4u; i++) {
-        codes[i] = 0;
-        bad[i] = 0;
-        if (t + i < numQueries) decodeKmer(chars, (t + i) * K, K, codes[i], bad[i]);
-      }
-    }
+    decodeFour<K>(chars, shift, t, numQueries, codes, bad);
     if (t + 3ull < last) { /* the four code words are 32 consecutive bytes at a 32-byte boundary: two 16-byte stores */
       ulonglong2 *out = (ulonglong2 *)(codesOut + t);
       out[0] = make_ulonglong2(bad[0] ? kCodeGeneral : codes[0], bad[1] ? kCodeGeneral : codes[1]);
@@ -321,7 +201,7 @@ __global__ void __launch_bounds__(256)
 }
 
 /* ---- lookup first, fused: the k-mers still alive after the table are searched where they are found ----
- * encodeLookupKernel hands its survivors (4.4 % of 10^8 random 21-mers) to a scan, a partition and orderedSearchKernel, which
+ * The unfused kernel before this one handed its survivors (4.4 % of 10^8 random 21-mers) to a scan, a partition and orderedSearchKernel, which
  * looks every survivor's table entry up again; those kernels take 0.45 ms per 10^8 k-mers and -- being chains of dependent
  * reads over a few k-mers -- hardly less per 10^7, which is what a rank of an 8-GPU run holds.  Here a wave that has looked
  * its 256 entries up puts the survivors' {codes, number, range} into LDS and takes them through their steps 16 at a time
@@ -358,10 +238,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
   __shared__ unsigned long long sCodes[4][kFusedSlots];
   __shared__ unsigned sNum[4][kFusedSlots];
   __shared__ pos_t sSp[4][kFusedSlots], sEp[4][kFusedSlots];
-  constexpr unsigned kHitBuffer = 32;
-  __shared__ unsigned sHitKmers[4][kHitBuffer];
-  __shared__ unsigned long long sHitRanges[4][kHitBuffer][2];
-  __shared__ unsigned sHitLeft[4], sWavesDone;
+  __shared__ HitList<4> sHits;
+  __shared__ unsigned sWavesDone;
   if (!lookupChosen(sampleAlive, samples, true)) return; /* this batch is encodeCodes4Kernel's (uniform) */
   if (threadIdx.x == 0) sWavesDone = 0u;
   if (threadIdx.x < 24) sC[threadIdx.x] = ix.prefixSums[threadIdx.x];
@@ -370,12 +248,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
   if (PAIR) pairStageTables<NARROW, 16u>(ix, sPairC, sPairSuper);
   __syncthreads();
   const unsigned bins = (1u << f.bucketBits) + 1u;
-  constexpr unsigned kLoads = (K + 1u + 3u) / 4u;
   const unsigned shift = (unsigned)((unsigned long long)chars & 3ull);
-  typedef const Dwords4 __attribute__((address_space(1))) *GlobalDwords4;
-  const unsigned share = blockIdx.x % kShares, localBlock = blockIdx.x / kShares, localGrid = gridDim.x / kShares;
-  const unsigned long long size = shareSize(numQueries), first = size * share;
-  const unsigned long long last = first + size < numQueries ? first + size : numQueries;
+  const auto [share, localBlock, localGrid, first, last] = shareRange(numQueries);
   const unsigned long long tableMask = (1ull << (2u * f.depth)) - 1ull;
   const unsigned lengthBits = deepLengthBits(ix);
   const unsigned lane = threadIdx.x & 63u, gl = threadIdx.x % G, firstSlice = gl;
@@ -389,21 +263,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
   const bool second = K > secondW && (useNext & 8u) == 0u, forceSecond = (useNext & 32u) != 0u;
   const unsigned secondShift = second ? 2u * (K - secondW) : 0u;
   unsigned gateTested = 0, gateDropped = 0, testedHere = 0, droppedHere = 0, trip = 0;
-  auto flushHits = [&]() {
-    if (hitFill != 0u) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      unsigned listBase = 0;
-      if (lane == 0) listBase = atomicAdd(sparse.count, hitFill);
-      listBase = (unsigned)__builtin_amdgcn_readfirstlane((int)listBase);
-      if (lane < hitFill && listBase + lane < sparse.cap) {
-        sparse.kmers[listBase + lane] = sHitKmers[w][lane];
-        sparse.ranges[listBase + lane] = make_ulonglong2(sHitRanges[w][lane][0], sHitRanges[w][lane][1]);
-      }
-      __builtin_amdgcn_wave_barrier();
-      hitFill = 0;
-    }
-  };
   /* (Round 5 tried dealing the 256-k-mer trips to the waves from a counter per share, the next ticket drawn a trip ahead, so
    * that the waves with long trips do not keep the chip waiting at the end: 0.39 instead of 0.36 ms per 1.25 * 10^7 k-mers, 2.89
    * instead of 2.68 per 10^8, and an 81st register: the fixed stride stays, with the grid trimmed to even trips.)
@@ -423,65 +282,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
     const unsigned long long t = tw + 4ull * lane;
     unsigned long long codes[4];
     unsigned bad[4];
-    if (t * K + 16ull * kLoads <= numQueries * K) { /* the 16-byte loads from the aligned-down start stay inside the batch */
-      const GlobalDwords4 from = (GlobalDwords4)(((unsigned long long)chars + t * K) & ~3ull);
-      unsigned dw[kLoads * 4u + 1u];
-#pragma unroll
-      for (unsigned j = 0; j < kLoads; j++) {
-        const Dwords4 q = from[j];
-        dw[4u * j] = q.x;
-        dw[4u * j + 1u] = q.y;
-        dw[4u * j + 2u] = q.z;
-        dw[4u * j + 3u] = q.w;
-      }
-      dw[kLoads * 4u] = 0u;
-      unsigned al[K + 1u];
-#pragma unroll
-      for (unsigned j = 0; j < K; j++) al[j] = __builtin_amdgcn_alignbyte(dw[j + 1u], dw[j], shift);
-      al[K] = 0u;
-#pragma unroll
-      for (unsigned i = 0; i < 4u; i++) {
-        constexpr unsigned kWords = (K + 3u) / 4u;
-        const unsigned at = i * K;
-        unsigned long long c = 0;
-        unsigned b = 0;
-#pragma unroll
-        for (unsigned x = 0; x < 8u; x++) {
-          unsigned packed = 0;
-          if (x < kWords) {
-            const unsigned lo = al[(at >> 2) + x], hi = (at >> 2) + x + 1u <= K ? al[(at >> 2) + x + 1u] : 0u;
-            const unsigned inKmer = K - 4u * x >= 4u ? 4u : K - 4u * x;
-            decodeWordAny(__builtin_amdgcn_alignbyte(hi, lo, at & 3u), inKmer >= 4u ? ~0u : (1u << (8u * inKmer)) - 1u, packed, b);
-          }
-          c = (c << 8) | packed;
-        }
-        codes[i] = c >> (2u * (32u - K));
-        bad[i] = b;
-      }
-    } else {
-#pragma unroll
-      for (unsigned i = 0; i < 4u; i++) {
-        codes[i] = 0;
-        bad[i] = 0;
-        if (t + i < numQueries) decodeKmer(chars, (t + i) * K, K, codes[i], bad[i]);
-      }
-    }
+    decodeFour<K>(chars, shift, t, numQueries, codes, bad);
     uint2 entry[4];
 #pragma unroll
     for (unsigned i = 0; i < 4u; i++) entry[i] = ((const uint2 *)ix.deepSeed)[t + i < last && !bad[i] ? (codes[i] & tableMask) : 0ull];
     /* a survivor is searched here when it is among the first kFusedSlots of its round (a round of 256 random 21-mers has
      * 11); the others -- and the k-mers with ambiguity characters, which are the general kernel's -- go to the share's
-     * region as encodeLookupKernel's survivors do, and the kernels behind this one take them from there.  Nothing of a
+     * region, and the kernels behind this one take them from there.  Nothing of a
      * k-mer is kept in registers past this point: the steps below work out of LDS. */
     unsigned long long amask[4];
     unsigned abefore[4], atotal = 0, stotal = 0;
     bool append[4];
 #pragma unroll
     for (unsigned i = 0; i < 4u; i++) {
-      const unsigned length = entry[i].y & lengthBits;
-      const bool bit = (useNext & 1u) == 0u || ((entry[i].y >> (16u + ((unsigned)(codes[i] >> (2u * f.depth)) & 15u))) & 1u) != 0u;
       const bool general = t + i < last && bad[i] != 0u;
-      const bool survives = t + i < last && bad[i] == 0u && length != 0u && bit;
+      const bool survives = t + i < last && bad[i] == 0u && deepEntryAlive(entry[i], lengthBits, (useNext & 1u) != 0u, codes[i] >> (2u * f.depth));
       const unsigned long long smask = __ballot(survives);
       const unsigned rank = stotal + (unsigned)__popcll(smask & ((1ull << lane) - 1ull));
       stotal += (unsigned)__popcll(smask);
@@ -551,8 +366,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
           c = sCodes[w][lane];
           const unsigned long long window = c >> secondShift;
           const uint2 e = ((const uint2 *)ix.deepSeed)[window & tableMask];
-          passes = (e.y & lengthBits) != 0u &&
-                   ((useNext & 1u) == 0u || ((e.y >> (16u + ((unsigned)(window >> (2u * f.depth)) & 15u))) & 1u) != 0u);
+          passes = deepEntryAlive(e, lengthBits, (useNext & 1u) != 0u, window >> (2u * f.depth));
         }
         const unsigned long long passMask = __ballot(passes);
         const unsigned passed = (unsigned)__popcll(passMask);
@@ -602,41 +416,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
           rem = c >> (2u * f.depth);
           pos = (int)(K - f.depth) - 1;
         }
-        if (PAIR) {
-          while (pos >= 1 && sp <= ep) {
-            const unsigned c2 = (unsigned)rem & 3u, c1 = (unsigned)(rem >> 2) & 3u;
-            if (pairSearchStep<NARROW>(ix, sPairC, sPairSuper, sMask, gl, c1 * 4u + c2, sp, ep) == kPairFlagged) {
-              nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, c2, sp, ep);
-              if (sp <= ep) nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, c1, sp, ep);
-            }
-            pos -= 2;
-            rem >>= 4;
-          }
-          if (pos == 0 && sp <= ep) {
-            nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, (unsigned)rem & 3u, sp, ep);
-            pos--;
-          }
+        if (PAIR) { /* pair steps while two characters are left, the odd one alone and last (hitsStep) */
+          while (pos >= 1 && sp <= ep) hitsStep<G, NARROW>(true, ix, sC, sSuper, sMask, sPairC, sPairSuper, gl, firstSlice, rem, pos, sp, ep);
+          if (pos == 0 && sp <= ep) hitsStep<G, NARROW>(false, ix, sC, sSuper, sMask, sPairC, sPairSuper, gl, firstSlice, rem, pos, sp, ep);
         } else {
-          while (pos >= 0 && sp <= ep) {
-            nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, (unsigned)rem & 3u, sp, ep);
-            pos--;
-            rem >>= 2;
-          }
+          while (pos >= 0 && sp <= ep) hitsStep<G, NARROW>(false, ix, sC, sSuper, sMask, sPairC, sPairSuper, gl, firstSlice, rem, pos, sp, ep);
         }
         const bool hit = live && gl == 0 && sp <= ep;
         if (LIST) {
-          const unsigned long long hitMask = __ballot(hit);
-          if (hitMask != 0ull) { /* wave-uniform; at most 16 hits a pass */
-            const unsigned hits = (unsigned)__builtin_amdgcn_readfirstlane((int)__popcll(hitMask));
-            if (hit) {
-              const unsigned at = hitFill + (unsigned)__popcll(hitMask & ((1ull << lane) - 1ull));
-              sHitKmers[w][at] = index;
-              sHitRanges[w][at][0] = (unsigned long long)sp;
-              sHitRanges[w][at][1] = (unsigned long long)ep;
-            }
-            hitFill = (unsigned)__builtin_amdgcn_readfirstlane((int)(hitFill + hits));
-          }
-          if (hitFill + 64u / G > kHitBuffer) flushHits();
+          sHits.template append<G>(sparse, w, lane, hitFill, hit, index, (unsigned long long)sp, (unsigned long long)ep);
         } else if (hit) {
           if (ranges) ranges[index] = make_ulonglong2((unsigned long long)sp, (unsigned long long)ep);
           if (counts) counts[index] = (unsigned)(ep - sp + (pos_t)1);
@@ -650,32 +438,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
   /* (words 1 and 2 of the same line: the survivors put to the second window, and those it dropped) */
   if (lane == 0 && testedHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u + 1u], testedHere);
   if (lane == 0 && droppedHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u + 2u], droppedHere);
-  if (LIST) { /* the waves' leftovers in one reservation, as in orderedSearchKernel */
-    if (lane == 0) sHitLeft[w] = hitFill;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    unsigned arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&sWavesDone, 1u);
-    arrived = (unsigned)__builtin_amdgcn_readfirstlane((int)arrived);
-    if (arrived == 3u) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      unsigned total = 0;
-      for (unsigned v = 0; v < 4u; v++) total += sHitLeft[v];
-      if (total != 0u) {
-        unsigned listBase = 0;
-        if (lane == 0) listBase = atomicAdd(sparse.count, total);
-        listBase = (unsigned)__builtin_amdgcn_readfirstlane((int)listBase);
-        unsigned before = 0;
-        for (unsigned v = 0; v < 4u; v++) {
-          const unsigned n = sHitLeft[v];
-          if (lane < n && listBase + before + lane < sparse.cap) {
-            sparse.kmers[listBase + before + lane] = sHitKmers[v][lane];
-            sparse.ranges[listBase + before + lane] = make_ulonglong2(sHitRanges[v][lane][0], sHitRanges[v][lane][1]);
-          }
-          before += n;
-        }
-      }
-    }
-  }
+  if (LIST) sHits.finish(sparse, w, lane, hitFill, sWavesDone);
 }
 
 /* Everything a bucketed search needs before its front end, in ONE launch (round 5; they were a memset, a fill kernel and
@@ -735,8 +498,7 @@ __global__ void __launch_bounds__(256)
         alive = true;
       } else {
         const uint2 e = ((const uint2 *)ix.deepSeed)[codes & ((1ull << (2u * depth)) - 1ull)];
-        const unsigned length = e.y & deepLengthBits(ix);
-        alive = length != 0u && (!useNext || ((e.y >> (16u + ((unsigned)(codes >> (2u * depth)) & 15u))) & 1u) != 0u);
+        alive = deepEntryAlive(e, deepLengthBits(ix), useNext != 0u, codes >> (2u * depth));
       }
     }
   }
@@ -765,22 +527,13 @@ __global__ void __launch_bounds__(1024)
       for (unsigned sh = 0; sh < kShares; sh++) v[j] += hist[sh * binsPad + e];
     sum += v[j];
   }
-  unsigned incl = sum;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned up = __shfl_up(incl, off);
-    if ((int)(threadIdx.x & 63u) >= off) incl += up;
-  }
-  if ((threadIdx.x & 63u) == 63u) sWave[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  unsigned before = 0;
-  for (unsigned w = 0; w < (threadIdx.x >> 6); w++) before += sWave[w];
-  unsigned running = before + incl - sum;
+  unsigned running = blockInclusiveScan(sum, sWave) - sum;
   for (unsigned j = 0; j < kPer; j++) {
     const unsigned e = threadIdx.x * kPer + j;
     if (e <= bins) bucketStart[e] = running; /* entry `bins` = the total */
     if (e < bins) {
       /* the last bin (k-mers left to the general kernel) sits at the END of the record array, where that kernel looks for
-       * it -- the same place as `running` when every k-mer of the batch is in some bin, behind a gap after encodeLookupKernel */
+       * it -- the same place as `running` when every k-mer of the batch is in some bin, behind a gap after lookupSearchKernel */
       unsigned at = e == bins - 1u ? generalEnd - v[j] : running;
       for (unsigned sh = 0; sh < kShares; sh++) {
         const unsigned n = hist[sh * binsPad + e];
@@ -806,16 +559,7 @@ __global__ void __launch_bounds__(1024)
     v[j] = e < bins ? hist[e] : 0u;
     sum += v[j];
   }
-  unsigned incl = sum;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned up = __shfl_up(incl, off);
-    if ((int)(threadIdx.x & 63u) >= off) incl += up;
-  }
-  if ((threadIdx.x & 63u) == 63u) sWave[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  unsigned before = 0;
-  for (unsigned w = 0; w < (threadIdx.x >> 6); w++) before += sWave[w];
-  unsigned running = before + incl - sum;
+  unsigned running = blockInclusiveScan(sum, sWave) - sum;
   for (unsigned j = 0; j < kPer; j++) {
     const unsigned e = threadIdx.x * kPer + j;
     if (e <= bins) bucketStart[e] = running; /* entry `bins` = the total */
@@ -830,7 +574,7 @@ __global__ void __launch_bounds__(kPartitionThreads)
     partitionKernel(const unsigned long long *__restrict__ codes, const unsigned fixedLen, const BucketFormat f,
                     const unsigned long long numQueries, const unsigned *__restrict__ subStart,
                     unsigned *__restrict__ cursors, unsigned long long *__restrict__ recs, const unsigned honourGeneral,
-                    const unsigned *__restrict__ shareCountIn = nullptr /* after encodeLookupKernel: code words in the share's region */,
+                    const unsigned *__restrict__ shareCountIn = nullptr /* after lookupSearchKernel: code words in the share's region */,
                     const unsigned *__restrict__ numbersIn = nullptr /* ... and the k-mer numbers beside them */,
                     const unsigned *__restrict__ sampleAlive = nullptr, const unsigned samples = 0u /* lookupChosen: was it that kernel? */,
                     const unsigned long long numberBase = 0ull /* a shard of a larger batch (awfmGpuOrderKmers): its first k-mer's number there */) {
@@ -850,11 +594,9 @@ __global__ void __launch_bounds__(kPartitionThreads)
   if (threadIdx.x == 0) sNumLong = 0u;
   const unsigned long long lenMask = fixedLen >= 32u ? ~0ull : ((1ull << (2u * fixedLen)) - 1ull);
   /* the tiles of this workgroup's share */
-  const unsigned share = blockIdx.x % kShares, localBlock = blockIdx.x / kShares, localGrid = gridDim.x / kShares;
+  const auto [share, localBlock, localGrid, shareFirst, shareLast] = shareRange(numQueries);
   const unsigned long long tilesPerShare = shareSize(numQueries) / kPartitionTile;
-  const unsigned long long shareFirst = shareSize(numQueries) * share;
-  const unsigned long long shareEnd = shareCount ? shareFirst + shareCount[share * kShareCountStride]
-                                                 : (shareFirst + shareSize(numQueries) < numQueries ? shareFirst + shareSize(numQueries) : numQueries);
+  const unsigned long long shareEnd = shareCount ? shareFirst + shareCount[share * kShareCountStride] : shareLast;
   const unsigned long long tiles = tilesPerShare * share + (shareEnd > shareFirst ? (shareEnd - shareFirst + kPartitionTile - 1ull) / kPartitionTile : 0ull);
   const unsigned *myStart = subStart + share * binsPad;
   unsigned *myCursors = cursors + share * binsPad;
@@ -883,7 +625,7 @@ __global__ void __launch_bounds__(kPartitionThreads)
     for (unsigned j = 0; j < kPartitionItems; j++) {
       const unsigned long long idx = tileBase + (unsigned long long)j * kPartitionThreads + threadIdx.x;
       where[j] = 0xFFFFFFFFu;
-      const bool valid = idx < shareEnd && !(shareCount && rec[j] == kCodeNone); /* (kCodeNone: an unused slot of encodeLookupKernel's) */
+      const bool valid = idx < shareEnd && !(shareCount && rec[j] == kCodeNone); /* (kCodeNone: an unused slot of lookupSearchKernel's) */
       const bool general = honourGeneral != 0u && (rec[j] & kCodeGeneral) != 0ull; /* never for bit-packed input: every word is a k-mer */
       const unsigned long long c = rec[j] & lenMask;
       const unsigned b = general ? bins - 1u : bucketOf(f, c);
@@ -1086,15 +828,7 @@ __global__ void __launch_bounds__(kPartitionThreads)
         got[j] = v[j] ? atomicAdd(&cursors[e], v[j]) : 0u;
         start[j] = v[j] ? bucketStart[e] : 0u;
       }
-      unsigned incl = sum;
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned up = __shfl_up(incl, off);
-        if ((int)(threadIdx.x & 63u) >= off) incl += up;
-      }
-      if ((threadIdx.x & 63u) == 63u) sWave[threadIdx.x >> 6] = incl;
-      __syncthreads();
-      unsigned running = incl - sum;
-      for (unsigned w = 0; w < (threadIdx.x >> 6); w++) running += sWave[w];
+      unsigned running = blockInclusiveScan(sum, sWave) - sum;
 #pragma unroll
       for (unsigned j = 0; j < kPer; j++) {
         const unsigned e = threadIdx.x * kPer + j;
@@ -1193,14 +927,12 @@ __global__ void __launch_bounds__(orderedThreads(PAIR)) __attribute__((amdgpu_nu
   __shared__ unsigned long long sPairC[PAIR ? 16 : 1];
   extern __shared__ unsigned sPairSuper[];
   static_assert(!PAIR || G == 4, "pair steps are written for 4 lanes per query");
-  /* the list of hits (SparseOut::count): a wave collects its hits here and appends them kHitBuffer at a time, or when it is
-   * done.  One returning atomic per wave round with a hit is 7 * 10^4 atomics on one word for 10^8 random 21-mers, and a
-   * word takes 88 per microsecond: 0.8 ms -- unnoticed inside a 2.3 ms kernel, twice the kernel once encodeLookupKernel had
-   * left it 4 * 10^6 k-mers (0.78 against 0.35 ms with dense results) */
-  static_assert(!LIST || BUCKET, "the collected list belongs to the bucketed variant (the one that runs after encodeLookupKernel)");
-  constexpr unsigned kHitBuffer = LIST ? 32 : 1;
-  __shared__ unsigned sHitKmers[LIST ? orderedThreads(PAIR) / 64 : 1][kHitBuffer];
-  __shared__ unsigned long long sHitRanges[LIST ? orderedThreads(PAIR) / 64 : 1][kHitBuffer][2];
+  /* the list of hits (SparseOut::count): a wave collects its hits here (HitList).  One returning atomic per wave round with a
+   * hit was 0.8 ms -- unnoticed inside a 2.3 ms kernel, twice the kernel once lookupSearchKernel had left it 4 * 10^6 k-mers
+   * (0.78 against 0.35 ms with dense results) */
+  static_assert(!LIST || BUCKET, "the collected list belongs to the bucketed variant (the one that runs after lookupSearchKernel)");
+  __shared__ HitList<orderedThreads(PAIR) / 64, LIST> sHits;
+  __shared__ unsigned sWavesDone;
   unsigned hitFill = 0; /* wave-uniform */
   /* the records this launch covers: the whole order, or the buckets [firstBucket, endBucket) of it */
   const unsigned long long coveredFirst = BUCKET && bucketFmt.endBucket != 0u ? (unsigned long long)bucketStart[bucketFmt.firstBucket] : 0ull;
@@ -1208,10 +940,6 @@ __global__ void __launch_bounds__(orderedThreads(PAIR)) __attribute__((amdgpu_nu
                                                : numRecs - (unsigned long long)*generalCount;
   /* nothing to search (the batch ended in lookupSearchKernel): not even the tables are staged */
   if (BUCKET && coveredEnd == coveredFirst) return;
-  /* ... and what the waves of a workgroup still hold when they are done goes out in ONE reservation, made by the wave that
-   * finishes last: the waves of the grid end together, and 7168 of them each taking a returning atomic on the list's counter
-   * were a tail of 60-80 us on a kernel that searched 5 * 10^5 k-mers (a word takes 88 atomics per microsecond) */
-  __shared__ unsigned sHitLeft[LIST ? orderedThreads(PAIR) / 64 : 1], sWavesDone;
   if (LIST && threadIdx.x == 0) sWavesDone = 0u;
   if (threadIdx.x < 24) sC[threadIdx.x] = ix.prefixSums[threadIdx.x];
   stageMaskTable(sMask);
@@ -1256,7 +984,7 @@ __global__ void __launch_bounds__(orderedThreads(PAIR)) __attribute__((amdgpu_nu
   };
   /* the records the fast path covers come first in the order; each XCD takes a contiguous eighth of them */
   /* (bucketed records: what lies before the last bin -- the batch without the k-mers of the general kernel, or the k-mers
-   * encodeLookupKernel kept) */
+   * lookupSearchKernel kept) */
   const unsigned long long covered = coveredEnd - coveredFirst;
   const unsigned xcds = (gridDim.x & 7u) == 0u ? 8u : 1u; /* (workgroup b runs on XCD b % 8 under round-robin dispatch) */
   const unsigned xcd = xcds == 8u ? (blockIdx.x & 7u) : 0u;
@@ -1279,22 +1007,6 @@ __global__ void __launch_bounds__(orderedThreads(PAIR)) __attribute__((amdgpu_nu
    * against 4.41-4.45 ms on the same box, 9.2 against 9.1-9.4 ms planted.) */
   constexpr unsigned kWaves = orderedThreads(PAIR) / 64, kChunk = 64 / G;
   const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  auto flushHits = [&]() { /* wave-uniform: the wave's collected hits go to the list, one reservation for all of them */
-    if (hitFill != 0u) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      unsigned listBase = 0;
-      if (lane == 0) listBase = atomicAdd(sparse.count, hitFill);
-      listBase = (unsigned)__builtin_amdgcn_readfirstlane((int)listBase);
-      if (lane < hitFill && listBase + lane < sparse.cap) {
-        const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        sparse.kmers[listBase + lane] = sHitKmers[w][lane];
-        sparse.ranges[listBase + lane] = make_ulonglong2(sHitRanges[w][lane][0], sHitRanges[w][lane][1]);
-      }
-      __builtin_amdgcn_wave_barrier();
-      hitFill = 0;
-    }
-  };
   /* kTicketGroups x kWaves counters per XCD: wave w of workgroup b draws from counter (b % kTicketGroups, w) */
   constexpr unsigned kCounters = kTicketGroups * kWaves;
   const unsigned counter = (blockInXcd % kTicketGroups) * kWaves + wave;
@@ -1538,19 +1250,9 @@ __global__ void __launch_bounds__(orderedThreads(PAIR)) __attribute__((amdgpu_nu
       const bool mine = at < end && gl == 0;
       if (sparse.count) { /* kernel argument: uniform */
         const bool hit = mine && sp <= ep;
-        if (!LIST) sparseAppend(sparse, hit, index, (unsigned long long)sp, (unsigned long long)ep);
-        const unsigned long long hitMask = LIST ? __ballot(hit) : 0ull;
-        if (hitMask != 0ull) { /* wave-uniform; at most 64 / G hits a round */
-          const unsigned hits = (unsigned)__builtin_amdgcn_readfirstlane((int)__popcll(hitMask));
-          if (hit) { /* there is room: the buffer is emptied below whenever a round's worth might not fit */
-            const unsigned at = hitFill + (unsigned)__popcll(hitMask & ((1ull << (threadIdx.x & 63u)) - 1ull));
-            const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-            sHitKmers[w][at] = index;
-            sHitRanges[w][at][0] = (unsigned long long)sp;
-            sHitRanges[w][at][1] = (unsigned long long)ep;
-          }
-          hitFill = (unsigned)__builtin_amdgcn_readfirstlane((int)(hitFill + hits));
-        }
+        const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        if (LIST) sHits.template append<G>(sparse, w, lane, hitFill, hit, index, (unsigned long long)sp, (unsigned long long)ep);
+        else sparseAppend(sparse, hit, index, (unsigned long long)sp, (unsigned long long)ep);
       } else if (sparse.kmers) { /* results in search order: entry `at`, whatever the outcome */
         if (mine && sparse.ranges) {
           sparse.kmers[at - coveredFirst] = index; /* (a share of the order: its entries from 0) */
@@ -1566,7 +1268,6 @@ __global__ void __launch_bounds__(orderedThreads(PAIR)) __attribute__((amdgpu_nu
         if (counts) counts[index] = (unsigned)(ep - sp + (pos_t)1);
       }
     }
-    if (LIST && hitFill + 64u / G > kHitBuffer) flushHits();
     base = baseNext;
     if (AHEAD) {
       baseNext = baseNext2;
@@ -1575,33 +1276,7 @@ __global__ void __launch_bounds__(orderedThreads(PAIR)) __attribute__((amdgpu_nu
       baseNext = nextChunk();
     }
   }
-  if (LIST) {
-    const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (lane == 0) sHitLeft[w] = hitFill;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    unsigned arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&sWavesDone, 1u);
-    arrived = (unsigned)__builtin_amdgcn_readfirstlane((int)arrived);
-    if (arrived == kWaves - 1u) { /* wave-uniform: every wave's leftovers are in LDS */
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      unsigned total = 0;
-      for (unsigned v = 0; v < kWaves; v++) total += sHitLeft[v];
-      if (total != 0u) {
-        unsigned listBase = 0;
-        if (lane == 0) listBase = atomicAdd(sparse.count, total);
-        listBase = (unsigned)__builtin_amdgcn_readfirstlane((int)listBase);
-        unsigned before = 0;
-        for (unsigned v = 0; v < kWaves; v++) {
-          const unsigned n = sHitLeft[v]; /* at most kHitBuffer <= 64 */
-          if (lane < n && listBase + before + lane < sparse.cap) {
-            sparse.kmers[listBase + before + lane] = sHitKmers[v][lane];
-            sparse.ranges[listBase + before + lane] = make_ulonglong2(sHitRanges[v][lane][0], sHitRanges[v][lane][1]);
-          }
-          before += n;
-        }
-      }
-    }
-  }
+  if (LIST) sHits.finish(sparse, (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane, hitFill, sWavesDone);
 }
 
 
@@ -1648,10 +1323,9 @@ __global__ void __launch_bounds__(orderedThreads(true)) __attribute__((amdgpu_nu
       unsigned next16 = 0;
       for (unsigned code = 0; code < 16u; code++) {
         pos_t sp = (pos_t)r.x, ep = (pos_t)r.y;
-        if (pairSearchStep<NARROW>(ix, sPairC, sPairSuper, sMask, gl, code, sp, ep) == kPairFlagged) {
-          nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, code & 3u, sp, ep);
-          if (sp <= ep) nucFastStep<G, NARROW>(ix, sC, sSuper, sMask, firstSlice, code >> 2, sp, ep);
-        }
+        unsigned long long rem = code; /* the pair step the search kernels take: c2 = code & 3 first, then c1 = code >> 2 */
+        int pos = 1;
+        hitsStep<G, NARROW>(true, ix, sC, sSuper, sMask, sPairC, sPairSuper, gl, firstSlice, rem, pos, sp, ep);
         if (sp <= ep) next16 |= 1u << code;
       }
       if (gl == 0) {
