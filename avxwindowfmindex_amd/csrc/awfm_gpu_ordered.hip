@@ -72,6 +72,14 @@ enum AwFmReturnCode launchOrderedKernel(AwFmGpuIndex *g, hipStream_t s, uint32_t
   const unsigned long long blocks = (nq + threads / G - 1) / (threads / G);
   if (blocks < grid) grid = (unsigned)blocks;
   if (grid >= 8u) grid &= ~7u; /* a multiple of the 8 XCDs, so that every XCD gets the same number of workgroups */
+  /* The chunks of an XCD's share are dealt round-robin to its kTicketGroups x (waves per workgroup) ticket counters, and a
+   * counter is drawn from only by the waves of the workgroups b with b % kTicketGroups = its group: an XCD with fewer than
+   * kTicketGroups workgroups leaves the chunks of the groups nobody has unsearched.  Rounding the grid down did that to the
+   * 16-byte records of batches of 513 to 2047 k-mers (8 to 31 workgroups; the 8-byte records' two chunks per ticket happened to
+   * cover their shares): 1025 clean 32-mers lost 8 k-mers, 1956 lost 424.  Such a grid is raised to kTicketGroups workgroups
+   * per XCD -- the ones with nothing to do draw a ticket past the end and leave.  (Below 8 workgroups the one share has a
+   * workgroup for every group its chunks reach: 4 chunks per workgroup, one per wave.) */
+  if (grid >= 8u && grid < 8u * kTicketGroups) grid = 8u * kTicketGroups;
   /* measurement hook (bench.py): HIP events around the kernel on its launch stream (events [2],[3]; when the call's
    * dominant kernel was the lookup kernel its own events [0],[1] are the ones reported) */
   /* (the events ride on the kernel's own dispatch -- hipExtLaunchKernelGGL -- instead of being recorded around it: a
@@ -600,20 +608,27 @@ static bool ensureOrderScratch(AwFmGpuIndex *g, size_t bytes) {
   return true;
 }
 
+/* ASCII 32-mers fill their code words, so "left to the general kernel" and "no k-mer" are marked in a byte beside each
+ * (awfm_ordered_kernel.h: flags32): the bytes a batch needs in the scratch, 0 for every other length */
+static size_t flags32Bytes(uint32_t fixedLength, unsigned long long nq, bool packed) {
+  return !packed && fixedLength == 32u ? alignUp256((size_t)nq) : 0u;
+}
+
 /* encodeCodes4Kernel<K> for the batch's k-mer length */
 template <unsigned K>
 static void launchEncode4At(unsigned len, unsigned grid, size_t lds, hipStream_t s, const uint8_t *dChars, const BucketFormat &fmt,
                             unsigned long long nq, unsigned long long *codes, unsigned *hist, unsigned binsPad,
-                            const unsigned *sampleAlive, unsigned samples) {
+                            const unsigned *sampleAlive, unsigned samples, unsigned char *flags32) {
   if (len == K)
-    hipLaunchKernelGGL((encodeCodes4Kernel<K>), dim3(grid), dim3(256), lds, s, dChars, fmt, nq, codes, hist, binsPad, sampleAlive, samples);
+    hipLaunchKernelGGL((encodeCodes4Kernel<K>), dim3(grid), dim3(256), lds, s, dChars, fmt, nq, codes, hist, binsPad, sampleAlive, samples, flags32);
   else if constexpr (K > 1u)
-    launchEncode4At<K - 1u>(len, grid, lds, s, dChars, fmt, nq, codes, hist, binsPad, sampleAlive, samples);
+    launchEncode4At<K - 1u>(len, grid, lds, s, dChars, fmt, nq, codes, hist, binsPad, sampleAlive, samples, flags32);
 }
 static void launchEncode4(unsigned len, unsigned grid, size_t lds, hipStream_t s, const uint8_t *dChars, const BucketFormat &fmt,
                           unsigned long long nq, unsigned long long *codes, unsigned *hist, unsigned binsPad,
-                          const unsigned *sampleAlive = nullptr, unsigned samples = 0u) {
-  launchEncode4At<32u>(len, grid, lds, s, dChars, fmt, nq, codes, hist, binsPad, sampleAlive, samples);
+                          unsigned char *flags32 /* the marks of 32-mers (flags32Bytes) */, const unsigned *sampleAlive = nullptr,
+                          unsigned samples = 0u) {
+  launchEncode4At<32u>(len, grid, lds, s, dChars, fmt, nq, codes, hist, binsPad, sampleAlive, samples, flags32);
 }
 
 /* lookupSearchKernel<K, NARROW> for the batch's k-mer length */
@@ -622,13 +637,13 @@ static void launchLookupSearchAt(unsigned len, unsigned grid, size_t lds, hipStr
                                  const BucketFormat &fmt, unsigned useNext, unsigned long long nq, unsigned long long *codes,
                                  unsigned *numbers, unsigned *shareCount, unsigned *hist, unsigned binsPad,
                                  const unsigned *sampleAlive, unsigned samples, ulonglong2 *rng, unsigned *dCounts,
-                                 const SparseOut &sparse, unsigned *keptCounters, hipEvent_t start, hipEvent_t stop) {
+                                 const SparseOut &sparse, unsigned *keptCounters, unsigned char *flags32, hipEvent_t start, hipEvent_t stop) {
   if (len == K)
     AWFM_LAUNCH_WITH_EVENTS((lookupSearchKernel<K, NARROW>), dim3(grid), dim3(256), (unsigned)lds, s, start, stop, dev, dChars, fmt, useNext, nq, codes,
-                          numbers, shareCount, hist, binsPad, sampleAlive, samples, rng, dCounts, sparse, keptCounters);
+                          numbers, shareCount, hist, binsPad, sampleAlive, samples, rng, dCounts, sparse, keptCounters, flags32);
   else if constexpr (K > 1u)
     launchLookupSearchAt<K - 1u, NARROW>(len, grid, lds, s, dev, dChars, fmt, useNext, nq, codes, numbers, shareCount, hist, binsPad, sampleAlive, samples,
-                                         rng, dCounts, sparse, keptCounters, start, stop);
+                                         rng, dCounts, sparse, keptCounters, flags32, start, stop);
 }
 
 /* ---- lookup prediction (AwFmGpuIndex::LookupPredict) ---- */
@@ -685,7 +700,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
                           bool rangesOfHitsOnly, const OrderTouch *touch, const BucketFormat &fmt, const SparseOut *sparse) {
   const unsigned bins = (1u << fmt.bucketBits) + 1u, binsPad = (bins + 3u) & ~3u;
   /* [counters 128 KB][hist -> sub-run starts: 8 shares x binsPad][cursors: 8 x binsPad][bucketStart: bins + 1]
-   * [codes: nq x 8 unless packed][records: nq x 8] */
+   * [codes: nq x 8 unless packed][records: nq x 8] ... [flags32: nq bytes, ASCII 32-mers only] */
   const size_t histAt = kOrderCounterBytes, cursorsAt = histAt + alignUp256((size_t)kShares * binsPad * 4u);
   const size_t startAt = cursorsAt + alignUp256((size_t)kShares * binsPad * 4u);
   const size_t codesAt = startAt + alignUp256((bins + 1u) * 4u), recsAt = codesAt + (packed ? 0u : alignUp256(nq * 8u));
@@ -705,7 +720,8 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
   constexpr unsigned countShift = kCountShift;
   const size_t countInAt = numbersAt + (lookupWanted ? alignUp256(nq * 4u) : 0u);
   const size_t countOutAt = countInAt + (countRecords ? alignUp256(nq * 8u) : 0u);
-  const size_t total = countOutAt + (countRecords ? alignUp256(((size_t)countBuckets << countShift) * 8u) : 0u);
+  const size_t flagsAt = countOutAt + (countRecords ? alignUp256(((size_t)countBuckets << countShift) * 8u) : 0u);
+  const size_t total = flagsAt + flags32Bytes(fixedLength, nq, packed);
   if (orderBeginSlot(g, s) != hipSuccess) {
     setError("seed-order search: could not order the use of its scratch across streams");
     return -(int)AwFmGeneralFailure;
@@ -730,6 +746,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
   unsigned *hist = (unsigned *)(w + histAt), *cursors = (unsigned *)(w + cursorsAt), *bucketStart = (unsigned *)(w + startAt);
   const unsigned long long *codes = packed ? (const unsigned long long *)dChars : (const unsigned long long *)(w + codesAt);
   unsigned long long *recs = (unsigned long long *)(w + recsAt);
+  unsigned char *flags32 = total != flagsAt ? w + flagsAt : nullptr;
   /* grids: multiples of the 8 shares (workgroup b works on share b % 8) */
   const unsigned long long perShare256 = (shareSize(nq) + 255ull) / 256ull;
   unsigned encodeGrid = (unsigned)(perShare256 * kShares < (unsigned long long)g->numCUs * 8u ? perShare256 * kShares : (unsigned long long)g->numCUs * 8u);
@@ -847,7 +864,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
   launchLookupSearchAt<32u, NR>(fixedLength, fusedGrid, lds, s, dev, dChars, fmt, useNext | (pairOff ? 2u : 0u) | (lookupOnly ? 4u : 0u) | secondBits, nq, \
                                 (unsigned long long *)(w + codesAt), lookupOnly ? (unsigned *)recs : numbers, lookupOnly ? generalCount : shareCount, \
                                 hist, binsPad, sampleAlive, kSamples, rng, dCounts, sparse ? *sparse : SparseOut(),                      \
-                                (unsigned *)(w + kKeptAt), timed ? g->orderTiming[0] : nullptr, timed ? g->orderTiming[1] : nullptr)
+                                (unsigned *)(w + kKeptAt), flags32, timed ? g->orderTiming[0] : nullptr, timed ? g->orderTiming[1] : nullptr)
       if (narrow) AWFM_LOOKUP_GO(true);
       else AWFM_LOOKUP_GO(false);
 #undef AWFM_LOOKUP_GO
@@ -873,7 +890,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
     hipLaunchKernelGGL((encodeCodesKernel<true>), dim3(encodeGrid), dim3(256), bins * 4u, s, dChars, fixedLength, fmt, nq,
                        (unsigned long long *)nullptr, hist, binsPad);
   else
-    launchEncode4(fixedLength, encodeGrid, bins * 4u, s, dChars, fmt, nq, (unsigned long long *)(w + codesAt), hist, binsPad, sampleAlive, kSamples);
+    launchEncode4(fixedLength, encodeGrid, bins * 4u, s, dChars, fmt, nq, (unsigned long long *)(w + codesAt), hist, binsPad, flags32, sampleAlive, kSamples);
   BUCKET_TRY(hipGetLastError());
   hipLaunchKernelGGL(bucketScanSharesKernel, dim3(1), dim3(1024), 0, s, hist, bins, binsPad, bucketStart, generalCount, (unsigned)nq);
   BUCKET_TRY(hipGetLastError());
@@ -891,7 +908,8 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
   hipLaunchKernelGGL(partitionKernel, dim3(partitionGrid), dim3(kPartitionThreads), partitionLds, s, codes, fixedLength, fmt, nq,
                      (const unsigned *)hist, cursors, recs, packed ? 0u : 1u,
                      lookupFirst || bySample ? (const unsigned *)shareCount : (const unsigned *)nullptr,
-                     lookupFirst || bySample ? (const unsigned *)numbers : (const unsigned *)nullptr, sampleAlive, kSamples);
+                     lookupFirst || bySample ? (const unsigned *)numbers : (const unsigned *)nullptr, sampleAlive, kSamples, 0ull,
+                     (const unsigned char *)flags32);
   BUCKET_TRY(hipGetLastError());
   const SparseOut countOut{nullptr, 0u, (unsigned *)(w + countInAt), nullptr};
   const SparseOut *results = countRecords ? &countOut : sparse;
@@ -1694,9 +1712,11 @@ extern "C" enum AwFmReturnCode awfmGpuOrderKmers(AwFmGpuIndex *g, const uint8_t 
   std::lock_guard<std::mutex> lock(g->orderMutex);
   const unsigned long long nq = numQueries;
   const unsigned bins = (1u << fmt.bucketBits) + 1u, binsPad = (bins + 3u) & ~3u;
-  /* [counters 128 KB][hist -> sub-run starts: 8 shares x binsPad][cursors: 8 x binsPad][codes: nq x 8] of the image's scratch */
+  /* [counters 128 KB][hist -> sub-run starts: 8 shares x binsPad][cursors: 8 x binsPad][codes: nq x 8][flags32: nq bytes,
+   * 32-mers only] of the image's scratch */
   const size_t histAt = kOrderCounterBytes, cursorsAt = histAt + alignUp256((size_t)kShares * binsPad * 4u);
-  const size_t codesAt = cursorsAt + alignUp256((size_t)kShares * binsPad * 4u), total = codesAt + alignUp256(nq * 8u);
+  const size_t codesAt = cursorsAt + alignUp256((size_t)kShares * binsPad * 4u), flagsAt = codesAt + alignUp256(nq * 8u);
+  const size_t total = flagsAt + flags32Bytes(fixedLength, nq, false);
 #define SHARD_TRY(call)                     \
   do {                                      \
     hipError_t e__ = (call);                \
@@ -1711,11 +1731,12 @@ extern "C" enum AwFmReturnCode awfmGpuOrderKmers(AwFmGpuIndex *g, const uint8_t 
   uint8_t *w = (uint8_t *)g->dOrder;
   unsigned *generalCount = (unsigned *)w, *hist = (unsigned *)(w + histAt), *cursors = (unsigned *)(w + cursorsAt);
   unsigned long long *codes = (unsigned long long *)(w + codesAt);
+  unsigned char *flags32 = total != flagsAt ? w + flagsAt : nullptr;
   SHARD_TRY(hipMemsetAsync(w, 0, codesAt, s));
   const unsigned long long perShare256 = (shareSize(nq) + 255ull) / 256ull;
   unsigned encodeGrid = (unsigned)(perShare256 * kShares < (unsigned long long)g->numCUs * 8u ? perShare256 * kShares : (unsigned long long)g->numCUs * 8u);
   encodeGrid = (encodeGrid + kShares - 1u) / kShares * kShares;
-  launchEncode4(fixedLength, encodeGrid, bins * 4u, s, dChars, fmt, nq, codes, hist, binsPad);
+  launchEncode4(fixedLength, encodeGrid, bins * 4u, s, dChars, fmt, nq, codes, hist, binsPad, flags32);
   SHARD_TRY(hipGetLastError());
   hipLaunchKernelGGL(bucketScanSharesKernel, dim3(1), dim3(1024), 0, s, hist, bins, binsPad, (unsigned *)dBucketStart, generalCount, (unsigned)nq);
   SHARD_TRY(hipGetLastError());
@@ -1728,7 +1749,7 @@ extern "C" enum AwFmReturnCode awfmGpuOrderKmers(AwFmGpuIndex *g, const uint8_t 
   /* (the records carry the k-mers' numbers in the WHOLE batch: firstNumber + the number in this shard) */
   hipLaunchKernelGGL(partitionKernel, dim3(partitionGrid), dim3(kPartitionThreads), partitionLds, s, (const unsigned long long *)codes, fixedLength, fmt, nq,
                      (const unsigned *)hist, cursors, (unsigned long long *)dRecords, 1u, (const unsigned *)nullptr, (const unsigned *)nullptr,
-                     (const unsigned *)nullptr, 0u, (unsigned long long)firstNumber);
+                     (const unsigned *)nullptr, 0u, (unsigned long long)firstNumber, (const unsigned char *)flags32);
   SHARD_TRY(hipGetLastError());
   /* (the size of the last bin -- the k-mers awfmGpuSearchGeneralRecords takes -- behind the bucket starts) */
   SHARD_TRY(hipMemcpyAsync(dBucketStart + bins + 1u, generalCount, 4, hipMemcpyDeviceToDevice, s));

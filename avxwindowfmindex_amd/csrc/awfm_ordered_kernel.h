@@ -82,6 +82,10 @@ __host__ __device__ inline unsigned orderStartDepth(unsigned len, unsigned seedK
  */
 constexpr unsigned kBucketBitsMax = 11; /* 2048 buckets (+ 1 for the k-mers left to the general kernel) */
 constexpr unsigned long long kCodeGeneral = 1ull << 63; /* a code word of a k-mer the ordered kernel does not cover */
+/* A 32-mer fills its code word: bits 63..62 are its first character, and neither kCodeGeneral nor kCodeNone (below) can be told
+ * from a k-mer there ('g' or 't' in front; 'c' and 31 x 'a').  Batches of ASCII 32-mers therefore carry the two marks OUTSIDE the
+ * code word, in a byte per code word (`flags32`; a null pointer for every other length): */
+constexpr unsigned kFlagKmer = 0, kFlagGeneral = 1, kFlagNone = 2;
 /* counters[bin] += 1 for the lanes with `valid`, returning each one's rank.  A batch that arrives sorted puts every lane of a
  * wave -- every k-mer of a tile -- into the same bin: 64 LDS atomics on one word per instruction, serialised (a sorted
  * batch took 2.9 instead of 1.0 ms through the two ordering passes).  When the valid lanes agree on the bin one of them adds
@@ -172,8 +176,10 @@ template <unsigned K>
 __global__ void __launch_bounds__(256)
     encodeCodes4Kernel(const unsigned char *__restrict__ chars, const BucketFormat f, const unsigned long long numQueries,
                        unsigned long long *__restrict__ codesOut, unsigned *__restrict__ hist /* [kShares][binsPad] */,
-                       const unsigned binsPad, const unsigned *__restrict__ sampleAlive = nullptr, const unsigned samples = 0u) {
+                       const unsigned binsPad, const unsigned *__restrict__ sampleAlive = nullptr, const unsigned samples = 0u,
+                       unsigned char *__restrict__ flags32 = nullptr /* K = 32: a byte per code word (kFlagKmer / kFlagGeneral) */) {
   extern __shared__ unsigned sHist[]; /* 2^bucketBits + 1 */
+  constexpr bool WIDE32 = K == 32u; /* the code word has no bit to spare: "general" goes to flags32 */
   if (lookupChosen(sampleAlive, samples, false)) return; /* this batch is lookupSearchKernel's (uniform) */
   const unsigned bins = (1u << f.bucketBits) + 1u;
   for (unsigned e = threadIdx.x; e < bins; e += 256u) sHist[e] = 0u;
@@ -186,12 +192,18 @@ __global__ void __launch_bounds__(256)
     decodeFour<K>(chars, shift, t, numQueries, codes, bad);
     if (t + 3ull < last) { /* the four code words are 32 consecutive bytes at a 32-byte boundary: two 16-byte stores */
       ulonglong2 *out = (ulonglong2 *)(codesOut + t);
-      out[0] = make_ulonglong2(bad[0] ? kCodeGeneral : codes[0], bad[1] ? kCodeGeneral : codes[1]);
-      out[1] = make_ulonglong2(bad[2] ? kCodeGeneral : codes[2], bad[3] ? kCodeGeneral : codes[3]);
+      out[0] = make_ulonglong2(!WIDE32 && bad[0] ? kCodeGeneral : codes[0], !WIDE32 && bad[1] ? kCodeGeneral : codes[1]);
+      out[1] = make_ulonglong2(!WIDE32 && bad[2] ? kCodeGeneral : codes[2], !WIDE32 && bad[3] ? kCodeGeneral : codes[3]);
+      if (WIDE32) /* (t is a multiple of 4: one 4-byte store) */
+        *(unsigned *)(flags32 + t) = (bad[0] ? kFlagGeneral : kFlagKmer) | (bad[1] ? kFlagGeneral : kFlagKmer) << 8 |
+                                     (bad[2] ? kFlagGeneral : kFlagKmer) << 16 | (bad[3] ? kFlagGeneral : kFlagKmer) << 24;
     }
 #pragma unroll
     for (unsigned i = 0; i < 4u; i++) {
-      if (t + i < last && t + 3ull >= last) codesOut[t + i] = bad[i] ? kCodeGeneral : codes[i];
+      if (t + i < last && t + 3ull >= last) {
+        codesOut[t + i] = !WIDE32 && bad[i] ? kCodeGeneral : codes[i];
+        if (WIDE32) flags32[t + i] = (unsigned char)(bad[i] ? kFlagGeneral : kFlagKmer);
+      }
       (void)ldsCountRank(sHist, bad[i] ? bins - 1u : bucketOf(f, codes[i]), t + i < last);
     }
   }
@@ -221,8 +233,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
                        unsigned *__restrict__ numbersOut, unsigned *__restrict__ shareCount, unsigned *__restrict__ hist,
                        const unsigned binsPad, const unsigned *__restrict__ sampleAlive, const unsigned samples,
                        ulonglong2 *__restrict__ ranges, unsigned *__restrict__ counts, const SparseOut sparse,
-                       unsigned *__restrict__ keptCounters) {
+                       unsigned *__restrict__ keptCounters,
+                       unsigned char *__restrict__ flags32 = nullptr /* K = 32: a byte per slot of codesOut (kFlagKmer / General / None) */) {
   constexpr int G = 4;
+  constexpr bool WIDE32 = K == 32u; /* the code word has no bit to spare: "general" and "no k-mer" go to flags32 */
   /* NARROW: 32-bit positions (awfmImageNarrow); otherwise (round 6) the 64-bit arithmetic of ref src/AwFmIndex.h:88-91 -- the
    * entries' format (DevIndex::deepNarrow: 1 or 2) is read at run time either way */
   typedef typename PositionType<NARROW>::type pos_t;
@@ -327,7 +341,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
         }
     } else if (atotal != 0u) { /* wave-uniform; rare */
       if (blockUsed + atotal > blockSlots) {
-        if (blockUsed + lane < blockSlots) codesOut[first + blockBase + blockUsed + lane] = kCodeNone;
+        if (blockUsed + lane < blockSlots) {
+          codesOut[first + blockBase + blockUsed + lane] = kCodeNone;
+          if (WIDE32) flags32[first + blockBase + blockUsed + lane] = (unsigned char)kFlagNone;
+        }
         blockSlots = atotal > kLookupBlock || tw + 256ull > last ? atotal : kLookupBlock;
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(&shareCount[share * kShareCountStride], blockSlots);
@@ -338,7 +355,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
       for (unsigned i = 0; i < 4u; i++)
         if (append[i]) {
           const unsigned long long slot = first + blockBase + blockUsed + abefore[i] + (unsigned)__popcll(amask[i] & ((1ull << lane) - 1ull));
-          codesOut[slot] = bad[i] ? kCodeGeneral : codes[i];
+          codesOut[slot] = !WIDE32 && bad[i] ? kCodeGeneral : codes[i];
+          if (WIDE32) flags32[slot] = (unsigned char)(bad[i] ? kFlagGeneral : kFlagKmer);
           numbersOut[slot] = (unsigned)(t + i);
           atomicAdd(&hist[share * binsPad + (bad[i] ? bins - 1u : bucketOf(f, codes[i]))], 1u);
         }
@@ -433,7 +451,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgp
       __builtin_amdgcn_wave_barrier(); /* the slots are written again by the next round */
     }
   }
-  for (unsigned at = blockUsed + lane; at < blockSlots; at += 64u) codesOut[first + blockBase + at] = kCodeNone;
+  for (unsigned at = blockUsed + lane; at < blockSlots; at += 64u) {
+    codesOut[first + blockBase + at] = kCodeNone;
+    if (WIDE32) flags32[first + blockBase + at] = (unsigned char)kFlagNone;
+  }
   if (lane == 0 && keptHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u], keptHere);
   /* (words 1 and 2 of the same line: the survivors put to the second window, and those it dropped) */
   if (lane == 0 && testedHere) atomicAdd(&keptCounters[((blockIdx.x * 4u + w) % kFusedCounters) * 16u + 1u], testedHere);
@@ -577,7 +598,8 @@ __global__ void __launch_bounds__(kPartitionThreads)
                     const unsigned *__restrict__ shareCountIn = nullptr /* after lookupSearchKernel: code words in the share's region */,
                     const unsigned *__restrict__ numbersIn = nullptr /* ... and the k-mer numbers beside them */,
                     const unsigned *__restrict__ sampleAlive = nullptr, const unsigned samples = 0u /* lookupChosen: was it that kernel? */,
-                    const unsigned long long numberBase = 0ull /* a shard of a larger batch (awfmGpuOrderKmers): its first k-mer's number there */) {
+                    const unsigned long long numberBase = 0ull /* a shard of a larger batch (awfmGpuOrderKmers): its first k-mer's number there */,
+                    const unsigned char *__restrict__ flags32 = nullptr /* ASCII 32-mers: the marks beside the code words (kFlagGeneral, kFlagNone) */) {
   const bool afterLookup = shareCountIn != nullptr && lookupChosen(sampleAlive, samples, true);
   const unsigned *__restrict__ shareCount = afterLookup ? shareCountIn : nullptr;
   const unsigned *__restrict__ numbers = afterLookup ? numbersIn : nullptr;
@@ -625,8 +647,12 @@ __global__ void __launch_bounds__(kPartitionThreads)
     for (unsigned j = 0; j < kPartitionItems; j++) {
       const unsigned long long idx = tileBase + (unsigned long long)j * kPartitionThreads + threadIdx.x;
       where[j] = 0xFFFFFFFFu;
-      const bool valid = idx < shareEnd && !(shareCount && rec[j] == kCodeNone); /* (kCodeNone: an unused slot of lookupSearchKernel's) */
-      const bool general = honourGeneral != 0u && (rec[j] & kCodeGeneral) != 0ull; /* never for bit-packed input: every word is a k-mer */
+      /* (uniform: a batch of ASCII 32-mers, whose code words have no bit for a mark) */
+      const unsigned flag = flags32 && idx < shareEnd ? (unsigned)flags32[idx] : kFlagKmer;
+      const bool none = flags32 ? flag == kFlagNone : rec[j] == kCodeNone;
+      const bool valid = idx < shareEnd && !(shareCount && none); /* (an unused slot of lookupSearchKernel's) */
+      /* never for bit-packed input: every word is a k-mer */
+      const bool general = honourGeneral != 0u && (flags32 ? flag == kFlagGeneral : (rec[j] & kCodeGeneral) != 0ull);
       const unsigned long long c = rec[j] & lenMask;
       const unsigned b = general ? bins - 1u : bucketOf(f, c);
       const unsigned rank = ldsCountRank(sCnt, b, valid);

@@ -234,8 +234,11 @@ def bucket_exchange_on_device(g, records, bucket_start, buckets, world, rank, gr
     d_slice_at, d_starts = slice_at.to(records.device, non_blocking=True), starts.to(records.device, non_blocking=True)
     out = torch.empty(max(int(sum(recv_sizes)), 1), dtype=torch.int64, device=records.device)
     d_full = torch.empty(buckets + 3, dtype=torch.int32, device=records.device)
-    g.merge_bucket_runs(recv.data_ptr(), d_slice_at.data_ptr(), d_starts.data_ptr(), len(recv_sizes), cuts[rank], cuts[rank + 1], buckets,
-                        out.data_ptr(), d_full.data_ptr(), stream)
+    # (a rank that received nothing -- its buckets are empty in every shard -- makes the call all the same, for the bucket starts
+    # (all 0) that tell the search there is nothing to do; torch gives an empty tensor no address, and the library takes no null
+    # pointer, so it passes its output array for the slices nobody reads)
+    g.merge_bucket_runs(recv.data_ptr() or out.data_ptr(), d_slice_at.data_ptr(), d_starts.data_ptr(), len(recv_sizes), cuts[rank], cuts[rank + 1],
+                        buckets, out.data_ptr(), d_full.data_ptr(), stream)
     keep = (recv, d_slice_at, d_starts)  # (alive until the kernel has run: the caller keeps the tuple)
     return out[: int(sum(recv_sizes))], d_full, keep
 

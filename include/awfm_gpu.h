@@ -1453,7 +1453,17 @@ enum AwFmReturnCode awfmGpuSynthMixedQueries(uint8_t *dOut, const uint64_t *dOff
  * range}, hit offsets and positions by the calls that follow awfmGpuSearchHitsInOrder).  K-mers the seed-order kernel does not
  * take (ambiguity characters) stay with the rank that holds their characters (awfmGpuSearchGeneralRecords).
  * dBucketStart: awfmGpuOrderBuckets() + 3 words -- [b] = records before bucket b, [buckets] = records the seed-order kernel
- * takes, [buckets + 1] = numQueries, [buckets + 2] = the k-mers left to the general kernel (the records' tail). */
+ * takes, [buckets + 1] = numQueries, [buckets + 2] = the k-mers left to the general kernel (the records' tail).
+ *
+ * Which batches these calls take.  A record is 8 bytes: {rest of the k-mer's 2K-bit code string : 64 - indexBits, number in the
+ * whole batch : indexBits}.  depth = the characters the table lookup consumes (the deeper device-only table's when the image
+ * has one and K reaches it, the index's seed table's otherwise); bucketBits = min(11, 2 * depth): the bucket of a k-mer is the
+ * leading bucketBits bits of its table index -- the code string of its LAST depth letters, where the backward search starts --
+ * and is not stored; indexBits = bits(totalQueries - 1), between 1 and 32.  A record fits iff
+ *     depth <= K <= 32,  1 <= totalQueries <= 2^32 - 2  and  2 K - bucketBits + indexBits <= 64
+ * on a nucleotide image (kernel AUTO or GROUP4).  awfmGpuOrderBuckets answers 2^bucketBits then and 0 otherwise; with 0 the
+ * other calls return AwFmIllegalPositionError and write nothing (32-mers on 2048 buckets: up to 2048 k-mers; 21-mers: any batch).
+ * The records' bits are the library's own: between the calls they are only moved. */
 uint32_t awfmGpuOrderBuckets(const AwFmGpuIndex *g, uint32_t fixedLength, uint64_t totalQueries); /* 0: not a batch for it */
 enum AwFmReturnCode awfmGpuOrderKmers(AwFmGpuIndex *g, const uint8_t *dChars, uint32_t fixedLength, uint64_t numQueries,
                                       uint64_t firstNumber, uint64_t totalQueries, uint64_t *dRecords, uint32_t *dBucketStart,
@@ -1463,7 +1473,9 @@ enum AwFmReturnCode awfmGpuOrderKmers(AwFmGpuIndex *g, const uint8_t *dChars, ui
  * bucket), dSliceStarts[j * (endBucket - firstBucket + 1) + b] = records of slice j before its bucket firstBucket + b (the
  * last one: the slice's length).  dRecords gets the runs of a bucket from all slices next to each other, slice by slice (any
  * order inside a bucket will do), dBucketStart the buckets + 3 words awfmGpuSearchOrderedRecords wants for an array that holds
- * those buckets only. */
+ * those buckets only.  A rank that received nothing (every slice empty: its buckets hold no k-mer of the batch) makes the call
+ * all the same: dReceived and dRecords are not null but neither is read or written, every word of dBucketStart becomes 0, and
+ * awfmGpuSearchOrderedRecords over such an array succeeds and stores nothing. */
 enum AwFmReturnCode awfmGpuMergeBucketRuns(AwFmGpuIndex *g, const uint64_t *dReceived, const uint64_t *dSliceAt, const uint32_t *dSliceStarts,
                                            uint32_t numSlices, uint32_t firstBucket, uint32_t endBucket, uint32_t buckets, uint64_t *dRecords,
                                            uint32_t *dBucketStart, void *stream);

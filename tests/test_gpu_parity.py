@@ -5,11 +5,15 @@ test/inMemorySaTest/inMemorySaTest.c:29-266 and test/searchTest/searchTest.c:124
 seeded inputs and exact {sp,ep}/hit-order comparison instead of order-insensitive checks.
 """
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from avxwindowfmindex_amd import synth
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bucket_records_common import _check_hits_contract  # noqa: E402,F401 -- (test_gpu_byte_values.py imports it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -1188,14 +1192,6 @@ def test_lookup_first_is_chosen_by_a_sample_of_the_batch(oracle, awfm, require_g
         assert np.array_equal(d_counts.cpu().numpy().view(np.uint32), cnt), name
     g.destroy()
     ix.dealloc()
-
-
-def _check_hits_contract(ranges, counts, sp, ep, cnt):
-    """awfmGpuSearchHits: exact range and count for queries with hits, count 0 and an empty range otherwise"""
-    hit = cnt > 0
-    assert np.array_equal(counts, cnt), "counts differ"
-    assert np.array_equal(ranges[hit, 0], sp[hit]) and np.array_equal(ranges[hit, 1], ep[hit]), "ranges of hits differ"
-    assert np.all(ranges[~hit, 0] > ranges[~hit, 1]), "a query without hits must have an empty range"
 
 
 @pytest.mark.parametrize("lookup_first", [None, "0", "1"])
