@@ -942,6 +942,7 @@ struct AwFmGpuImage {
   std::string accelNotes;
   uint64_t deviceBytes = 0;
   uint64_t numBlocks = 0; /* device blocks (128 positions each) */
+  std::atomic<unsigned> dynamicLdsSet{0}; /* kernels whose dynamic-LDS limit is raised on this image's device (awfm_gpu_ordered.hip) */
   /* Accelerators built BEHIND the first searches (round 6).  An image made by awfmGpuIndexAcquireAll -- the drop-in entry
    * points' way -- is usable as soon as its blocks, seed table, sampled array and pair image are on the device (the reference's
    * index is usable the moment awFmReadIndexFromFile returns, ref src/AwFmFile.c:195-449); its deeper table and full suffix array
@@ -1045,10 +1046,6 @@ struct AwFmGpuIndex {
   hipEvent_t orderDoneEvent = nullptr; /* set while a search is enqueued: its last kernel carries it (stop event) ... */
   bool orderDoneArmed = false;         /* ... and says so here */
   StreamGate sparseGate; /* dSparse */
-  /* $AWFM_GPU_TIME_ORDERED: [0],[1] around the front end that looks the table up (encodeLookupKernel), [2],[3] around
-   * orderedSearchKernel; which pair is the call's dominant kernel follows from orderLookup */
-  hipEvent_t orderTiming[4] = {nullptr, nullptr, nullptr, nullptr}; /* the current entry of orderLog */
-  bool orderTimedFront = false, orderTimedKernel = false;
   /* one entry per timed search, so that a caller can time every step of a loop without waiting inside it
    * (awfmGpuOrderedKernelLog): a ring of kOrderLogMax entries, events created on first use */
   struct OrderLogEntry {
@@ -1058,15 +1055,22 @@ struct AwFmGpuIndex {
   static constexpr unsigned kOrderLogMax = 1024;
   std::vector<OrderLogEntry> orderLog;
   unsigned long long orderLogCount = 0; /* searches timed since the log was last read */
-  /* did the last bucketed search keep its k-mers by encodeLookupKernel?  0 no, 1 yes, 2 decided ON THE DEVICE from the
-   * sample (no host wait inside the search): the sample's count is the device word orderSampleAt, the pass was taken when
-   * 4 x that count < orderSamples */
-  int orderLookup = 0;
-  const unsigned *orderSampleAt = nullptr;
-  unsigned orderSamples = 0;
-  bool orderLookupFused = false;               /* ... by lookupSearchKernel, which searched the k-mers it kept itself */
-  const unsigned *orderFusedKeptAt = nullptr;  /* its survivor counters (kFusedCounters words, 64 B apart) */
-  const unsigned *orderKeptAt = nullptr; /* device word: k-mers that search ordered (after encodeLookupKernel: the ones it kept) */
+  /* what the last seed-order search on the handle did (reporting: the awfmGpuLast* calls), reset as a whole when the next one
+   * begins; its three device words lie in a slot's scratch and go with it (ensureOrderScratch).  Under orderMutex. */
+  struct OrderReport {
+    /* $AWFM_GPU_TIME_ORDERED: [0],[1] around the front end that looks the table up (encodeLookupKernel), [2],[3] around
+     * orderedSearchKernel; which pair is the call's dominant kernel follows from `lookup` */
+    hipEvent_t timing[4] = {nullptr, nullptr, nullptr, nullptr}; /* the current entry of orderLog */
+    bool timedFront = false, timedKernel = false;
+    /* did the search keep its k-mers by encodeLookupKernel?  0 no, 1 yes, 2 decided ON THE DEVICE from the sample (no host
+     * wait inside the search): the sample's count is the device word sampleAt, the pass was taken when 4 x that count < samples */
+    int lookup = 0;
+    const unsigned *sampleAt = nullptr;
+    unsigned samples = 0;
+    bool lookupFused = false;               /* ... by lookupSearchKernel, which searched the k-mers it kept itself */
+    const unsigned *fusedKeptAt = nullptr;  /* its survivor counters (kFusedCounters words, 64 B apart) */
+    const unsigned *keptAt = nullptr; /* device word: k-mers that search ordered (after encodeLookupKernel: the ones it kept) */
+  } report;
   /* Lookup prediction (round 5, awfm_gpu_ordered.hip): a sampled search publishes {its number, the sample's count} in
    * page-locked host memory when its sample is in; a later search of the same k-mer length reads the newest verdict -- no
    * wait: whatever has arrived -- and launches only the front end it names (the lookup kernel with what it cannot finish

@@ -7,6 +7,11 @@
  * for fixed-length batches (8-byte records), the same passes over 16-byte records or mixedLookupSearchKernel for the others,
  * aminoLookupSearchKernel for amino batches, exactLookupSearchKernel behind awfmGpuSearch.  Called by awfmGpuSearchHits
  * (awfm_gpu.hip); nothing here synchronises with the host except a scratch (re)allocation.
+ * What the five drivers (bucketedSearch, wideBucketedSearch, aminoLookupSearch, awfmGpuExactLookupSearch, awfmGpuOrderKmers and
+ * the sharded calls) share is written once: the counter block's map (kShareCountAt ... kKeptAt); withBools (run-time bools ->
+ * template arguments); launchLeftover (the general kernel over what a front end left); the report of the last search
+ * (AwFmGpuIndex::OrderReport: recordLookupFront, readFusedCounters); the prologue of a sampled search (ensureVerdictHost,
+ * sampleWords), launchFillNoHit, shareGrid, ensureDynamicLds and launchOrderingPass.  Errors leave through AWFM_HIP_TRY.
  */
 #include <cstring>
 #include <cstdio>
@@ -42,7 +47,18 @@ inline hipError_t fillSparseList(const SparseOut *sparse, hipStream_t s) {
   return hipGetLastError();
 }
 constexpr size_t kOrderCounterBytes = 131072; /* 256 B for the count + 8 XCDs x kTicketGroups x 8 waves x 256 B of ticket counters */
-static_assert(256 + 8 * kTicketGroups * 8 * 256 <= kOrderCounterBytes, "ticket counters");
+/* the counter block's map, bytes into it: [0] the general kernel's count, [256, 65792) the ticket counters, then */
+constexpr size_t kTicketsEnd = 256 + 8 * kTicketGroups * 8 * 256;
+constexpr size_t kCountCursorsAt = 66048; /* countScatterKernel's cursors (zeroed with the counters) */
+constexpr size_t kShareCountAt = 98304;   /* bucketedSearch: lookupSearchKernel's share counts, kShareCountStride words apart ... */
+constexpr size_t kSampleAt = kShareCountAt + kShares * kShareCountStride * 4u; /* ... and lookupPrepKernel's two sample words, a line each */
+constexpr size_t kLeftCountAt = 98304;                 /* wideBucketedSearch: mixedLookupSearchKernel's leftover count ... */
+constexpr size_t kWideSampleAt = kLeftCountAt + 256;   /* ... and its sample's count */
+constexpr size_t kKeptAt = 102400; /* the lookup kernels' survivor counters: kFusedCounters words a line apart */
+static_assert(kTicketsEnd <= kOrderCounterBytes, "ticket counters");
+static_assert(kTicketsEnd <= kCountCursorsAt && kCountCursorsAt + kCountBucketsMax * 4u <= kShareCountAt, "counter block");
+static_assert(kTicketsEnd <= kShareCountAt && kSampleAt + 256 <= kKeptAt && kWideSampleAt + 4 <= kKeptAt, "counter block");
+static_assert(kKeptAt + kFusedCounters * 64u <= kOrderCounterBytes, "counter block");
 
 template <class Kernel>
 unsigned residentGrid(const AwFmGpuIndex *g, Kernel kernel, size_t dynamicLds = 0, int threads = kThreads) {
@@ -54,6 +70,16 @@ unsigned residentGrid(const AwFmGpuIndex *g, Kernel kernel, size_t dynamicLds = 
 
 /* does the image step two characters per block read?  ($AWFM_GPU_PAIR=0 leaves the pair image out altogether) */
 inline bool pairSteps(const AwFmGpuIndex *g) { return g->image->dev.pairBlocks != nullptr; }
+
+/* f(std::bool_constant...) for run-time bools: the one place that turns `narrow`, `pair`, `off != nullptr` into template
+ * arguments -- withBools([&](auto NR, auto PR) { return launch<NR(), PR()>(...); }, narrow, pair) */
+template <class F>
+auto withBools(F &&f) { return f(); }
+template <class F, class... Rest>
+auto withBools(F &&f, bool b, Rest... rest) {
+  return b ? withBools([&](auto... t) { return f(std::true_type(), t...); }, rest...)
+           : withBools([&](auto... t) { return f(std::false_type(), t...); }, rest...);
+}
 
 template <bool NARROW, bool VARLEN, bool PAIR = false, bool TOUCH = false, bool BUCKET = false, bool LIST = false>
 enum AwFmReturnCode launchOrderedKernel(AwFmGpuIndex *g, hipStream_t s, uint32_t len, unsigned depth, const ulonglong2 *table,
@@ -84,14 +110,14 @@ enum AwFmReturnCode launchOrderedKernel(AwFmGpuIndex *g, hipStream_t s, uint32_t
    * dominant kernel was the lookup kernel its own events [0],[1] are the ones reported) */
   /* (the events ride on the kernel's own dispatch -- hipExtLaunchKernelGGL -- instead of being recorded around it: a
    * recorded event is a packet of its own and left the queue idle for about 5 us each, 24 us per search) */
-  const bool timed = g->orderTiming[2] != nullptr; /* this search has an entry in the timing log */
+  const bool timed = g->report.timing[2] != nullptr; /* this search has an entry in the timing log */
   OrderSkip<VARLEN> skip;
   if constexpr (VARLEN) {
     skip.sampleAlive = skipSampleAlive;
     skip.samples = skipSamples;
   }
   AWFM_LAUNCH_WITH_EVENTS((orderedSearchKernel<G, NARROW, VARLEN, PAIR, TOUCH, BUCKET, LIST>), dim3(grid ? grid : 1u), dim3(threads), (unsigned)lds, s,
-                        timed ? g->orderTiming[2] : nullptr, timed ? g->orderTiming[3] : nullptr, dev, recs, nq, generalCount, len, depth, table,
+                        timed ? g->report.timing[2] : nullptr, timed ? g->report.timing[3] : nullptr, dev, recs, nq, generalCount, len, depth, table,
                         rng, dCounts, (unsigned *)generalCount + 64, touch ? *touch : OrderTouch(), bucketStart, bucketFmt,
                         sparse ? *sparse : SparseOut(),
                         /* chunks a ticket is worth: 10^8 random 21-mers 3.92 (1), 3.49 (2), 3.47 (4), 3.50 (8), 3.65 ms (16); planted
@@ -99,69 +125,62 @@ enum AwFmReturnCode launchOrderedKernel(AwFmGpuIndex *g, hipStream_t s, uint32_t
                          * 5.01 (2), 5.19 (3), 5.18 (4): the records in flight on an XCD span fewer buckets.  Mixed lengths: no gain */
                         BUCKET ? 2u : 1u, skip);
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
-  g->orderTimedKernel = timed;
+  g->report.timedKernel = timed;
   if (timed) g->orderLog[(g->orderLogCount - 1u) % AwFmGpuIndex::kOrderLogMax].kernel = true;
   return AwFmSuccess;
 }
 
 /* the general kernel over what a hits-only front end left (the last *leftCount of the `numRecs` 8-byte or 16-byte records at
- * `recs`: k-mers with ambiguity characters, none or more than 32 characters, survivors beyond a round's slots) -- the last
- * kernel of a search: it carries the event that says the scratch slot is free again */
-template <bool NARROW, bool CSR>
-enum AwFmReturnCode launchLeftover(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, const unsigned long long *off, uint32_t len,
-                                   unsigned long long nq, ulonglong2 *rng, uint32_t *dCounts, const void *recs, unsigned recordBytes,
-                                   unsigned indexAt, const unsigned *leftCount, const SparseOut *sparse, bool last = true) {
-  const unsigned grid = residentGrid(g, searchKernel<false, 4, CSR, false, NARROW, true>);
-  AWFM_LAUNCH_WITH_EVENTS((searchKernel<false, 4, CSR, false, NARROW, true>), dim3(grid), dim3(kThreads), 0u, s, nullptr, last ? g->orderDoneEvent : nullptr,
-                          g->image->dev, dChars, off, len, nq, rng, dCounts, (unsigned long long *)nullptr, (const unsigned char *)recs, recordBytes,
-                          indexAt, nq, leftCount, sparse ? *sparse : SparseOut(), (const unsigned *)nullptr, 0u);
+ * `recs`: k-mers with ambiguity characters, none or more than 32 characters, survivors beyond a round's slots) -- with `last`
+ * the last kernel of a search: it carries the event that says the scratch slot is free again */
+enum AwFmReturnCode launchLeftover(AwFmGpuIndex *g, hipStream_t s, bool narrow, bool csr, const uint8_t *dChars, const unsigned long long *off,
+                                   uint32_t len, unsigned long long nq, ulonglong2 *rng, uint32_t *dCounts, const void *recs,
+                                   unsigned long long numRecs, unsigned recordBytes, unsigned indexAt, const unsigned *leftCount,
+                                   const SparseOut *sparse, bool last = true) {
+  withBools([&](auto NR, auto CSR) {
+    const unsigned grid = residentGrid(g, searchKernel<false, 4, CSR(), false, NR(), true>);
+    AWFM_LAUNCH_WITH_EVENTS((searchKernel<false, 4, CSR(), false, NR(), true>), dim3(grid), dim3(kThreads), 0u, s, nullptr, last ? g->orderDoneEvent : nullptr,
+                            g->image->dev, dChars, off, len, nq, rng, dCounts, (unsigned long long *)nullptr, (const unsigned char *)recs, recordBytes,
+                            indexAt, numRecs, leftCount, sparse ? *sparse : SparseOut(), (const unsigned *)nullptr, 0u);
+  }, narrow, csr);
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
   if (last) g->orderDoneArmed = g->orderDoneEvent != nullptr;
   return AwFmSuccess;
 }
 
 /* the search over 16-byte records (partitionRecordsKernel), then the general kernel over the last bin */
-template <bool NARROW, bool VARLEN>
-enum AwFmReturnCode launchOrdered(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, const unsigned long long *off,
+enum AwFmReturnCode launchOrdered(AwFmGpuIndex *g, hipStream_t s, bool narrow, const uint8_t *dChars, const unsigned long long *off,
                                   uint32_t len, unsigned depth, const ulonglong2 *table, unsigned long long nq,
                                   const void *recs, const unsigned *generalCount, ulonglong2 *rng, uint32_t *dCounts,
                                   const OrderTouch *touch = nullptr, const SparseOut *sparse = nullptr,
                                   const unsigned *skipSampleAlive = nullptr, unsigned skipSamples = 0u) {
-  enum AwFmReturnCode rc;
   const BucketFormat none = BucketFormat();
-  if (touch) /* instrumented launch: the variant the image would run */
-    rc = pairSteps(g) ? launchOrderedKernel<NARROW, VARLEN, true, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, touch)
-                      : launchOrderedKernel<NARROW, VARLEN, false, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, touch);
-  else
-    rc = pairSteps(g) ? launchOrderedKernel<NARROW, VARLEN, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, nullptr, none, sparse, skipSampleAlive, skipSamples)
-                      : launchOrderedKernel<NARROW, VARLEN, false>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, nullptr, none, sparse, skipSampleAlive, skipSamples);
+  const enum AwFmReturnCode rc = withBools([&](auto NR, auto VL, auto PR) {
+    if (touch) /* instrumented launch: the variant the image would run */
+      return launchOrderedKernel<NR(), VL(), PR(), true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, touch);
+    return launchOrderedKernel<NR(), VL(), PR()>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, nullptr, none, sparse, skipSampleAlive, skipSamples);
+  }, narrow, off != nullptr, pairSteps(g));
   if (rc != AwFmSuccess) return rc;
-  return launchLeftover<NARROW, VARLEN>(g, s, dChars, off, len, nq, rng, dCounts, recs, (unsigned)sizeof(QueryRec), (unsigned)offsetof(QueryRec, index),
-                                        generalCount, sparse);
+  return launchLeftover(g, s, narrow, off != nullptr, dChars, off, len, nq, rng, dCounts, recs, nq, (unsigned)sizeof(QueryRec),
+                        (unsigned)offsetof(QueryRec, index), generalCount, sparse);
 }
 
 /* the search over bucketed 8-byte records (partitionKernel), then the general kernel over the last bucket */
-template <bool NARROW>
-enum AwFmReturnCode launchBucketed(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, uint32_t len, unsigned depth,
+enum AwFmReturnCode launchBucketed(AwFmGpuIndex *g, hipStream_t s, bool narrow, const uint8_t *dChars, uint32_t len, unsigned depth,
                                    const ulonglong2 *table, unsigned long long nq, const void *recs, const unsigned *bucketStart,
                                    const BucketFormat &fmt, const unsigned *generalCount, ulonglong2 *rng, uint32_t *dCounts,
                                    bool packed, const OrderTouch *touch, const SparseOut *sparse, bool countRecords = false) {
   /* countRecords: `sparse` names the array of {k-mer number, count} the ordered kernel fills in search order; the caller takes
    * them home and launches the general kernel over the last bucket itself (the last kernel of a search) */
-  const bool pair = pairSteps(g);
-  enum AwFmReturnCode rc;
-  if (touch)
-    rc = pair ? launchOrderedKernel<NARROW, false, true, true, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, touch, bucketStart, fmt)
-              : launchOrderedKernel<NARROW, false, false, true, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, touch, bucketStart, fmt);
-  else if (sparse && sparse->count) /* the list of hits: collected per wave */
-    rc = pair ? launchOrderedKernel<NARROW, false, true, false, true, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, bucketStart, fmt, sparse)
-              : launchOrderedKernel<NARROW, false, false, false, true, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, bucketStart, fmt, sparse);
-  else
-    rc = pair ? launchOrderedKernel<NARROW, false, true, false, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, bucketStart, fmt, sparse)
-              : launchOrderedKernel<NARROW, false, false, false, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, bucketStart, fmt, sparse);
+  const enum AwFmReturnCode rc = withBools([&](auto NR, auto PR) {
+    if (touch) return launchOrderedKernel<NR(), false, PR(), true, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, touch, bucketStart, fmt);
+    if (sparse && sparse->count) /* the list of hits: collected per wave */
+      return launchOrderedKernel<NR(), false, PR(), false, true, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, bucketStart, fmt, sparse);
+    return launchOrderedKernel<NR(), false, PR(), false, true>(g, s, len, depth, table, nq, recs, generalCount, rng, dCounts, nullptr, bucketStart, fmt, sparse);
+  }, narrow, pairSteps(g));
   if (rc != AwFmSuccess || packed || countRecords) return rc; /* bit-packed k-mers: every one of them is covered */
   /* the last bucket: k-mers with ambiguity characters; a record of it is the query number alone */
-  return launchLeftover<NARROW, false>(g, s, dChars, nullptr, len, nq, rng, dCounts, recs, 8u, 0u, generalCount, sparse);
+  return launchLeftover(g, s, narrow, false, dChars, nullptr, len, nq, rng, dCounts, recs, nq, 8u, 0u, generalCount, sparse);
 }
 
 }  // namespace
@@ -194,8 +213,6 @@ static bool orderedApplies(const AwFmGpuIndex *g, bool hasOffsets, uint32_t fixe
   return mode != 0;
 }
 
-/* milliseconds orderedSearchKernel took in the last awfmGpuSearchHits on this image that ran with
- * $AWFM_GPU_TIME_ORDERED set (waits for it); negative when there is none */
 /* awfm_device.h.  Two passes over the finished table: the saturated lengths are counted (so that the side list is
  * allocated exactly and the in-place rewrite cannot fail half-way), then deepNextKernel rewrites the entries. */
 int awfmGpuDeepSeedAddNext(AwFmGpuIndex *g, void *table, unsigned deepK, unsigned format, void **bigOut, unsigned *numBigOut) {
@@ -305,15 +322,47 @@ int awfmGpuDeepSeedAddNext(AwFmGpuIndex *g, void *table, unsigned deepK, unsigne
  * the device (orderLookup == 2) the sample's count is read back here -- a reporting call, it waits for the device.  The
  * caller holds orderMutex. */
 static bool lastSearchLookedUpFirst(AwFmGpuIndex *g) {
-  if (g->orderLookup != 2) return g->orderLookup == 1;
-  if (!g->orderSampleAt) return false;
+  const AwFmGpuIndex::OrderReport &r = g->report;
+  if (r.lookup != 2) return r.lookup == 1;
+  if (!r.sampleAt) return false;
   DeviceGuard guard(g->device);
   unsigned alive = 0;
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&alive, g->orderSampleAt, sizeof alive, hipMemcpyDeviceToHost) != hipSuccess) {
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&alive, r.sampleAt, sizeof alive, hipMemcpyDeviceToHost) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
-  return alive * 4u < g->orderSamples;
+  return alive * 4u < r.samples;
+}
+
+/* what a driver's lookup front end leaves in the report: whether its kernel runs and whether the device decides that from the
+ * sample (word `sampleAt`, threshold `samples`), its survivor counters, and the word that counts the k-mers it left to the
+ * general kernel (bucketedSearch without the kernel: the scan's total).  The caller holds orderMutex. */
+static void recordLookupFront(AwFmGpuIndex *g, bool runs, bool onDevice, const unsigned *sampleAt, unsigned samples,
+                              const unsigned *fusedKeptAt, const unsigned *keptAt) {
+  AwFmGpuIndex::OrderReport &r = g->report;
+  r.lookup = runs ? (onDevice ? 2 : 1) : 0;
+  r.sampleAt = sampleAt;
+  r.samples = samples;
+  r.lookupFused = runs; /* the k-mers still alive after the table are searched by the kernel that looked them up */
+  r.fusedKeptAt = runs ? fusedKeptAt : nullptr;
+  r.keptAt = keptAt;
+}
+
+/* the sums of words 0, 1 and 2 of the lines the waves of the last search's lookup kernel counted into: survivors, those put to
+ * its second table window, those that window dropped (waits for the device; the caller holds orderMutex).  1: read, 0: the
+ * last search did not run that kernel, -1: the read failed */
+static int readFusedCounters(AwFmGpuIndex *g, uint64_t sums[3]) {
+  sums[0] = sums[1] = sums[2] = 0;
+  if (!g->report.lookupFused || !g->report.fusedKeptAt || !lastSearchLookedUpFirst(g)) return 0;
+  DeviceGuard guard(g->device);
+  unsigned words[kFusedCounters * 16u];
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(words, g->report.fusedKeptAt, sizeof words, hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  for (unsigned i = 0; i < kFusedCounters; i++)
+    for (unsigned j = 0; j < 3u; j++) sums[j] += words[i * 16u + j];
+  return 1;
 }
 
 /* 1 when the last seed-order search on the image kept its k-mers by encodeLookupKernel: that kernel is then the one
@@ -329,26 +378,17 @@ extern "C" int awfmGpuLastOrderedKernelIsLookup(AwFmGpuIndex *g) {
 extern "C" uint64_t awfmGpuLastOrderedKept(AwFmGpuIndex *g) {
   if (!g) return 0;
   std::lock_guard<std::mutex> lock(g->orderMutex); /* the word lives in the scratch a search may be re-allocating */
-  if (!g->orderKeptAt) return 0;
+  if (!g->report.keptAt) return 0;
   DeviceGuard guard(g->device);
   unsigned kept = 0;
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&kept, g->orderKeptAt, sizeof kept, hipMemcpyDeviceToHost) != hipSuccess) {
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&kept, g->report.keptAt, sizeof kept, hipMemcpyDeviceToHost) != hipSuccess) {
     (void)hipGetLastError();
     return 0;
   }
-  if (g->orderLookupFused && g->orderFusedKeptAt && lastSearchLookedUpFirst(g)) {
-    /* the survivors were searched by the kernel that looked them up: its waves counted them (what `kept` holds are the
-     * k-mers left to the general kernel) */
-    unsigned words[kFusedCounters * 16u];
-    if (hipMemcpy(words, g->orderFusedKeptAt, sizeof words, hipMemcpyDeviceToHost) != hipSuccess) {
-      (void)hipGetLastError();
-      return 0;
-    }
-    uint64_t total = kept;
-    for (unsigned i = 0; i < kFusedCounters; i++) total += words[i * 16u];
-    return total;
-  }
-  return kept;
+  /* the survivors were searched by the kernel that looked them up: its waves counted them (what `kept` holds are then the
+   * k-mers left to the general kernel) */
+  uint64_t fused[3];
+  return readFusedCounters(g, fused) < 0 ? 0 : kept + fused[0];
 }
 
 /* {survivors the lookup kernel of the last seed-order search put to its second table window, survivors that window dropped}:
@@ -359,17 +399,10 @@ extern "C" void awfmGpuLastSecondWindow(AwFmGpuIndex *g, uint64_t out[2]) {
   out[0] = out[1] = 0;
   if (!g) return;
   std::lock_guard<std::mutex> lock(g->orderMutex);
-  if (!g->orderLookupFused || !g->orderFusedKeptAt || !lastSearchLookedUpFirst(g)) return;
-  DeviceGuard guard(g->device);
-  unsigned words[kFusedCounters * 16u];
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(words, g->orderFusedKeptAt, sizeof words, hipMemcpyDeviceToHost) != hipSuccess) {
-    (void)hipGetLastError();
-    return;
-  }
-  for (unsigned i = 0; i < kFusedCounters; i++) {
-    out[0] += words[i * 16u + 1u];
-    out[1] += words[i * 16u + 2u];
-  }
+  uint64_t fused[3];
+  if (readFusedCounters(g, fused) <= 0) return;
+  out[0] = fused[1];
+  out[1] = fused[2];
 }
 
 /* milliseconds the dominant kernel of the last awfmGpuSearchHits* on this image took -- encodeLookupKernel when the batch
@@ -379,8 +412,8 @@ extern "C" double awfmGpuLastOrderedKernelMs(AwFmGpuIndex *g) {
   if (!g) return -1.0;
   std::lock_guard<std::mutex> lock(g->orderMutex);
   const bool front = lastSearchLookedUpFirst(g);
-  if (front ? !g->orderTimedFront : !g->orderTimedKernel) return -1.0;
-  hipEvent_t from = g->orderTiming[front ? 0 : 2], to = g->orderTiming[front ? 1 : 3];
+  if (front ? !g->report.timedFront : !g->report.timedKernel) return -1.0;
+  hipEvent_t from = g->report.timing[front ? 0 : 2], to = g->report.timing[front ? 1 : 3];
   if (!from || !to) return -1.0;
   float ms = 0.0f;
   if (hipEventSynchronize(to) != hipSuccess || hipEventElapsedTime(&ms, from, to) != hipSuccess) return -1.0;
@@ -413,10 +446,10 @@ extern "C" int awfmGpuOrderedKernelLog(AwFmGpuIndex *g, double *frontMs, double 
 extern "C" double awfmGpuLastOrderedSearchKernelMs(AwFmGpuIndex *g) {
   if (!g) return -1.0;
   std::lock_guard<std::mutex> lock(g->orderMutex);
-  if (!g->orderTimedKernel || !g->orderTiming[2] || !g->orderTiming[3]) return -1.0;
+  const AwFmGpuIndex::OrderReport &r = g->report;
+  if (!r.timedKernel || !r.timing[2] || !r.timing[3]) return -1.0;
   float ms = 0.0f;
-  if (hipEventSynchronize(g->orderTiming[3]) != hipSuccess || hipEventElapsedTime(&ms, g->orderTiming[2], g->orderTiming[3]) != hipSuccess)
-    return -1.0;
+  if (hipEventSynchronize(r.timing[3]) != hipSuccess || hipEventElapsedTime(&ms, r.timing[2], r.timing[3]) != hipSuccess) return -1.0;
   return (double)ms;
 }
 
@@ -447,6 +480,7 @@ static int orderedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, 
  * that a caller with another way to the same results (the general kernel needs no scratch) takes it and the others say
  * what really happened */
 constexpr int kOrderNoScratch = -(int)AwFmAllocationFailure;
+constexpr int kOrderFailed = -(int)AwFmGeneralFailure; /* what AWFM_HIP_TRY returns from the drivers that answer 1 / 0 / -AwFmReturnCode */
 
 /* ---- gates: who used a piece of scratch last ---- */
 /* `s` is about to use what the gate guards: it waits for the last user unless that was the same stream (in the same thread:
@@ -593,8 +627,8 @@ static bool ensureOrderScratch(AwFmGpuIndex *g, size_t bytes) {
   slot.bytes = 0;
   g->dOrder = nullptr;
   g->orderBytes = 0;
-  g->orderKeptAt = nullptr;
-  g->orderSampleAt = nullptr;
+  g->report.keptAt = g->report.sampleAt = g->report.fusedKeptAt = nullptr; /* the report's device words lay in it */
+  g->report.lookupFused = false;
   g->orderPrevParity = -1;
   const size_t want = bytes + bytes / 8;
   if (hipMalloc(&slot.mem, want) != hipSuccess) {
@@ -693,6 +727,72 @@ static unsigned predictTag(AwFmGpuIndex *g, int front, unsigned fixedLength) {
   return p.searches | ((unsigned)front << 22) | ((fixedLength & 63u) << 24);
 }
 
+/* ---- what the drivers share: the prologue of a sampled search, the no-hit fill, the ordering pass ---- */
+/* the page-locked words the sampled searches publish their verdicts in; no verdicts: every search launches both front ends */
+static void ensureVerdictHost(AwFmGpuIndex *g) {
+  AwFmGpuIndex::LookupPredict &predict = g->predict;
+  if (predict.verdictHost) return;
+  if (hipHostMalloc((void **)&predict.verdictHost, 64, hipHostMallocDefault) == hipSuccess) {
+    memset(predict.verdictHost, 0, 64);
+  } else {
+    (void)hipGetLastError();
+    predict.verdictHost = nullptr;
+  }
+}
+/* lookupPrepKernel's two sample words, a line each (base, base + 128): this search adds to the one the last search on the
+ * slot left zero (*aliveOut) and zeroes the other (*aliveNext); both are zeroed here when another kind of search has used
+ * the counter block since.  The slot remembers which of them the next search finds zero. */
+static hipError_t sampleWords(AwFmGpuIndex *g, hipStream_t s, uint8_t *base, unsigned long long **aliveOut, unsigned long long **aliveNext) {
+  int parity = g->orderPrevParity;
+  if (parity < 0) {
+    const hipError_t e = hipMemsetAsync(base, 0, 256, s);
+    if (e != hipSuccess) return e;
+    parity = 0;
+  }
+  *aliveOut = (unsigned long long *)(base + 128u * (unsigned)parity);
+  *aliveNext = (unsigned long long *)(base + 128u * (unsigned)(1 - parity));
+  g->orderSlot[g->orderCur].prepParity = 1 - parity;
+  return hipSuccess;
+}
+/* dense results before a hits-only search: count 0 and an empty range under every k-mer (no ranges where the caller takes
+ * them for the k-mers with hits only and has the counts to tell) */
+static hipError_t launchFillNoHit(AwFmGpuIndex *g, hipStream_t s, ulonglong2 *rng, uint32_t *dCounts, unsigned long long nq, bool rangesOfHitsOnly) {
+  hipLaunchKernelGGL(fillNoHitKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, s, rangesOfHitsOnly && dCounts ? (ulonglong2 *)nullptr : rng, dCounts, nq);
+  return hipGetLastError();
+}
+/* a grid of at most `most` workgroups over `perShare` tiles in each share: a multiple of the 8 shares (workgroup b works on share b % 8) */
+static unsigned shareGrid(unsigned long long perShare, unsigned long long most) {
+  const unsigned grid = (unsigned)(perShare * kShares < most ? perShare * kShares : most);
+  return (grid + kShares - 1u) / kShares * kShares;
+}
+/* more dynamic LDS than 64 KB has to be asked for, per kernel and per device (a code object is loaded on every device): once
+ * for a kernel and device image, a bit of the image's mask each -- two handles that ask at once ask for the same */
+enum { kLdsPartition = 1u, kLdsCountPlace = 2u, kLdsPartitionRecordsCsr = 4u, kLdsPartitionRecordsFixed = 8u };
+static hipError_t ensureDynamicLds(AwFmGpuIndex *g, unsigned bit, const void *kernel, size_t bytes) {
+  if (g->image->dynamicLdsSet.load(std::memory_order_relaxed) & bit) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) g->image->dynamicLdsSet.fetch_or(bit, std::memory_order_relaxed);
+  return e;
+}
+/* the ordering pass over 8-byte records, behind the encode front end that left the shares' histograms in `hist`:
+ * bucketScanSharesKernel -> partitionKernel (`firstNumber`: a shard's records carry the k-mers' numbers in the WHOLE batch) */
+static hipError_t launchOrderingPass(AwFmGpuIndex *g, hipStream_t s, uint32_t fixedLength, const BucketFormat &fmt, unsigned long long nq,
+                                     unsigned *hist, unsigned *cursors, unsigned *bucketStart, unsigned *generalCount,
+                                     const unsigned long long *codes, unsigned long long *recs, unsigned honourGeneral,
+                                     const unsigned *shareCount, const unsigned *numbers, const unsigned *sampleAlive, unsigned samples,
+                                     unsigned long long firstNumber, const unsigned char *flags32) {
+  const unsigned bins = (1u << fmt.bucketBits) + 1u, binsPad = (bins + 3u) & ~3u;
+  hipLaunchKernelGGL(bucketScanSharesKernel, dim3(1), dim3(1024), 0, s, hist, bins, binsPad, bucketStart, generalCount, (unsigned)nq);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess)
+    e = ensureDynamicLds(g, kLdsPartition, (const void *)partitionKernel, kPartitionTile * 8u + 3u * (((1u << kBucketBitsMax) + 4u) & ~3u) * 4u);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(partitionKernel, dim3(shareGrid(shareSize(nq) / kPartitionTile, (unsigned long long)g->numCUs)), dim3(kPartitionThreads),
+                     (size_t)kPartitionTile * 8u + 3u * binsPad * 4u, s, codes, fixedLength, fmt, nq, (const unsigned *)hist, cursors, recs, honourGeneral,
+                     shareCount, numbers, sampleAlive, samples, firstNumber, flags32);
+  return hipGetLastError();
+}
+
 /* fillNoHitKernel -> encodeCodes4Kernel -> bucketScanSharesKernel -> partitionKernel -> orderedSearchKernel<BUCKET> ->
  * searchKernel<INDIRECT> on the caller's stream; the caller holds orderMutex.  Return values as awfmGpuOrderedSearch. */
 static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, uint32_t fixedLength, unsigned depth,
@@ -728,29 +828,15 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
   }
   OrderSlotScope slotScope(g, s);
   if (!ensureOrderScratch(g, total)) return kOrderNoScratch;
-  constexpr size_t kShareCountAt = 98304, kSampleAt = kShareCountAt + kShares * kShareCountStride * 4u; /* bytes into the counter block (tickets end at 65792) */
-  constexpr size_t kKeptAt = 102400; /* lookupSearchKernel's survivor counters: kFusedCounters words a line apart */
-  constexpr size_t kCountCursorsAt = 66048; /* countScatterKernel's cursors (zeroed with the counters) */
-  static_assert(256 + 8 * kTicketGroups * 8 * 256 <= kCountCursorsAt && kCountCursorsAt + kCountBucketsMax * 4u <= kShareCountAt, "counter block");
-  static_assert(256 + 8 * kTicketGroups * 8 * 256 <= kShareCountAt && kSampleAt + 4 <= kKeptAt && kKeptAt + kFusedCounters * 64u <= kOrderCounterBytes, "counter block");
-#define BUCKET_TRY(call)                    \
-  do {                                      \
-    hipError_t e__ = (call);                \
-    if (e__ != hipSuccess) {                \
-      setError(#call, e__);                 \
-      return -(int)AwFmGeneralFailure;      \
-    }                                       \
-  } while (0)
   uint8_t *w = (uint8_t *)g->dOrder;
   unsigned *generalCount = (unsigned *)w;
   unsigned *hist = (unsigned *)(w + histAt), *cursors = (unsigned *)(w + cursorsAt), *bucketStart = (unsigned *)(w + startAt);
   const unsigned long long *codes = packed ? (const unsigned long long *)dChars : (const unsigned long long *)(w + codesAt);
   unsigned long long *recs = (unsigned long long *)(w + recsAt);
   unsigned char *flags32 = total != flagsAt ? w + flagsAt : nullptr;
-  /* grids: multiples of the 8 shares (workgroup b works on share b % 8) */
   const unsigned long long perShare256 = (shareSize(nq) + 255ull) / 256ull;
-  unsigned encodeGrid = (unsigned)(perShare256 * kShares < (unsigned long long)g->numCUs * 8u ? perShare256 * kShares : (unsigned long long)g->numCUs * 8u);
-  encodeGrid = (encodeGrid + kShares - 1u) / kShares * kShares;
+  const unsigned encodeGrid = shareGrid(perShare256, (unsigned long long)g->numCUs * 8u);
+  /* (kShareCountAt: the bytes the 16-byte-record driver has its leftover count at) */
   unsigned *shareCount = (unsigned *)(w + kShareCountAt), *numbers = (unsigned *)(w + numbersAt);
   const unsigned useNext = g->image->dev.deepNext != 0u && pairSteps(g) && fixedLength >= depth + 2u ? 1u : 0u;
   /* lookup first: forced ($AWFM_GPU_LOOKUP_FIRST=1), or left to a sample of the batch -- 16384 k-mers at a fixed stride; the
@@ -764,28 +850,13 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
   /* the scratch's counters zeroed, the list's fill and the sample in one launch (lookupPrepKernel); a sampled batch has 2^20
    * k-mers and more */
   const bool prepFused = bySample && nq >= kSamples;
-  AwFmGpuIndex::LookupPredict &predict = g->predict;
-  if (prepFused && !predict.verdictHost) {
-    if (hipHostMalloc((void **)&predict.verdictHost, 64, hipHostMallocDefault) == hipSuccess) {
-      memset(predict.verdictHost, 0, 64);
-    } else {
-      (void)hipGetLastError();
-      predict.verdictHost = nullptr; /* no verdicts: every search launches both front ends */
-    }
-  }
+  if (prepFused) ensureVerdictHost(g);
   const int front = prepFused ? predictFront(g, fixedLength) : kFrontBoth;
-  const unsigned *sampleAlive = nullptr;
+  const unsigned *sampleAlive = nullptr, *sampleAt = (const unsigned *)(w + kSampleAt);
   bool lookupFirst = forced;
   if (prepFused) {
-    /* the two sample words, a line each (kSampleAt, kSampleAt + 128): this search adds to the one the last search on the
-     * slot left zero and zeroes the other */
-    int parity = g->orderPrevParity;
-    if (parity < 0) {
-      BUCKET_TRY(hipMemsetAsync(w + kSampleAt, 0, 256, s));
-      parity = 0;
-    }
-    unsigned long long *aliveOut = (unsigned long long *)(w + kSampleAt + 128u * (unsigned)parity);
-    unsigned long long *aliveNext = (unsigned long long *)(w + kSampleAt + 128u * (unsigned)(1 - parity));
+    unsigned long long *aliveOut, *aliveNext; /* the two sample words (kSampleAt, kSampleAt + 128) */
+    AWFM_HIP_TRY(sampleWords(g, s, w + kSampleAt, &aliveOut, &aliveNext), kOrderFailed);
     /* what the launch zeroes: everything the memset did but the sample words -- or, when only the lookup kernel follows, the
      * line of the general kernel's count and the survivor counters */
     uint4 *zeroA = (uint4 *)w, *zeroB = (uint4 *)(w + kSampleAt + 256u);
@@ -799,41 +870,25 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
     const unsigned number = predictTag(g, front, fixedLength);
     const unsigned prepGrid = front == kFrontLookupOnly && !(sparse && sparse->count) ? kSamples / 256u : 2u * (kSamples / 256u);
     hipLaunchKernelGGL(lookupPrepKernel<false>, dim3(prepGrid), dim3(256), 0, s, g->image->dev, dChars, fixedLength, depth, useNext, nq, kSamples, aliveOut,
-                       aliveNext, zeroA, vecsA, zeroB, vecsB, sparse && sparse->count ? *sparse : SparseOut(), predict.verdictHost, number);
-    BUCKET_TRY(hipGetLastError());
-    g->orderSlot[g->orderCur].prepParity = 1 - parity;
-    if (!sparse) {
-      hipLaunchKernelGGL(fillNoHitKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, s,
-                         rangesOfHitsOnly && dCounts ? (ulonglong2 *)nullptr : rng, dCounts, nq);
-      BUCKET_TRY(hipGetLastError());
-    }
-    g->orderSampleAt = (const unsigned *)aliveOut; /* (the count is the word's low half) */
-    if (front == kFrontBoth) sampleAlive = (const unsigned *)aliveOut;
+                       aliveNext, zeroA, vecsA, zeroB, vecsB, sparse && sparse->count ? *sparse : SparseOut(), g->predict.verdictHost, number);
+    AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
+    sampleAt = (const unsigned *)aliveOut; /* (the count is the word's low half) */
+    if (front == kFrontBoth) sampleAlive = sampleAt;
     else {
       bySample = false; /* the host has decided: one front end, which does not look at the sample */
       lookupFirst = front == kFrontLookupOnly;
     }
   } else {
-    BUCKET_TRY(hipMemsetAsync(w, 0, startAt, s)); /* the count, the ticket counters, the histograms, the cursors */
-    BUCKET_TRY(fillSparseList(sparse, s)); /* (lookupPrepKernel fills the list beside its other work) */
-    if (!sparse) { /* a sparse search lists its hits: there is nothing to pre-fill */
-      hipLaunchKernelGGL(fillNoHitKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, s,
-                         rangesOfHitsOnly && dCounts ? (ulonglong2 *)nullptr : rng, dCounts, nq);
-      BUCKET_TRY(hipGetLastError());
-    }
+    AWFM_HIP_TRY(hipMemsetAsync(w, 0, startAt, s), kOrderFailed); /* the count, the ticket counters, the histograms, the cursors */
+    AWFM_HIP_TRY(fillSparseList(sparse, s), kOrderFailed); /* (lookupPrepKernel fills the list beside its other work) */
     bySample = false; /* (a batch of fewer k-mers than the sample takes: forced, or not looked up first at all) */
-    g->orderSampleAt = (const unsigned *)(w + kSampleAt);
   }
+  if (!sparse) AWFM_HIP_TRY(launchFillNoHit(g, s, rng, dCounts, nq, rangesOfHitsOnly), kOrderFailed); /* (a sparse search lists its hits: nothing to pre-fill) */
   const bool lookupOnly = prepFused && front == kFrontLookupOnly; /* no ordering passes, no ordered kernel behind the lookup kernel */
-  g->orderLookup = bySample ? 2 : (lookupFirst ? 1 : 0);
-  g->orderSamples = kSamples;
-  g->orderKeptAt = lookupOnly ? generalCount : bucketStart + bins; /* the k-mers left to the general kernel / the scan's total */
-  g->orderTimedFront = false;
+  /* (lookupSearchKernel searches the k-mers still alive after the table itself; what it leaves to the general kernel, or the scan's total) */
+  recordLookupFront(g, lookupFirst || bySample, bySample, sampleAt, kSamples, (const unsigned *)(w + kKeptAt), lookupOnly ? generalCount : bucketStart + bins);
   if (lookupFirst || bySample) {
-    const bool timed = g->orderTiming[0] != nullptr; /* this search has an entry in the timing log: the events ride on the dispatch */
-    /* the k-mers still alive after the table are searched by the kernel that looked them up (lookupSearchKernel) */
-    g->orderLookupFused = true;
-    g->orderFusedKeptAt = (const unsigned *)(w + kKeptAt);
+    const bool timed = g->report.timing[0] != nullptr; /* this search has an entry in the timing log: the events ride on the dispatch */
     {
       const bool pairOff = !pairSteps(g);
       const bool superInLds = !pairOff && narrow && awfmPairSuperInLds(g);
@@ -846,8 +901,7 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
       const size_t lds = superInLds ? (size_t)g->image->dev.numPairSuper * 64u : 0u;
       /* persistent grid: what is resident (7 workgroups per CU; the 64-bit instantiation: 80 registers, 6), a multiple of the 8 shares */
       const unsigned perCU = narrow ? 7u : 6u;
-      unsigned fusedGrid = (unsigned)(perShare256 * kShares < (unsigned long long)g->numCUs * perCU ? perShare256 * kShares : (unsigned long long)g->numCUs * perCU);
-      fusedGrid = (fusedGrid + kShares - 1u) / kShares * kShares;
+      unsigned fusedGrid = shareGrid(perShare256, (unsigned long long)g->numCUs * perCU);
       /* A workgroup takes its share 1024 k-mers a trip.  A small batch is a few trips per workgroup -- 6.8 for the 1.25 * 10^7
        * k-mers of a shard of an 8-GPU run on 1792 workgroups: most take 7, and the chip idles while they finish -- so the grid
        * is trimmed to the workgroups that share the trips evenly (1744 x 7) */
@@ -860,28 +914,24 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
       }
       /* (lookup only: what the kernel does not search itself goes to the END of the record array, 8 bytes a k-mer number,
        * counted in the general kernel's word -- no code words, no numbers, no histogram) */
-#define AWFM_LOOKUP_GO(NR)                                                                                                               \
-  launchLookupSearchAt<32u, NR>(fixedLength, fusedGrid, lds, s, dev, dChars, fmt, useNext | (pairOff ? 2u : 0u) | (lookupOnly ? 4u : 0u) | secondBits, nq, \
-                                (unsigned long long *)(w + codesAt), lookupOnly ? (unsigned *)recs : numbers, lookupOnly ? generalCount : shareCount, \
-                                hist, binsPad, sampleAlive, kSamples, rng, dCounts, sparse ? *sparse : SparseOut(),                      \
-                                (unsigned *)(w + kKeptAt), flags32, timed ? g->orderTiming[0] : nullptr, timed ? g->orderTiming[1] : nullptr)
-      if (narrow) AWFM_LOOKUP_GO(true);
-      else AWFM_LOOKUP_GO(false);
-#undef AWFM_LOOKUP_GO
+      withBools([&](auto NR) {
+        launchLookupSearchAt<32u, NR()>(fixedLength, fusedGrid, lds, s, dev, dChars, fmt, useNext | (pairOff ? 2u : 0u) | (lookupOnly ? 4u : 0u) | secondBits, nq,
+                                        (unsigned long long *)(w + codesAt), lookupOnly ? (unsigned *)recs : numbers, lookupOnly ? generalCount : shareCount,
+                                        hist, binsPad, sampleAlive, kSamples, rng, dCounts, sparse ? *sparse : SparseOut(), (unsigned *)(w + kKeptAt),
+                                        flags32, timed ? g->report.timing[0] : nullptr, timed ? g->report.timing[1] : nullptr);
+      }, narrow);
     }
-    g->orderTimedFront = timed;
+    g->report.timedFront = timed;
     if (timed) g->orderLog[(g->orderLogCount - 1u) % AwFmGpuIndex::kOrderLogMax].front = true;
-    BUCKET_TRY(hipGetLastError());
+    AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
   }
   if (lookupOnly) {
     /* what the lookup kernel left (k-mers with ambiguity characters, survivors beyond a round's slots): the general kernel
      * over the tail of the record array -- the last kernel of the search: it carries the event that says the slot is free */
     enum AwFmReturnCode rc = AwFmSuccess;
-    if (!packed)
-      rc = narrow ? launchLeftover<true, false>(g, s, dChars, nullptr, fixedLength, nq, rng, dCounts, recs, 8u, 0u, generalCount, sparse)
-                  : launchLeftover<false, false>(g, s, dChars, nullptr, fixedLength, nq, rng, dCounts, recs, 8u, 0u, generalCount, sparse);
+    if (!packed) rc = launchLeftover(g, s, narrow, false, dChars, nullptr, fixedLength, nq, rng, dCounts, recs, nq, 8u, 0u, generalCount, sparse);
     if (rc != AwFmSuccess) return -(int)rc;
-    BUCKET_TRY(slotScope.end());
+    AWFM_HIP_TRY(slotScope.end(), kOrderFailed);
     return 1;
   }
   if (lookupFirst) {
@@ -891,31 +941,14 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
                        (unsigned long long *)nullptr, hist, binsPad);
   else
     launchEncode4(fixedLength, encodeGrid, bins * 4u, s, dChars, fmt, nq, (unsigned long long *)(w + codesAt), hist, binsPad, flags32, sampleAlive, kSamples);
-  BUCKET_TRY(hipGetLastError());
-  hipLaunchKernelGGL(bucketScanSharesKernel, dim3(1), dim3(1024), 0, s, hist, bins, binsPad, bucketStart, generalCount, (unsigned)nq);
-  BUCKET_TRY(hipGetLastError());
-  const size_t partitionLds = (size_t)kPartitionTile * 8u + 3u * binsPad * 4u;
-  static std::once_flag ldsOnce;
-  static hipError_t ldsError = hipSuccess;
-  std::call_once(ldsOnce, [] {
-    ldsError = hipFuncSetAttribute((const void *)partitionKernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(kPartitionTile * 8u + 3u * (((1u << kBucketBitsMax) + 4u) & ~3u) * 4u));
-  });
-  BUCKET_TRY(ldsError);
-  const unsigned long long tilesPerShare = shareSize(nq) / kPartitionTile;
-  unsigned partitionGrid = (unsigned)(tilesPerShare * kShares < (unsigned long long)g->numCUs ? tilesPerShare * kShares : (unsigned long long)g->numCUs);
-  partitionGrid = (partitionGrid + kShares - 1u) / kShares * kShares;
-  hipLaunchKernelGGL(partitionKernel, dim3(partitionGrid), dim3(kPartitionThreads), partitionLds, s, codes, fixedLength, fmt, nq,
-                     (const unsigned *)hist, cursors, recs, packed ? 0u : 1u,
-                     lookupFirst || bySample ? (const unsigned *)shareCount : (const unsigned *)nullptr,
-                     lookupFirst || bySample ? (const unsigned *)numbers : (const unsigned *)nullptr, sampleAlive, kSamples, 0ull,
-                     (const unsigned char *)flags32);
-  BUCKET_TRY(hipGetLastError());
+  AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
+  const bool lookedUp = lookupFirst || bySample; /* code words in the shares' regions, the k-mer numbers beside them */
+  AWFM_HIP_TRY(launchOrderingPass(g, s, fixedLength, fmt, nq, hist, cursors, bucketStart, generalCount, codes, recs, packed ? 0u : 1u,
+                                  lookedUp ? shareCount : nullptr, lookedUp ? numbers : nullptr, sampleAlive, kSamples, 0ull, flags32),
+               kOrderFailed);
   const SparseOut countOut{nullptr, 0u, (unsigned *)(w + countInAt), nullptr};
-  const SparseOut *results = countRecords ? &countOut : sparse;
-  const enum AwFmReturnCode rc =
-      narrow ? launchBucketed<true>(g, s, dChars, fixedLength, depth, table, nq, recs, bucketStart, fmt, generalCount, rng, dCounts, packed, touch, results, countRecords)
-                         : launchBucketed<false>(g, s, dChars, fixedLength, depth, table, nq, recs, bucketStart, fmt, generalCount, rng, dCounts, packed, touch, results, countRecords);
+  const enum AwFmReturnCode rc = launchBucketed(g, s, narrow, dChars, fixedLength, depth, table, nq, recs, bucketStart, fmt, generalCount, rng, dCounts,
+                                                packed, touch, countRecords ? &countOut : sparse, countRecords);
   if (rc != AwFmSuccess) return -(int)rc;
   if (countRecords) { /* the counts home from search order (the number of records: where the general kernel's bucket begins) */
     const unsigned *ordered = bucketStart + (1u << fmt.bucketBits);
@@ -924,24 +957,17 @@ static int bucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars,
     const unsigned scatterGrid = (unsigned)(tiles < (unsigned long long)g->numCUs * 8u ? tiles : (unsigned long long)g->numCUs * 8u); /* (16 KB of LDS each) */
     hipLaunchKernelGGL(countScatterKernel, dim3(scatterGrid ? scatterGrid : 1u), dim3(kCountScatterThreads), 0, s, (const uint2 *)(w + countInAt), ordered,
                        countBuckets, (uint2 *)(w + countOutAt), countCursors);
-    BUCKET_TRY(hipGetLastError());
-    static std::once_flag placeOnce;
-    static hipError_t placeError = hipSuccess;
-    std::call_once(placeOnce, [] {
-      placeError = hipFuncSetAttribute((const void *)countPlaceKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((1u << kCountShift) * 4u));
-    });
-    BUCKET_TRY(placeError);
+    AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
+    AWFM_HIP_TRY(ensureDynamicLds(g, kLdsCountPlace, (const void *)countPlaceKernel, (1u << kCountShift) * 4u), kOrderFailed);
     hipLaunchKernelGGL(countPlaceKernel, dim3(countBuckets), dim3(kCountPlaceThreads), (size_t)(1u << kCountShift) * 4u, s, (const uint2 *)(w + countOutAt),
                        (const unsigned *)countCursors, nq, dCounts);
-    BUCKET_TRY(hipGetLastError());
+    AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
     if (!packed) { /* the k-mers the order does not hold: stored at counts[number] */
-      const enum AwFmReturnCode left = narrow ? launchLeftover<true, false>(g, s, dChars, nullptr, fixedLength, nq, rng, dCounts, recs, 8u, 0u, generalCount, nullptr)
-                                              : launchLeftover<false, false>(g, s, dChars, nullptr, fixedLength, nq, rng, dCounts, recs, 8u, 0u, generalCount, nullptr);
+      const enum AwFmReturnCode left = launchLeftover(g, s, narrow, false, dChars, nullptr, fixedLength, nq, rng, dCounts, recs, nq, 8u, 0u, generalCount, nullptr);
       if (left != AwFmSuccess) return -(int)left;
     }
   }
-  BUCKET_TRY(slotScope.end());
-#undef BUCKET_TRY
+  AWFM_HIP_TRY(slotScope.end(), kOrderFailed);
   return 1;
 }
 
@@ -1023,15 +1049,7 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
    * device as before and its verdict published to the host, and a batch whose predecessors' verdicts have arrived and agree
    * launches ONE front end -- the lookup kernel, which then takes whatever the batch is (correct for any batch), or the
    * 16-byte-record path alone */
-  AwFmGpuIndex::LookupPredict &predict = g->predict;
-  if (bySample && !predict.verdictHost) {
-    if (hipHostMalloc((void **)&predict.verdictHost, 64, hipHostMallocDefault) == hipSuccess) {
-      memset(predict.verdictHost, 0, 64);
-    } else {
-      (void)hipGetLastError();
-      predict.verdictHost = nullptr;
-    }
-  }
+  if (bySample) ensureVerdictHost(g);
   const int front = bySample ? predictFront(g, 0u, kChooseOf) : kFrontBoth;
   const bool lookupOnly = lengthTable && (mixedForced || front == kFrontLookupOnly);
   const bool lookupRuns = lengthTable && front != kFrontOrderedOnly;
@@ -1041,43 +1059,28 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
    * bytes per k-mer; advisor, round 5) */
   const bool wholeCounts = lookupOnly && !sparse && (dCounts || rng) && !(rangesOfHitsOnly && dCounts && rng);
   const size_t total = leftAt + (lengthTable ? alignUp256(nq * 8u) : 0u);
-  /* in the counter block, beyond the ticket counters (which end at 65792): the leftover count, the sample's count, the
-   * survivor counters (kFusedCounters words a line apart) */
-  constexpr size_t kLeftCountAt = 98304, kSampleAt = 98304 + 256, kKeptAt = 102400;
-  static_assert(kKeptAt + kFusedCounters * 64u <= kOrderCounterBytes, "counter block");
   if (orderBeginSlot(g, s) != hipSuccess) {
     setError("seed-order search: could not order the use of its scratch across streams");
     return -(int)AwFmGeneralFailure;
   }
   OrderSlotScope slotScope(g, s);
   if (!ensureOrderScratch(g, total)) return kOrderNoScratch;
-#define WIDE_TRY(call)                      \
-  do {                                      \
-    hipError_t e__ = (call);                \
-    if (e__ != hipSuccess) {                \
-      setError(#call, e__);                 \
-      return -(int)AwFmGeneralFailure;      \
-    }                                       \
-  } while (0)
   uint8_t *w = (uint8_t *)g->dOrder;
   unsigned *generalCount = (unsigned *)w;
   unsigned *hist = (unsigned *)(w + histAt), *cursors = (unsigned *)(w + cursorsAt), *bucketStart = (unsigned *)(w + startAt);
   QueryRec *recsIn = (QueryRec *)(w + inAt), *recsOut = (QueryRec *)(w + outAt);
-  WIDE_TRY(hipMemsetAsync(w, 0, startAt, s));
-  WIDE_TRY(fillSparseList(sparse, s));
-  if (!sparse && !wholeCounts) {
-    hipLaunchKernelGGL(fillNoHitKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, s,
-                       rangesOfHitsOnly && dCounts ? (ulonglong2 *)nullptr : rng, dCounts, nq);
-    WIDE_TRY(hipGetLastError());
-  }
+  AWFM_HIP_TRY(hipMemsetAsync(w, 0, startAt, s), kOrderFailed);
+  AWFM_HIP_TRY(fillSparseList(sparse, s), kOrderFailed);
+  if (!sparse && !wholeCounts) AWFM_HIP_TRY(launchFillNoHit(g, s, rng, dCounts, nq, rangesOfHitsOnly), kOrderFailed);
   const unsigned *sampleAlive = nullptr;
+  unsigned *sampleWord = (unsigned *)(w + kWideSampleAt);
   if (bySample) { /* the sample: always taken (the next searches' prediction), consulted on the device when both front ends run */
     const bool pairOff = !pairSteps(g);
     const unsigned useNext = (g->image->dev.deepNext != 0u && !pairOff ? 1u : 0u) | (pairOff ? 2u : 0u);
-    unsigned *sampleWord = (unsigned *)(w + kSampleAt);
     static_assert(kSamples == kPredictSamples, "the verdict is judged against the sample's size");
     const unsigned number = predictTag(g, front, 0u);
-    WIDE_TRY(awfmGpuLaunchMixedSample(g, s, lengthTable, dChars, off, nq, useNext, kSamples, (unsigned long long *)sampleWord, predict.verdictHost, number));
+    AWFM_HIP_TRY(awfmGpuLaunchMixedSample(g, s, lengthTable, dChars, off, nq, useNext, kSamples, (unsigned long long *)sampleWord, g->predict.verdictHost, number),
+                 kOrderFailed);
     if (front == kFrontBoth) sampleAlive = sampleWord;
   }
   if (lookupRuns) {
@@ -1087,35 +1090,27 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
     /* the superblock bases of the pair image are read from memory: 24 KB of them in LDS (a 3.1 Gbp image) would leave room
      * for 3 workgroups per CU where the survivors' slots alone allow 6 (10^8 8..30-mers: 6.36 against 6.74 ms) */
     const bool superInLds = false;
-    unsigned *leftoverCount = (unsigned *)(w + kLeftCountAt), *sampleWord = (unsigned *)(w + kSampleAt), *kept = (unsigned *)(w + kKeptAt);
+    /* (kLeftCountAt: the bytes the 8-byte-record driver has its share counts at) */
+    unsigned *leftoverCount = (unsigned *)(w + kLeftCountAt), *kept = (unsigned *)(w + kKeptAt);
     unsigned long long *leftover = (unsigned long long *)(w + leftAt);
-    g->orderLookup = sampleAlive ? 2 : 1;
-    g->orderSampleAt = sampleWord;
-    g->orderSamples = kChooseOf;
-    g->orderLookupFused = true;
-    g->orderFusedKeptAt = kept;
-    g->orderKeptAt = leftoverCount;
+    recordLookupFront(g, true, sampleAlive != nullptr, sampleWord, kChooseOf, kept, leftoverCount);
     const SparseOut out = sparse ? *sparse : SparseOut();
-    const bool timed = g->orderTiming[0] != nullptr; /* this search has an entry in the timing log: the events ride on the dispatch */
-    WIDE_TRY(awfmGpuLaunchMixedLookup(g, s, timed ? g->orderTiming[0] : nullptr, timed ? g->orderTiming[1] : nullptr, lengthTable, dChars, off, nq,
-                                      useNext, superInLds, sampleAlive, kChooseOf, rng, dCounts, out.count, out.cap, out.kmers, out.ranges, leftover,
-                                      leftoverCount, kept));
-    g->orderTimedFront = timed;
+    const bool timed = g->report.timing[0] != nullptr; /* this search has an entry in the timing log: the events ride on the dispatch */
+    AWFM_HIP_TRY(awfmGpuLaunchMixedLookup(g, s, timed ? g->report.timing[0] : nullptr, timed ? g->report.timing[1] : nullptr, lengthTable, dChars, off, nq,
+                                          useNext, superInLds, sampleAlive, kChooseOf, rng, dCounts, out.count, out.cap, out.kmers, out.ranges, leftover,
+                                          leftoverCount, kept),
+                 kOrderFailed);
+    g->report.timedFront = timed;
     if (timed) g->orderLog[(g->orderLogCount - 1u) % AwFmGpuIndex::kOrderLogMax].front = true;
     /* what the lookup kernel left: the last *leftoverCount records of the list */
-    {
-      const enum AwFmReturnCode left =
-          awfmImageNarrow(g) ? launchLeftover<true, true>(g, s, dChars, off, fixedLength, nq, rng, dCounts, leftover, 8u, 0u, leftoverCount, sparse, lookupOnly)
-                             : launchLeftover<false, true>(g, s, dChars, off, fixedLength, nq, rng, dCounts, leftover, 8u, 0u, leftoverCount, sparse, lookupOnly);
-      if (left != AwFmSuccess) return -(int)left; /* (not lookup only: more kernels follow, and the last one carries the slot's event) */
-    }
+    const enum AwFmReturnCode left =
+        launchLeftover(g, s, awfmImageNarrow(g), true, dChars, off, fixedLength, nq, rng, dCounts, leftover, nq, 8u, 0u, leftoverCount, sparse, lookupOnly);
+    if (left != AwFmSuccess) return -(int)left; /* (not lookup only: more kernels follow, and the last one carries the slot's event) */
     if (lookupOnly) { /* forced or predicted: the other front end is not launched */
-      WIDE_TRY(slotScope.end());
+      AWFM_HIP_TRY(slotScope.end(), kOrderFailed);
       return 1;
     }
-  } else if (bySample) { /* predicted: the 16-byte-record path alone */
-    g->orderLookup = 0;
-  }
+  } /* (else, predicted: the 16-byte-record path alone -- the report stays as orderedSearch reset it) */
   const unsigned long long encodeTiles = (nq + 255ull) / 256ull;
   const unsigned encodeGrid = (unsigned)(encodeTiles < (unsigned long long)g->numCUs * 8u ? encodeTiles : (unsigned long long)g->numCUs * 8u);
   const unsigned seedK = g->image->dev.seedK, deepK = g->image->dev.deepK;
@@ -1125,18 +1120,12 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
   else
     hipLaunchKernelGGL((encodeRecordsKernel<false>), dim3(encodeGrid), dim3(256), 0, s, dChars, off, fixedLength, depth, seedK, deepK, nq,
                        recsIn, hist);
-  WIDE_TRY(hipGetLastError());
+  AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
   hipLaunchKernelGGL(bucketScanKernel, dim3(1), dim3(1024), 0, s, (const unsigned *)hist, bins, bucketStart, generalCount);
-  WIDE_TRY(hipGetLastError());
+  AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
   const size_t lds = (size_t)kWideTile * 16u + 3u * binsPad * 4u;
-  static std::once_flag ldsOnce;
-  static hipError_t ldsError = hipSuccess;
-  std::call_once(ldsOnce, [] {
-    ldsError = hipFuncSetAttribute((const void *)partitionRecordsKernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (ldsError == hipSuccess)
-      ldsError = hipFuncSetAttribute((const void *)partitionRecordsKernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
-  WIDE_TRY(ldsError);
+  AWFM_HIP_TRY(ensureDynamicLds(g, kLdsPartitionRecordsCsr, (const void *)partitionRecordsKernel<true>, lds), kOrderFailed);
+  AWFM_HIP_TRY(ensureDynamicLds(g, kLdsPartitionRecordsFixed, (const void *)partitionRecordsKernel<false>, lds), kOrderFailed);
   const unsigned long long tiles = (nq + kWideTile - 1ull) / kWideTile;
   const unsigned grid = (unsigned)(tiles < (unsigned long long)g->numCUs ? tiles : (unsigned long long)g->numCUs);
   if (off)
@@ -1145,17 +1134,11 @@ static int wideBucketedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCh
   else
     hipLaunchKernelGGL((partitionRecordsKernel<false>), dim3(grid), dim3(kPartitionThreads), lds, s, (const QueryRec *)recsIn, depth, seedK,
                        deepK, nq, (const unsigned *)bucketStart, cursors, recsOut);
-  WIDE_TRY(hipGetLastError());
-  const bool narrow = awfmImageNarrow(g);
-  enum AwFmReturnCode rc;
-#define WIDE_GO(NR, VL) \
-  launchOrdered<NR, VL>(g, s, dChars, off, fixedLength, depth, table, nq, recsOut, generalCount, rng, dCounts, touch, sparse, sampleAlive, kChooseOf)
-  if (off) rc = narrow ? WIDE_GO(true, true) : WIDE_GO(false, true);
-  else rc = narrow ? WIDE_GO(true, false) : WIDE_GO(false, false);
-#undef WIDE_GO
+  AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
+  const enum AwFmReturnCode rc = launchOrdered(g, s, awfmImageNarrow(g), dChars, off, fixedLength, depth, table, nq, recsOut, generalCount, rng, dCounts,
+                                               touch, sparse, sampleAlive, kChooseOf);
   if (rc != AwFmSuccess) return -(int)rc;
-  WIDE_TRY(slotScope.end());
-#undef WIDE_TRY
+  AWFM_HIP_TRY(slotScope.end(), kOrderFailed);
   return 1;
 }
 
@@ -1183,10 +1166,7 @@ static int orderedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, 
   }
 
   std::lock_guard<std::mutex> lock(g->orderMutex);
-  g->orderLookup = 0;
-  g->orderTimedFront = false;
-  g->orderTimedKernel = false;
-  for (int i = 0; i < 4; i++) g->orderTiming[i] = nullptr;
+  g->report = AwFmGpuIndex::OrderReport();
   if (awfmKnob(AWFM_KNOB_TIME_ORDERED)) { /* measurement hook: this search's entry of the timing log */
     DeviceGuard guard(g->device);
     const unsigned at = (unsigned)(g->orderLogCount % AwFmGpuIndex::kOrderLogMax);
@@ -1197,7 +1177,7 @@ static int orderedSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, 
       if (!entry.ev[i]) ok = hipEventCreate(&entry.ev[i]) == hipSuccess;
     if (ok) {
       entry.front = entry.kernel = false;
-      for (int i = 0; i < 4; i++) g->orderTiming[i] = entry.ev[i];
+      for (int i = 0; i < 4; i++) g->report.timing[i] = entry.ev[i];
       g->orderLogCount++;
     } else {
       (void)hipGetLastError();
@@ -1253,15 +1233,7 @@ static int aminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
   /* [counters 4 KB: sample @0, leftover count @64 B, survivor counters @256 B][leftover list: nq x 8 B] */
   constexpr size_t kCounterBytes = 256u + kFusedCounters * 64u;
   const size_t listAt = alignUp256(kCounterBytes), total = listAt + alignUp256(nq * 8u);
-#define AMINO_TRY(call)                     \
-  do {                                      \
-    hipError_t e__ = (call);                \
-    if (e__ != hipSuccess) {                \
-      setError(#call, e__);                 \
-      return -(int)AwFmGeneralFailure;      \
-    }                                       \
-  } while (0)
-  AMINO_TRY(orderBeginSlot(g, s));
+  AWFM_HIP_TRY(orderBeginSlot(g, s), kOrderFailed);
   OrderSlotScope slotScope(g, s);
   if (!ensureOrderScratch(g, total)) return kOrderNoScratch;
   uint8_t *w = (uint8_t *)g->dOrder;
@@ -1271,15 +1243,7 @@ static int aminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
    * (lookupPrepKernel<true>; the sample's two words at bytes 0 and 128 of the counter block), and only the kernel an earlier
    * search's sample named when its verdict has reached the host (predictFront: 1 = this kernel, 2 = the general kernel) */
   const bool prepFused = !forced;
-  AwFmGpuIndex::LookupPredict &predict = g->predict;
-  if (prepFused && !predict.verdictHost) {
-    if (hipHostMalloc((void **)&predict.verdictHost, 64, hipHostMallocDefault) == hipSuccess) {
-      memset(predict.verdictHost, 0, 64);
-    } else {
-      (void)hipGetLastError();
-      predict.verdictHost = nullptr;
-    }
-  }
+  if (prepFused) ensureVerdictHost(g);
   /* the lookup kernel has a slot for every k-mer of a round (round 5): it is chosen while fewer than `percent` of the sample
    * are still alive after their entry (lookupChosen compares 4 x alive with the number it is given) -- the general kernel
    * keeps twice the chains in flight per wave, which wins when nearly every k-mer goes on for several steps (k-mers drawn
@@ -1290,70 +1254,49 @@ static int aminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
   const unsigned *sampleAlive = nullptr;
   unsigned *sampleWord = (unsigned *)w;
   if (prepFused) {
-    int parity = g->orderPrevParity;
-    if (parity < 0) {
-      AMINO_TRY(hipMemsetAsync(w, 0, 256, s));
-      parity = 0;
-    }
-    unsigned long long *aliveOut = (unsigned long long *)(w + 128u * (unsigned)parity);
-    unsigned long long *aliveNext = (unsigned long long *)(w + 128u * (unsigned)(1 - parity));
+    unsigned long long *aliveOut, *aliveNext;
+    AWFM_HIP_TRY(sampleWords(g, s, w, &aliveOut, &aliveNext), kOrderFailed);
     static_assert(kSamples == kPredictSamples, "the verdict is judged against the sample's size");
     const unsigned number = predictTag(g, front, fixedLength);
     hipLaunchKernelGGL(lookupPrepKernel<true>, dim3(sparse && sparse->count ? 2u * (kSamples / 256u) : kSamples / 256u), dim3(256), 0, s, g->image->dev, dChars,
                        fixedLength, g->image->dev.deepK, 0u, nq, kSamples, aliveOut, aliveNext, (uint4 *)(w + 64), 64u / 16u, (uint4 *)(w + 256),
-                       (unsigned)(kFusedCounters * 64u / 16u), sparse && sparse->count ? *sparse : SparseOut(), predict.verdictHost, number);
-    AMINO_TRY(hipGetLastError());
-    g->orderSlot[g->orderCur].prepParity = 1 - parity;
+                       (unsigned)(kFusedCounters * 64u / 16u), sparse && sparse->count ? *sparse : SparseOut(), g->predict.verdictHost, number);
+    AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
     sampleWord = (unsigned *)aliveOut;
     if (front == kFrontBoth) sampleAlive = sampleWord;
   } else { /* forced: no sample */
-    AMINO_TRY(hipMemsetAsync(w, 0, kCounterBytes, s));
-    AMINO_TRY(fillSparseList(sparse, s));
+    AWFM_HIP_TRY(hipMemsetAsync(w, 0, kCounterBytes, s), kOrderFailed);
+    AWFM_HIP_TRY(fillSparseList(sparse, s), kOrderFailed);
   }
-  if (!sparse) {
-    hipLaunchKernelGGL(fillNoHitKernel, dim3((unsigned)g->numCUs * 8u), dim3(256), 0, s,
-                       rangesOfHitsOnly && dCounts ? (ulonglong2 *)nullptr : rng, dCounts, nq);
-    AMINO_TRY(hipGetLastError());
-  }
+  if (!sparse) AWFM_HIP_TRY(launchFillNoHit(g, s, rng, dCounts, nq, rangesOfHitsOnly), kOrderFailed);
   const bool lookupRuns = !(prepFused && front == kFrontOrderedOnly), generalRuns = !forced && !(prepFused && front == kFrontLookupOnly);
-  g->orderLookup = sampleAlive ? 2 : (lookupRuns ? 1 : 0);
-  g->orderSampleAt = sampleWord;
-  g->orderSamples = chooseOf;
-  g->orderLookupFused = true;
-  g->orderFusedKeptAt = kept;
-  g->orderKeptAt = leftoverCount;
+  recordLookupFront(g, lookupRuns, sampleAlive != nullptr, sampleWord, chooseOf, kept, leftoverCount);
   const SparseOut out = sparse ? *sparse : SparseOut();
+  /* the general kernel: over the whole batch (`alive`: only when the sample says so), or over the records the lookup kernel left */
+  auto general = [&](bool indirect, const unsigned *alive, unsigned aliveOf) {
+    withBools([&](auto NR, auto INDIRECT) {
+      const unsigned grid = residentGrid(g, searchKernel<true, 2, false, false, NR(), INDIRECT()>);
+      hipLaunchKernelGGL((searchKernel<true, 2, false, false, NR(), INDIRECT()>), dim3(grid), dim3(kThreads), 0, s, g->image->dev, dChars,
+                         (const unsigned long long *)nullptr, fixedLength, nq, rng, dCounts, (unsigned long long *)nullptr,
+                         indirect ? (const unsigned char *)leftover : nullptr, indirect ? 8u : 0u, 0u, indirect ? nq : 0ull,
+                         indirect ? (const unsigned *)leftoverCount : nullptr, out, alive, aliveOf);
+    }, narrow, indirect);
+    return hipGetLastError();
+  };
   if (lookupRuns) {
     const unsigned long long rounds = (nq + 1023ull) / 1024ull; /* a workgroup takes 1024 k-mers a round */
-    unsigned grid = narrow ? residentGrid(g, aminoLookupSearchKernel<10u, true>) : residentGrid(g, aminoLookupSearchKernel<10u, false>);
-    if (rounds < grid) grid = (unsigned)rounds;
-    if (narrow) launchAminoLookupAt<kMaxLength, true>(fixedLength, grid ? grid : 1u, s, g->image->dev, dChars, nq, sampleAlive, chooseOf, rng, dCounts, out, leftover, leftoverCount, kept);
-    else launchAminoLookupAt<kMaxLength, false>(fixedLength, grid ? grid : 1u, s, g->image->dev, dChars, nq, sampleAlive, chooseOf, rng, dCounts, out, leftover, leftoverCount, kept);
-    AMINO_TRY(hipGetLastError());
+    withBools([&](auto NR) {
+      unsigned grid = residentGrid(g, aminoLookupSearchKernel<10u, NR()>);
+      if (rounds < grid) grid = (unsigned)rounds;
+      launchAminoLookupAt<kMaxLength, NR()>(fixedLength, grid ? grid : 1u, s, g->image->dev, dChars, nq, sampleAlive, chooseOf, rng, dCounts, out, leftover, leftoverCount, kept);
+    }, narrow);
+    AWFM_HIP_TRY(hipGetLastError(), kOrderFailed);
   }
-  if (generalRuns) { /* the whole batch through the general kernel when the sample says so (it returns at once otherwise) */
-#define AMINO_GENERAL(NR, ...)                                                                                                     \
-  do {                                                                                                                             \
-    const unsigned grid__ = residentGrid(g, searchKernel<true, 2, false, false, NR, __VA_ARGS__>);                                 \
-    hipLaunchKernelGGL((searchKernel<true, 2, false, false, NR, __VA_ARGS__>), dim3(grid__), dim3(kThreads), 0, s, g->image->dev, dChars, \
-                       (const unsigned long long *)nullptr, fixedLength, nq, rng, dCounts, (unsigned long long *)nullptr, AMINO_GENERAL_ARGS); \
-  } while (0)
-#define AMINO_GENERAL_ARGS (const unsigned char *)nullptr, 0u, 0u, 0ull, (const unsigned *)nullptr, out, sampleAlive, chooseOf
-    if (narrow) AMINO_GENERAL(true, false);
-    else AMINO_GENERAL(false, false);
-#undef AMINO_GENERAL_ARGS
-    AMINO_TRY(hipGetLastError());
-  }
-  if (lookupRuns) { /* what the lookup kernel left: the last *leftoverCount records of the list */
-#define AMINO_GENERAL_ARGS (const unsigned char *)leftover, 8u, 0u, nq, (const unsigned *)leftoverCount, out, (const unsigned *)nullptr, 0u
-    if (narrow) AMINO_GENERAL(true, true);
-    else AMINO_GENERAL(false, true);
-#undef AMINO_GENERAL_ARGS
-#undef AMINO_GENERAL
-    AMINO_TRY(hipGetLastError());
-  }
-  AMINO_TRY(slotScope.end());
-#undef AMINO_TRY
+  /* the whole batch through the general kernel when the sample says so (it returns at once otherwise) */
+  if (generalRuns) AWFM_HIP_TRY(general(false, sampleAlive, chooseOf), kOrderFailed);
+  /* what the lookup kernel left: the last *leftoverCount records of the list */
+  if (lookupRuns) AWFM_HIP_TRY(general(true, nullptr, 0u), kOrderFailed);
+  AWFM_HIP_TRY(slotScope.end(), kOrderFailed);
   return 1;
 }
 int awfmGpuAminoLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dChars, uint32_t fixedLength, unsigned long long nq,
@@ -1394,37 +1337,22 @@ int awfmGpuExactLookupSearch(AwFmGpuIndex *g, hipStream_t s, const uint8_t *dCha
   std::lock_guard<std::mutex> lock(g->orderMutex);
   /* [counters 256 B: the leftover count][leftover list: nq x 8 B] */
   const size_t listAt = 256u, total = listAt + alignUp256(nq * 8u);
-#define EXACT_TRY(call)                     \
-  do {                                      \
-    hipError_t e__ = (call);                \
-    if (e__ != hipSuccess) {                \
-      setError(#call, e__);                 \
-      return -(int)AwFmGeneralFailure;      \
-    }                                       \
-  } while (0)
-  EXACT_TRY(orderBeginSlot(g, s));
+  AWFM_HIP_TRY(orderBeginSlot(g, s), kOrderFailed);
   OrderSlotScope slotScope(g, s);
   if (!ensureOrderScratch(g, total)) return kOrderNoScratch;
   uint8_t *w = (uint8_t *)g->dOrder;
   unsigned *leftoverCount = (unsigned *)w;
   unsigned long long *leftover = (unsigned long long *)(w + listAt);
-  EXACT_TRY(hipMemsetAsync(w, 0, 256, s));
+  AWFM_HIP_TRY(hipMemsetAsync(w, 0, 256, s), kOrderFailed);
   const bool pairOff = !pairSteps(g);
-  EXACT_TRY(awfmGpuLaunchExactLookup(g, s, nullptr, nullptr, lengthTable, dChars, off, fixedLength, nq, pairOff, rng, dCounts, leftover, leftoverCount));
+  AWFM_HIP_TRY(awfmGpuLaunchExactLookup(g, s, nullptr, nullptr, lengthTable, dChars, off, fixedLength, nq, pairOff, rng, dCounts, leftover, leftoverCount),
+               kOrderFailed);
   /* what the lookup kernel left, letter by letter (exact by construction): the last kernel of the search carries the event
    * that says the scratch slot is free again */
-  {
-    const bool narrow = awfmImageNarrow(g);
-    const unsigned long long *csr = (const unsigned long long *)off;
-    enum AwFmReturnCode left;
-    if (off) left = narrow ? launchLeftover<true, true>(g, s, dChars, csr, fixedLength, nq, rng, dCounts, leftover, 8u, 0u, leftoverCount, nullptr)
-                           : launchLeftover<false, true>(g, s, dChars, csr, fixedLength, nq, rng, dCounts, leftover, 8u, 0u, leftoverCount, nullptr);
-    else left = narrow ? launchLeftover<true, false>(g, s, dChars, nullptr, fixedLength, nq, rng, dCounts, leftover, 8u, 0u, leftoverCount, nullptr)
-                       : launchLeftover<false, false>(g, s, dChars, nullptr, fixedLength, nq, rng, dCounts, leftover, 8u, 0u, leftoverCount, nullptr);
-    if (left != AwFmSuccess) return -(int)left;
-  }
-  EXACT_TRY(slotScope.end());
-#undef EXACT_TRY
+  const enum AwFmReturnCode left =
+      launchLeftover(g, s, awfmImageNarrow(g), off != nullptr, dChars, off, fixedLength, nq, rng, dCounts, leftover, nq, 8u, 0u, leftoverCount, nullptr);
+  if (left != AwFmSuccess) return -(int)left;
+  AWFM_HIP_TRY(slotScope.end(), kOrderFailed);
   return 1;
 }
 
@@ -1717,43 +1645,24 @@ extern "C" enum AwFmReturnCode awfmGpuOrderKmers(AwFmGpuIndex *g, const uint8_t 
   const size_t histAt = kOrderCounterBytes, cursorsAt = histAt + alignUp256((size_t)kShares * binsPad * 4u);
   const size_t codesAt = cursorsAt + alignUp256((size_t)kShares * binsPad * 4u), flagsAt = codesAt + alignUp256(nq * 8u);
   const size_t total = flagsAt + flags32Bytes(fixedLength, nq, false);
-#define SHARD_TRY(call)                     \
-  do {                                      \
-    hipError_t e__ = (call);                \
-    if (e__ != hipSuccess) {                \
-      setError(#call, e__);                 \
-      return AwFmGeneralFailure;            \
-    }                                       \
-  } while (0)
-  SHARD_TRY(orderBeginSlot(g, s));
+  AWFM_HIP_TRY(orderBeginSlot(g, s), AwFmGeneralFailure);
   OrderSlotScope slotScope(g, s);
   if (!ensureOrderScratch(g, total)) return AwFmAllocationFailure;
   uint8_t *w = (uint8_t *)g->dOrder;
   unsigned *generalCount = (unsigned *)w, *hist = (unsigned *)(w + histAt), *cursors = (unsigned *)(w + cursorsAt);
   unsigned long long *codes = (unsigned long long *)(w + codesAt);
   unsigned char *flags32 = total != flagsAt ? w + flagsAt : nullptr;
-  SHARD_TRY(hipMemsetAsync(w, 0, codesAt, s));
-  const unsigned long long perShare256 = (shareSize(nq) + 255ull) / 256ull;
-  unsigned encodeGrid = (unsigned)(perShare256 * kShares < (unsigned long long)g->numCUs * 8u ? perShare256 * kShares : (unsigned long long)g->numCUs * 8u);
-  encodeGrid = (encodeGrid + kShares - 1u) / kShares * kShares;
+  AWFM_HIP_TRY(hipMemsetAsync(w, 0, codesAt, s), AwFmGeneralFailure);
+  const unsigned encodeGrid = shareGrid((shareSize(nq) + 255ull) / 256ull, (unsigned long long)g->numCUs * 8u);
   launchEncode4(fixedLength, encodeGrid, bins * 4u, s, dChars, fmt, nq, codes, hist, binsPad, flags32);
-  SHARD_TRY(hipGetLastError());
-  hipLaunchKernelGGL(bucketScanSharesKernel, dim3(1), dim3(1024), 0, s, hist, bins, binsPad, (unsigned *)dBucketStart, generalCount, (unsigned)nq);
-  SHARD_TRY(hipGetLastError());
-  const size_t partitionLds = (size_t)kPartitionTile * 8u + 3u * binsPad * 4u;
-  SHARD_TRY(hipFuncSetAttribute((const void *)partitionKernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(kPartitionTile * 8u + 3u * (((1u << kBucketBitsMax) + 4u) & ~3u) * 4u)));
-  const unsigned long long tilesPerShare = shareSize(nq) / kPartitionTile;
-  unsigned partitionGrid = (unsigned)(tilesPerShare * kShares < (unsigned long long)g->numCUs ? tilesPerShare * kShares : (unsigned long long)g->numCUs);
-  partitionGrid = (partitionGrid + kShares - 1u) / kShares * kShares;
+  AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
   /* (the records carry the k-mers' numbers in the WHOLE batch: firstNumber + the number in this shard) */
-  hipLaunchKernelGGL(partitionKernel, dim3(partitionGrid), dim3(kPartitionThreads), partitionLds, s, (const unsigned long long *)codes, fixedLength, fmt, nq,
-                     (const unsigned *)hist, cursors, (unsigned long long *)dRecords, 1u, (const unsigned *)nullptr, (const unsigned *)nullptr,
-                     (const unsigned *)nullptr, 0u, (unsigned long long)firstNumber, (const unsigned char *)flags32);
-  SHARD_TRY(hipGetLastError());
+  AWFM_HIP_TRY(launchOrderingPass(g, s, fixedLength, fmt, nq, hist, cursors, (unsigned *)dBucketStart, generalCount, codes, (unsigned long long *)dRecords, 1u,
+                                  nullptr, nullptr, nullptr, 0u, (unsigned long long)firstNumber, flags32),
+               AwFmGeneralFailure);
   /* (the size of the last bin -- the k-mers awfmGpuSearchGeneralRecords takes -- behind the bucket starts) */
-  SHARD_TRY(hipMemcpyAsync(dBucketStart + bins + 1u, generalCount, 4, hipMemcpyDeviceToDevice, s));
-  SHARD_TRY(slotScope.end());
+  AWFM_HIP_TRY(hipMemcpyAsync(dBucketStart + bins + 1u, generalCount, 4, hipMemcpyDeviceToDevice, s), AwFmGeneralFailure);
+  AWFM_HIP_TRY(slotScope.end(), AwFmGeneralFailure);
   return AwFmSuccess;
 }
 
@@ -1857,19 +1766,16 @@ extern "C" enum AwFmReturnCode awfmGpuSearchOrderedRecordsCounts(AwFmGpuIndex *g
   if (!ensureOrderScratch(g, kOrderCounterBytes)) return AwFmAllocationFailure;
   unsigned *generalCount = (unsigned *)g->dOrder;
   AWFM_HIP_TRY(hipMemsetAsync(generalCount, 0, kOrderCounterBytes, s), AwFmGeneralFailure);
-  for (int i = 0; i < 4; i++) g->orderTiming[i] = nullptr;
+  for (int i = 0; i < 4; i++) g->report.timing[i] = nullptr;
   SparseOut out;
   out.count = nullptr;
   out.cap = 0;
   out.kmers = (unsigned *)dOrderKmers;
   out.ranges = (ulonglong2 *)dOrderRanges;
-  const bool pair = pairSteps(g);
-  enum AwFmReturnCode rc;
-#define SHARD_GO(NR, PR) \
-  launchOrderedKernel<NR, false, PR, false, true>(g, s, fixedLength, depth, table, totalQueries, dRecords, generalCount, nullptr, dOrderCounts, nullptr, (const unsigned *)dBucketStart, fmt, &out)
-  if (awfmImageNarrow(g)) rc = pair ? SHARD_GO(true, true) : SHARD_GO(true, false);
-  else rc = pair ? SHARD_GO(false, true) : SHARD_GO(false, false);
-#undef SHARD_GO
+  const enum AwFmReturnCode rc = withBools([&](auto NR, auto PR) {
+    return launchOrderedKernel<NR(), false, PR(), false, true>(g, s, fixedLength, depth, table, totalQueries, dRecords, generalCount, nullptr, dOrderCounts,
+                                                               nullptr, (const unsigned *)dBucketStart, fmt, &out);
+  }, awfmImageNarrow(g), pairSteps(g));
   if (rc != AwFmSuccess) return rc;
   AWFM_HIP_TRY(slotScope.end(), AwFmGeneralFailure);
   return AwFmSuccess;
@@ -1903,20 +1809,10 @@ extern "C" enum AwFmReturnCode awfmGpuSearchGeneralRecords(AwFmGpuIndex *g, cons
   out.kmers = (unsigned *)dOrderKmers;
   out.ranges = (ulonglong2 *)dOrderRanges;
   const uint8_t *base = dChars - (size_t)firstNumber * fixedLength;
-  const bool narrow = awfmImageNarrow(g);
-  const unsigned grid = narrow ? residentGrid(g, searchKernel<false, 4, false, false, true, true>) : residentGrid(g, searchKernel<false, 4, false, false, false, true>);
-  if (narrow)
-    hipLaunchKernelGGL((searchKernel<false, 4, false, false, true, true>), dim3(grid), dim3(kThreads), 0, s, g->image->dev, base, (const unsigned long long *)nullptr, fixedLength,
-                       (unsigned long long)(firstNumber + numQueries), (ulonglong2 *)nullptr, (unsigned *)nullptr, (unsigned long long *)nullptr,
-                       (const unsigned char *)dRecords, 8u, 0u, (unsigned long long)numQueries, leftCount, out, (const unsigned *)nullptr, 0u);
-  else
-    hipLaunchKernelGGL((searchKernel<false, 4, false, false, false, true>), dim3(grid), dim3(kThreads), 0, s, g->image->dev, base, (const unsigned long long *)nullptr, fixedLength,
-                       (unsigned long long)(firstNumber + numQueries), (ulonglong2 *)nullptr, (unsigned *)nullptr, (unsigned long long *)nullptr,
-                       (const unsigned char *)dRecords, 8u, 0u, (unsigned long long)numQueries, leftCount, out, (const unsigned *)nullptr, 0u);
-  AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
-  return AwFmSuccess;
+  /* (not the last kernel of a search on a scratch slot: it uses none) */
+  return launchLeftover(g, s, awfmImageNarrow(g), false, base, nullptr, fixedLength, (unsigned long long)(firstNumber + numQueries), nullptr, nullptr, dRecords,
+                        (unsigned long long)numQueries, 8u, 0u, leftCount, &out, false);
 }
-#undef SHARD_TRY
 
 extern "C" enum AwFmReturnCode awfmGpuCompactHits(AwFmGpuIndex *g, const uint32_t *dCounts, const struct AwFmSearchRange *dRanges,
                                                   uint64_t numQueries, uint64_t *dFlagOffsets, void *dScratch, uint32_t *dHitKmers,
