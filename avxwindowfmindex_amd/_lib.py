@@ -50,6 +50,7 @@ GPU_SYMBOLS = [
     "awfmScoreWindowsAffine", "awfmGpuScoreWindowsAffineScratchBytes", "awfmGpuScoreWindowsAffine",
     "awfmPairMates", "awfmGpuPairMates", "awfmReverseComplementReads", "awfmGpuReverseComplementReads",
     "awfmInsertHistogram", "awfmGpuInsertHistogram", "awfmInsertInterval", "awfmGpuInsertInterval", "awfmGpuPairMatesEstimated",
+    "awfmAlignmentStrings", "awfmGpuAlignmentStringsScratchBytes", "awfmGpuAlignmentStrings",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -179,6 +180,17 @@ class AwFmInsertEstimate(C.Structure):
     """struct AwFmInsertEstimate (include/awfm_gpu.h): 64 bytes, minInsert and maxInsert first"""
     _fields_ = [("minInsert", C.c_int64), ("maxInsert", C.c_int64), ("quartiles", C.c_int64 * 3), ("mean", C.c_int64),
                 ("numSamples", C.c_uint64), ("valid", C.c_uint64)]
+
+
+class AwFmStringInputs(C.Structure):
+    """struct AwFmStringInputs (include/awfm_gpu.h, "alignment strings"): host or device addresses"""
+    _fields_ = [("sequences", C.c_void_p), ("slots", C.c_void_p), ("textBegins", C.c_void_p), ("numOps", C.c_void_p), ("ops", C.c_void_p)]
+
+
+class AwFmStringOutputs(C.Structure):
+    """struct AwFmStringOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL, and the arenas' capacities"""
+    _fields_ = [("cigarOffsets", C.c_void_p), ("cigarChars", C.c_void_p), ("cigarCapacity", C.c_uint64), ("mdOffsets", C.c_void_p),
+                ("mdChars", C.c_void_p), ("mdCapacity", C.c_uint64), ("numSkipped", C.c_void_p), ("numOverflow", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -362,6 +374,11 @@ def lib():
         "awfmInsertHistogram": (C.c_int, [C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmInsertParams), vp, vp, vp, C.c_uint]),
         "awfmGpuInsertHistogram": (C.c_int, [vp, C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmInsertParams), vp, vp, vp, vp]),
         "awfmInsertInterval": (C.c_int, [vp, C.POINTER(AwFmInsertParams), C.POINTER(AwFmInsertEstimate)]),
+        "awfmAlignmentStrings": (C.c_int, [C.POINTER(AwFmStringInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.c_int,
+                                           C.POINTER(AwFmStringOutputs), C.c_uint]),
+        "awfmGpuAlignmentStringsScratchBytes": (u64, [vp, u64]),
+        "awfmGpuAlignmentStrings": (C.c_int, [vp, C.POINTER(AwFmStringInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.POINTER(AwFmStringOutputs), vp, vp]),
         "awfmGpuInsertInterval": (C.c_int, [vp, vp, C.POINTER(AwFmInsertParams), vp, vp]),
         "awfmGpuPairMatesEstimated": (C.c_int, [vp, C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmPairParams), vp,
                                                 C.POINTER(AwFmPairOutputs), vp]),

@@ -658,6 +658,92 @@ def align_chains_affine_host(read_chars, read_offsets, slots, chosen, text, sequ
     return result
 
 
+STRINGS_CIGAR_M = 1  # AWFM_STRINGS_CIGAR_M: the classic CIGAR, '=' and 'X' merged into M
+STRING_INPUTS = (("sequences", np.uint32), ("slots", np.uint32), ("textBegins", np.uint64), ("numOps", np.uint32), ("ops", np.uint32))
+
+
+def string_inputs(sequences, slots, text_begins, num_ops, ops):
+    """struct AwFmStringInputs (include/awfm_gpu.h, "alignment strings") from five addresses, host or device: the slot table's
+    sequences, the slots the alignment call was given, and its textBegins, numOps and ops"""
+    return _lib.AwFmStringInputs(sequences or None, slots or None, text_begins or None, num_ops or None, ops or None)
+
+
+def string_outputs(**addresses):
+    """struct AwFmStringOutputs from addresses by field name (cigarOffsets, cigarChars, mdOffsets, mdChars, numSkipped,
+    numOverflow) and the two capacities (cigarCapacity, mdCapacity); a field left out is NULL or 0"""
+    out = _lib.AwFmStringOutputs()
+    for name, value in addresses.items():
+        if name not in dict(_lib.AwFmStringOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, int(value) if name.endswith("Capacity") else (value or None))
+    return out
+
+
+def strings_of(offsets, chars):
+    """the strings of a packed arena as a list of bytes: read r's is chars[offsets[r] : offsets[r + 1]]"""
+    data = np.ascontiguousarray(chars, dtype=np.uint8).tobytes()
+    return [data[int(offsets[r]):int(offsets[r + 1])] for r in range(len(offsets) - 1)]
+
+
+def alignment_strings_host(sequences, slots, text_begins, num_ops, ops, text, sequence_ends=None, alphabet=AwFmAlphabetDna, classic=False,
+                           cigar_capacity=None, md_capacity=None, outputs=None, threads=4, fill=None, skipped_before=0, overflow_before=0,
+                           flags=None, max_candidates=None, max_ops=None):
+    """awfmAlignmentStrings (include/awfm_gpu.h, "alignment strings"), the host twin: sequences shaped (reads, max_candidates), slots,
+    text_begins and num_ops per read, ops shaped (reads, max_ops) -> a dict of cigarOffsets, mdOffsets (uint64, reads + 1),
+    cigarChars, mdChars (uint8 arenas of the capacity given; None: exactly what the strings need, found by a first call for the
+    offsets), numSkipped and numOverflow (ints: the values before plus this call's).  outputs: the names to compute (None: all);
+    the others are passed as NULL and left out.  fill: the value (per byte) the arrays hold before the call."""
+    seq = np.ascontiguousarray(sequences, dtype=np.uint32)
+    arrays = {"sequences": seq, "slots": np.ascontiguousarray(slots, dtype=np.uint32), "textBegins": np.ascontiguousarray(text_begins, dtype=np.uint64),
+              "numOps": np.ascontiguousarray(num_ops, dtype=np.uint32), "ops": np.ascontiguousarray(ops, dtype=np.uint32)}
+    n = arrays["slots"].size
+    if seq.ndim != 2 or seq.shape[0] != n or arrays["ops"].ndim != 2 or arrays["ops"].shape[0] != n or arrays["textBegins"].shape != (n,) \
+            or arrays["numOps"].shape != (n,):
+        raise ValueError("sequences is shaped (reads, max_candidates), ops (reads, max_ops), the others (reads,)")
+    t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    ends = None if sequence_ends is None else np.ascontiguousarray(sequence_ends, dtype=np.uint64)
+    C_ = seq.shape[1] if max_candidates is None else max_candidates
+    M_ = arrays["ops"].shape[1] if max_ops is None else max_ops
+    flags = (STRINGS_CIGAR_M if classic else 0) if flags is None else flags
+    names = ["cigarOffsets", "cigarChars", "mdOffsets", "mdChars", "numSkipped", "numOverflow"]
+    outputs = names if outputs is None else list(outputs)
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a is not None and a.size else dummy.ctypes.data
+
+    sin = string_inputs(*(address(arrays[name]) for name, _ in STRING_INPUTS))
+
+    def call(sout):
+        rc = _lib.lib().awfmAlignmentStrings(C.byref(sin), n, C_, M_, flags, address(t), t.size,
+                                             None if ends is None or not ends.size else ends.ctypes.data, 0 if ends is None else ends.size,
+                                             alphabet, C.byref(sout), threads)
+        _check("awfmAlignmentStrings", rc)
+
+    if (cigar_capacity is None and "cigarChars" in outputs) or (md_capacity is None and "mdChars" in outputs):
+        sizing = {"cigarOffsets": np.zeros(n + 1, np.uint64), "mdOffsets": np.zeros(n + 1, np.uint64)}
+        call(string_outputs(**{name: a.ctypes.data for name, a in sizing.items()}))
+        cigar_capacity = int(sizing["cigarOffsets"][n]) if cigar_capacity is None else cigar_capacity
+        md_capacity = int(sizing["mdOffsets"][n]) if md_capacity is None else md_capacity
+    result = {}
+    for name, size, dtype in (("cigarOffsets", n + 1, np.uint64), ("cigarChars", cigar_capacity or 0, np.uint8), ("mdOffsets", n + 1, np.uint64),
+                              ("mdChars", md_capacity or 0, np.uint8)):
+        if name in outputs:
+            result[name] = np.zeros(size, dtype)
+            if fill is not None:
+                result[name].view(np.uint8)[...] = fill
+    counters = {"numSkipped": np.array([skipped_before], np.uint64), "numOverflow": np.array([overflow_before], np.uint64)}
+    sout = string_outputs(cigarCapacity=cigar_capacity or 0, mdCapacity=md_capacity or 0, **{name: address(a) for name, a in result.items()})
+    for name, counter in counters.items():
+        if name in outputs:
+            setattr(sout, name, counter.ctypes.data)
+    call(sout)
+    for name, counter in counters.items():
+        if name in outputs:
+            result[name] = int(counter[0])
+    return result
+
+
 SCORE_MAX_MAPQ = 254  # AWFM_SCORE_MAX_MAPQ: upper limit of mapq_cap (255 is SAM's "unavailable")
 SCORE_SLOT_OUTPUTS = (("slotScores", np.uint32), ("slotReadEnds", np.uint32), ("slotTextEnds", np.uint64))
 SCORE_READ_OUTPUTS = (("bestSlots", np.uint32), ("bestScores", np.uint32), ("secondSlots", np.uint32), ("secondScores", np.uint32),
@@ -1217,6 +1303,21 @@ class GpuIndex:
                _lib.lib().awfmGpuAlignChainsAffine(self.handle, C.byref(inputs), d_slots or None, num_reads, max_candidates, band_pad, max_drift,
                                                    None if costs is None else C.byref(costs), max_ops, max_rows, C.byref(outputs),
                                                    d_scratch or None, stream or None))
+
+    # alignment strings (include/awfm_gpu.h) ------------------------------
+    def alignment_strings_scratch_bytes(self, num_reads):
+        """awfmGpuAlignmentStringsScratchBytes: the bytes of device scratch alignment_strings needs for num_reads reads"""
+        return int(_lib.lib().awfmGpuAlignmentStringsScratchBytes(self.handle, num_reads))
+
+    def alignment_strings(self, inputs, num_reads, outputs, d_scratch, max_candidates=4, max_ops=32, classic=False, flags=None, stream=0):
+        """awfmGpuAlignmentStrings: inputs string_inputs(...) and outputs string_outputs(...) of device addresses -- the arrays as
+        align_chains or align_chains_affine left them --, d_scratch alignment_strings_scratch_bytes(num_reads) bytes of device memory
+        of this call's own, aligned to 16 bytes; the CIGAR (classic: with M) and the MD:Z string of every read, packed behind
+        their offsets; asynchronous on `stream`; *numSkipped and *numOverflow are added to"""
+        flags = (STRINGS_CIGAR_M if classic else 0) if flags is None else flags
+        _check("awfmGpuAlignmentStrings",
+               _lib.lib().awfmGpuAlignmentStrings(self.handle, None if inputs is None else C.byref(inputs), num_reads, max_candidates, max_ops,
+                                                  flags, None if outputs is None else C.byref(outputs), d_scratch or None, stream or None))
 
     # slot scores and mapping quality (include/awfm_gpu.h) -----------------
     def score_chains_affine(self, inputs, num_reads, outputs, max_candidates=4, band_pad=8, max_drift=15, scoring=AFFINE_SCORING,

@@ -1284,6 +1284,10 @@ extern "C" uint64_t awfmGpuHitBudget(const AwFmGpuIndex *g);
 /* exclusive scan of the flags (counts[i] != 0) into dFlagOffsets[0..n] (awfm_gpu.hip); scratch as for the hit offsets */
 enum AwFmReturnCode awfmGpuScanFlags(AwFmGpuIndex *g, const uint32_t *dCounts, uint64_t numQueries, uint64_t *dFlagOffsets,
                                      void *dScratch, hipStream_t s);
+/* the scan behind awfmGpuHitOffsetsOnDevice over any 32-bit counts, whatever the image's size (awfm_gpu_locate.hip): dOffsets[0..n]
+ * = their exclusive prefix sums in 64 bits, dOffsets[n] the total; scratch as for the hit offsets; the caller guards the device */
+enum AwFmReturnCode awfmGpuScanCounts(AwFmGpuIndex *g, const uint32_t *dCounts, uint64_t numCounts, uint64_t *dOffsets, void *dScratch,
+                                      hipStream_t s);
 /* awfm_gpu_build.hip: level-wise construction of the deeper seed table into a new device buffer */
 /* peakBytesOut (may be NULL): the most device memory the construction held at once (the table and the level below it) */
 /* allocSecondsOut (may be NULL): wall seconds spent inside the hipMalloc calls of the levels -- on this pool a process's first

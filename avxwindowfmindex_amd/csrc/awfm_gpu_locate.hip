@@ -553,6 +553,15 @@ enum AwFmReturnCode awfmGpuScanFlags(AwFmGpuIndex *g, const uint32_t *dCounts, u
   return scanRecursive<kScanFlags>(dCounts, numQueries, (unsigned long long *)dFlagOffsets, (unsigned long long *)dScratch, s);
 }
 
+enum AwFmReturnCode awfmGpuScanCounts(AwFmGpuIndex *g, const uint32_t *dCounts, uint64_t numCounts, uint64_t *dOffsets, void *dScratch,
+                                      hipStream_t s) {
+  if (!g || !dCounts || !dOffsets || !dScratch || numCounts == 0) {
+    setError("awfmGpuScanCounts: null argument");
+    return AwFmNullPtrError;
+  }
+  return scanRecursive<kScanU32>(dCounts, numCounts, (unsigned long long *)dOffsets, (unsigned long long *)dScratch, s);
+}
+
 extern "C" {
 
 enum AwFmReturnCode awfmGpuLocate(AwFmGpuIndex *g, const struct AwFmSearchRange *dRanges,

@@ -91,6 +91,8 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   pair_group=64           awfmGpuPairMates: a wave per pair also where 16 lanes hold the candidates
  *   insert_tier=global      awfmGpuInsertHistogram: global atomics at any bin count (default: a private histogram in LDS per
  *                       workgroup up to 8192 bins)
+ *   strings_tier=direct     awfmGpuAlignmentStrings: every wave stores its strings read by read in bytes (default: a span that
+ *                       fits the LDS tile is formatted there and stored in dwords)
  *   second_window=0|1   the lookup kernel's second table window (a survivor's leftmost characters): 0 never, 1 on every trip;
  *                       unset, the kernel's own gate decides trip by trip (the results are the same either way)
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
@@ -1155,6 +1157,85 @@ enum AwFmReturnCode awfmGpuInsertInterval(AwFmGpuIndex *g, const uint64_t *dHist
 enum AwFmReturnCode awfmGpuPairMatesEstimated(AwFmGpuIndex *g, const struct AwFmPairInputs *dIn, uint64_t numPairs, uint32_t maxCandidates,
                                               const struct AwFmPairParams *params, const struct AwFmInsertEstimate *dEstimate,
                                               const struct AwFmPairOutputs *dOut, void *stream);
+
+/* ---- alignment strings: the CIGAR and the MD:Z string of every aligned read, packed, on host and device ----
+ * The last step to a mapper's output record.  Both strings are functions of arrays that lie on the device after
+ * awfmGpuAlignChains or awfmGpuAlignChainsAffine -- the scripts, where they begin in their record -- and of the text, which only
+ * the library holds there (awfmGpuIndexSetText): no script and no text window is downloaded to make them.  The host twin
+ * (csrc/awfm_strings.c) is the definition and the checker of the device call.
+ *
+ * INPUTS (struct AwFmStringInputs), as the alignment calls left them: sequences [numReads * C], the slot table's; slots
+ * [numReads], the array the alignment call was given; textBegins [numReads], sequence-local; numOps [numReads]; ops [numReads *
+ * maxOps].  C = maxCandidates 1..16, maxOps 1..AWFM_ALIGN_MAX_OPS, numReads < 2^32, flags: AWFM_STRINGS_CIGAR_M or 0 (anything
+ * outside its range, or another bit: AwFmIllegalPositionError).  A missing input array: AwFmNullPtrError.  The read characters
+ * are no input: neither string needs them.  The call TRUSTS the script: '=' and 'X' are not checked against the text.
+ *
+ * Per read r, in this order, with k = numOps[r], j = slots[r] and run i = (len_i, op_i) = (ops[r * maxOps + i] >> 4, & 15):
+ *   NONE      k == 0: both strings are empty, the read is counted nowhere and nothing else of it is read.
+ *   SKIPPED   both strings are empty, the read is counted in *numSkipped and NOTHING of the text is read through it, when any of
+ *             these holds: k > maxOps (a truncated row); j >= C (AWFM_CHAINS_NO_SLOT among them); s = sequences[r * C + j] >=
+ *             max(numRecords, 1) (no record table: one sequence, the text); the record's end lies beyond the text's length or
+ *             before its begin; a run with len == 0 or an op outside {1 I, 2 D, 4 S, 7 =, 8 X}; the script's read length (the sum
+ *             of len over I, S, =, X) exceeds AWFM_ALIGN_MAX_LENGTH; its text length Tn (the sum over =, X, D) exceeds 2 *
+ *             AWFM_ALIGN_MAX_LENGTH; with L the record's length, textBegins[r] > L or Tn > L - textBegins[r].  Sums are taken in
+ *             64 bits; with the two caps a string stays below 2^19 bytes.
+ *   otherwise the read gets both strings:
+ *     CIGAR, extended  for every run in order len in decimal without leading zeros, then its letter I D S = X;
+ *     CIGAR, classic   (AWFM_STRINGS_CIGAR_M) the same, except that every maximal sequence of adjacent '=' and 'X' runs becomes
+ *                      ONE run, its length their sum, its letter M;
+ *     MD               p = the global text position of the record's begin + textBegins[r], m = 0; for every run in order:
+ *                      '=': m += len, p += len;  'X': for each of its len characters emit m in decimal, then letter(text[p]), m =
+ *                      0, p += 1;  'D': emit m in decimal, then '^', then letter of text[p .. p + len), m = 0, p += len;  I, S:
+ *                      nothing.  After the last run emit m.  letter(c): a..z are raised to upper case, A..Z stay, every other
+ *                      byte becomes N on a nucleotide image and X on an amino one.  The result matches
+ *                      [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*: the 0 between adjacent mismatches, and between a deletion and a
+ *                      mismatch, falls out of the rule.
+ *
+ * OUTPUTS (struct AwFmStringOutputs; every pointer may be NULL): cigarOffsets / mdOffsets [numReads + 1] are the exclusive prefix
+ * sums of the TRUE string lengths whatever the capacities are; cigarChars / mdChars are arenas of cigarCapacity / mdCapacity
+ * bytes.  An arena without its offsets: AwFmNullPtrError; offsets without an arena are how a caller sizes one.  A read's string
+ * is written to an arena exactly when offsets[r + 1] <= that arena's capacity; a read with a non-empty string that was not
+ * written to at least one requested arena is counted once in *numOverflow.  No byte of an arena beyond min(total, capacity) is
+ * written, nor any byte that belongs to a read that does not fit.  Both counters are ADDED to.  numReads == 0 succeeds and
+ * touches nothing.
+ *
+ * awfmAlignmentStrings (csrc/awfm_strings.c): over `threads` threads of the pool, one formatter counts and writes; text, record
+ * table and alphabet are parameters as with the alignment twins.  awfmGpuAlignmentStrings (csrc/awfm_strings_kernel.h): text,
+ * record table and alphabet are the image's (AwFmUnsupportedVersionError without a text); asynchronous on `stream`, no host
+ * wait, no allocation.  A lengths kernel (a thread per read, the rows in 16-byte loads where maxOps % 4 == 0, no text), the
+ * library's on-device scan once per requested offsets array, and a write kernel: a wave owns 64 consecutive reads, hence one
+ * contiguous span of each arena; it formats the span in LDS and stores it in whole dwords, the span's edges up to the next dword
+ * boundary as bytes; a span beyond the LDS tile is stored read by read in bytes ($AWFM_GPU_DIAG strings_tier=direct: every
+ * wave; tests, the result is the same).  Text loads are aligned dwords that hold a byte the record owns, issued only for reads
+ * that passed every check.  dScratch: awfmGpuAlignmentStringsScratchBytes(g, numReads) bytes, 16-byte aligned
+ * (AwFmIllegalPositionError otherwise; NULL: AwFmNullPtrError), this call's own until it has finished -- two streams may run the
+ * call at once with a dScratch each.  Out of scope: hard clips, N, P, BAM bytes. */
+#define AWFM_STRINGS_CIGAR_M 1u /* flags: the classic CIGAR, '=' and 'X' merged into M */
+struct AwFmStringInputs {
+  const uint32_t *sequences;  /* [numReads * maxCandidates]  the slot table's */
+  const uint32_t *slots;      /* [numReads]  what the alignment call was given */
+  const uint64_t *textBegins; /* [numReads]  sequence-local */
+  const uint32_t *numOps;     /* [numReads] */
+  const uint32_t *ops;        /* [numReads * maxOps]  run << 4 | op */
+};
+struct AwFmStringOutputs {
+  uint64_t *cigarOffsets; /* [numReads + 1] */
+  uint8_t *cigarChars;    /* cigarCapacity bytes */
+  uint64_t cigarCapacity;
+  uint64_t *mdOffsets;    /* [numReads + 1] */
+  uint8_t *mdChars;       /* mdCapacity bytes */
+  uint64_t mdCapacity;
+  uint64_t *numSkipped;   /* one counter, added to */
+  uint64_t *numOverflow;  /* one counter, added to */
+};
+enum AwFmReturnCode awfmAlignmentStrings(const struct AwFmStringInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t maxOps,
+                                         uint32_t flags, const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds,
+                                         uint64_t numRecords, enum AwFmAlphabetType alphabet, const struct AwFmStringOutputs *out,
+                                         unsigned threads);
+uint64_t awfmGpuAlignmentStringsScratchBytes(const AwFmGpuIndex *g, uint64_t numReads);
+enum AwFmReturnCode awfmGpuAlignmentStrings(AwFmGpuIndex *g, const struct AwFmStringInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
+                                            uint32_t maxOps, uint32_t flags, const struct AwFmStringOutputs *dOut, void *dScratch,
+                                            void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
