@@ -971,7 +971,8 @@ def test_list_sorted_scanned_and_located_without_a_host_wait(oracle, awfm, requi
 @pytest.mark.parametrize("shape", ["sparse", "half", "clustered", "repeats"])
 def test_list_tail_in_one_launch(oracle, awfm, require_gpu, wide, shape, dense_sa):
     """awfmGpuSearchHitsCompact -> awfmGpuListLocateOnDevice: the appended list comes out in k-mer order with its hit offsets
-    and positions from ONE kernel (each workgroup finds its own prefix: no scan, no scratch), with and without the full suffix
+    and positions from ONE kernel (each workgroup finds its own prefix: no scan, no scratch -- up to 2^18 entries; the fall-back
+    beyond them, with its scan and scratch, is held by tests/test_gpu_locate_chain.py at 2^18 + 1), with and without the full suffix
     array, equal to the oracle's and to what the three calls it replaces leave; `clustered`: a stretch of 12 000 consecutive
     k-mers that all occur, i.e. more entries in one workgroup's range than its LDS slots hold (sub-ranges); a position buffer
     that is too small gets the first `capacity` hits and nothing behind them; offsets only when there is no buffer.  `repeats`:
