@@ -47,6 +47,8 @@ GPU_SYMBOLS = [
     "awfmAlignChains", "awfmGpuAlignChainsScratchBytes", "awfmGpuAlignChains",
     "awfmAlignChainsAffine", "awfmGpuAlignChainsAffineScratchBytes", "awfmGpuAlignChainsAffine",
     "awfmScoreChainsAffine", "awfmGpuScoreChainsAffine",
+    "awfmMatrixScoringUniform", "awfmMatrixScoringFromText", "awfmScoreChainsMatrix", "awfmGpuScoreChainsMatrix", "awfmAlignChainsMatrix",
+    "awfmGpuAlignChainsMatrix",
     "awfmScoreWindowsAffine", "awfmGpuScoreWindowsAffineScratchBytes", "awfmGpuScoreWindowsAffine",
     "awfmPairMates", "awfmGpuPairMates", "awfmReverseComplementReads", "awfmGpuReverseComplementReads",
     "awfmInsertHistogram", "awfmGpuInsertHistogram", "awfmInsertInterval", "awfmGpuInsertInterval", "awfmGpuPairMatesEstimated",
@@ -120,6 +122,12 @@ class AwFmAlignOutputs(C.Structure):
 class AwFmAlignScoring(C.Structure):
     """struct AwFmAlignScoring (include/awfm_gpu.h): match 1..255, mismatch 0..255, gapOpen 0..255, gapExtend 1..255"""
     _fields_ = [("match", C.c_uint32), ("mismatch", C.c_uint32), ("gapOpen", C.c_uint32), ("gapExtend", C.c_uint32)]
+
+
+class AwFmMatrixScoring(C.Structure):
+    """struct AwFmMatrixScoring (include/awfm_gpu.h): 21 x 21 substitution values [class(read) * 21 + class(text)], gapOpen 0..255,
+    gapExtend 1..255"""
+    _fields_ = [("substitution", C.c_int8 * (21 * 21)), ("gapOpen", C.c_uint32), ("gapExtend", C.c_uint32)]
 
 
 class AwFmAffineOutputs(C.Structure):
@@ -361,6 +369,16 @@ def lib():
         "awfmAlignChainsAffine": (C.c_int, [C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmAlignScoring),
                                             C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmAffineOutputs), C.c_uint]),
         "awfmGpuAlignChainsAffineScratchBytes": (u64, [vp, C.c_uint32]),
+        "awfmMatrixScoringUniform": (C.c_int, [C.c_int, C.POINTER(AwFmAlignScoring), C.POINTER(AwFmMatrixScoring)]),
+        "awfmMatrixScoringFromText": (C.c_int, [C.c_int, vp, u64, C.c_uint32, C.c_uint32, C.POINTER(AwFmMatrixScoring)]),
+        "awfmAlignChainsMatrix": (C.c_int, [C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmMatrixScoring),
+                                            C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmAffineOutputs), C.c_uint]),
+        "awfmGpuAlignChainsMatrix": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.POINTER(AwFmMatrixScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmAffineOutputs), vp, vp]),
+        "awfmScoreChainsMatrix": (C.c_int, [C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmMatrixScoring),
+                                            C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmSlotScoreOutputs), C.c_uint]),
+        "awfmGpuScoreChainsMatrix": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.POINTER(AwFmMatrixScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmSlotScoreOutputs), vp]),
         "awfmGpuAlignChainsAffine": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmAffineOutputs), vp, vp]),
         "awfmScoreChainsAffine": (C.c_int, [C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmAlignScoring),

@@ -599,6 +599,46 @@ def align_scoring(match=1, mismatch=4, gap_open=6, gap_extend=1):
     return _lib.AwFmAlignScoring(match, mismatch, gap_open, gap_extend)
 
 
+MATRIX_CLASSES = 21  # AWFM_MATRIX_CLASSES
+
+
+def matrix_scoring(substitution, gap_open=6, gap_extend=1):
+    """struct AwFmMatrixScoring (include/awfm_gpu.h, "substitution matrices") from 21 x 21 int8 values, [class of the read's character,
+    class of the text's], and the gap costs"""
+    values = np.ascontiguousarray(substitution)
+    if values.shape != (MATRIX_CLASSES, MATRIX_CLASSES) or (values < -128).any() or (values > 127).any():
+        raise ValueError("a substitution matrix is 21 x 21 values of -128 .. 127")
+    out = _lib.AwFmMatrixScoring()
+    out.substitution[:] = [int(v) for v in values.reshape(-1)]
+    out.gapOpen, out.gapExtend = gap_open, gap_extend
+    return out
+
+
+def matrix_values(matrix):
+    """the 21 x 21 values of a struct AwFmMatrixScoring as an int8 array"""
+    return np.array(matrix.substitution[:], np.int8).reshape(MATRIX_CLASSES, MATRIX_CLASSES)
+
+
+def matrix_scoring_uniform(alphabet=AwFmAlphabetDna, scoring=AFFINE_SCORING):
+    """awfmMatrixScoringUniform: the matrix under which the matrix calls equal the affine ones under `scoring`"""
+    costs = scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+    out = _lib.AwFmMatrixScoring()
+    _check("awfmMatrixScoringUniform", _lib.lib().awfmMatrixScoringUniform(alphabet, C.byref(costs), C.byref(out)))
+    return out
+
+
+def matrix_scoring_from_text(text, alphabet=AwFmAlphabetAmino, gap_open=11, gap_extend=1, num_bytes=None):
+    """awfmMatrixScoringFromText: the usual matrix text format (bytes or str; num_bytes: only that many of them) -> a struct
+    AwFmMatrixScoring"""
+    data = text.encode() if isinstance(text, str) else bytes(text)
+    size = len(data) if num_bytes is None else num_bytes
+    block = np.frombuffer(data[:size], np.uint8).copy()  # exactly the bytes the call may read
+    out = _lib.AwFmMatrixScoring()
+    _check("awfmMatrixScoringFromText", _lib.lib().awfmMatrixScoringFromText(alphabet, block.ctypes.data if size else None, size, gap_open,
+                                                                              gap_extend, C.byref(out)))
+    return out
+
+
 def affine_outputs(**addresses):
     """struct AwFmAffineOutputs from addresses by field name (scores, editDistances, readBegins, readEnds, textBegins, textEnds,
     numOps, ops, numUnaligned, numTruncated); a field left out is NULL"""
@@ -617,6 +657,23 @@ def align_chains_affine_host(read_chars, read_offsets, slots, chosen, text, sequ
     mismatch, gap_open, gap_extend) -> a dict of scores, editDistances, readBegins, readEnds, textBegins, textEnds, numOps per read,
     ops shaped (reads, max_ops), numUnaligned and numTruncated (ints: the values before plus this call's).  outputs: the names to
     compute (None: all); the others are passed as NULL and left out.  fill: the value (per byte) the arrays hold before the call."""
+    costs = scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+    return _align_chains_scored_host("awfmAlignChainsAffine", costs, read_chars, read_offsets, slots, chosen, text, sequence_ends, alphabet,
+                                     band_pad, max_drift, max_ops, threads, outputs, num_read_chars, fill, unaligned_before, truncated_before)
+
+
+def align_chains_matrix_host(read_chars, read_offsets, slots, chosen, text, matrix, sequence_ends=None, alphabet=AwFmAlphabetDna, band_pad=8,
+                             max_drift=15, max_ops=32, threads=4, outputs=None, num_read_chars=None, fill=None, unaligned_before=0,
+                             truncated_before=0):
+    """awfmAlignChainsMatrix (include/awfm_gpu.h, "substitution matrices"): align_chains_affine_host with a matrix_scoring(...) in
+    place of the scoring (None: the call's NULL)"""
+    return _align_chains_scored_host("awfmAlignChainsMatrix", matrix, read_chars, read_offsets, slots, chosen, text, sequence_ends, alphabet,
+                                     band_pad, max_drift, max_ops, threads, outputs, num_read_chars, fill, unaligned_before, truncated_before)
+
+
+def _align_chains_scored_host(symbol, costs, read_chars, read_offsets, slots, chosen, text, sequence_ends, alphabet, band_pad, max_drift, max_ops,
+                              threads, outputs, num_read_chars, fill, unaligned_before, truncated_before):
+    """the two calls above: `symbol` with `costs`, the struct it takes"""
     chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
     t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
     o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
@@ -647,11 +704,10 @@ def align_chains_affine_host(read_chars, read_offsets, slots, chosen, text, sequ
     for name, counter in counters.items():
         if name in outputs:
             setattr(aout, name, counter.ctypes.data)
-    costs = scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
-    rc = _lib.lib().awfmAlignChainsAffine(C.byref(vin), address(which), n, shape[1], band_pad, max_drift, C.byref(costs), max_ops, address(t),
-                                          t.size, None if ends is None or not ends.size else ends.ctypes.data,
-                                          0 if ends is None else ends.size, alphabet, C.byref(aout), threads)
-    _check("awfmAlignChainsAffine", rc)
+    rc = getattr(_lib.lib(), symbol)(C.byref(vin), address(which), n, shape[1], band_pad, max_drift, None if costs is None else C.byref(costs),
+                                     max_ops, address(t), t.size, None if ends is None or not ends.size else ends.ctypes.data,
+                                     0 if ends is None else ends.size, alphabet, C.byref(aout), threads)
+    _check(symbol, rc)
     for name, counter in counters.items():
         if name in outputs:
             result[name] = int(counter[0])
@@ -769,6 +825,23 @@ def score_chains_affine_host(read_chars, read_offsets, slots, text, sequence_end
     bestScores, secondSlots, secondScores, mappingQualities per read, numUnscored and numMapped (ints: the values before plus this
     call's).  outputs: the names to compute (None: all); the others are passed as NULL and left out.  fill: the value (per byte)
     the arrays hold before the call."""
+    costs = scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
+    return _score_chains_scored_host("awfmScoreChainsAffine", costs, read_chars, read_offsets, slots, text, sequence_ends, alphabet, band_pad,
+                                     max_drift, min_score, mapq_cap, threads, outputs, num_read_chars, fill, unscored_before, mapped_before)
+
+
+def score_chains_matrix_host(read_chars, read_offsets, slots, text, matrix, sequence_ends=None, alphabet=AwFmAlphabetDna, band_pad=8, max_drift=15,
+                             min_score=0, mapq_cap=60, threads=4, outputs=None, num_read_chars=None, fill=None, unscored_before=0,
+                             mapped_before=0):
+    """awfmScoreChainsMatrix (include/awfm_gpu.h, "substitution matrices"): score_chains_affine_host with a matrix_scoring(...) in
+    place of the scoring (None: the call's NULL)"""
+    return _score_chains_scored_host("awfmScoreChainsMatrix", matrix, read_chars, read_offsets, slots, text, sequence_ends, alphabet, band_pad,
+                                     max_drift, min_score, mapq_cap, threads, outputs, num_read_chars, fill, unscored_before, mapped_before)
+
+
+def _score_chains_scored_host(symbol, costs, read_chars, read_offsets, slots, text, sequence_ends, alphabet, band_pad, max_drift, min_score,
+                              mapq_cap, threads, outputs, num_read_chars, fill, unscored_before, mapped_before):
+    """the two calls above: `symbol` with `costs`, the struct it takes"""
     chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
     t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
     o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
@@ -797,11 +870,10 @@ def score_chains_affine_host(read_chars, read_offsets, slots, text, sequence_end
     for name, counter in counters.items():
         if name in outputs:
             setattr(sout, name, counter.ctypes.data)
-    costs = scoring if isinstance(scoring, _lib.AwFmAlignScoring) else align_scoring(*scoring)
-    rc = _lib.lib().awfmScoreChainsAffine(C.byref(vin), n, shape[1], band_pad, max_drift, C.byref(costs), min_score, mapq_cap, address(t), t.size,
-                                          None if ends is None or not ends.size else ends.ctypes.data, 0 if ends is None else ends.size,
-                                          alphabet, C.byref(sout), threads)
-    _check("awfmScoreChainsAffine", rc)
+    rc = getattr(_lib.lib(), symbol)(C.byref(vin), n, shape[1], band_pad, max_drift, None if costs is None else C.byref(costs), min_score,
+                                     mapq_cap, address(t), t.size, None if ends is None or not ends.size else ends.ctypes.data,
+                                     0 if ends is None else ends.size, alphabet, C.byref(sout), threads)
+    _check(symbol, rc)
     for name, counter in counters.items():
         if name in outputs:
             result[name] = int(counter[0])
@@ -1303,6 +1375,25 @@ class GpuIndex:
                _lib.lib().awfmGpuAlignChainsAffine(self.handle, C.byref(inputs), d_slots or None, num_reads, max_candidates, band_pad, max_drift,
                                                    None if costs is None else C.byref(costs), max_ops, max_rows, C.byref(outputs),
                                                    d_scratch or None, stream or None))
+
+    # substitution matrices (include/awfm_gpu.h) --------------------------
+    def align_chains_matrix(self, inputs, d_slots, num_reads, outputs, d_scratch, max_candidates=4, band_pad=8, max_drift=15, scoring=None,
+                            max_ops=32, max_rows=4096, stream=0):
+        """awfmGpuAlignChainsMatrix: align_chains_affine with scoring a matrix_scoring(...) (None: the call's NULL); the struct may be
+        changed as soon as the call returns; d_scratch is align_chains_affine_scratch_bytes(max_rows) bytes"""
+        _check("awfmGpuAlignChainsMatrix",
+               _lib.lib().awfmGpuAlignChainsMatrix(self.handle, C.byref(inputs), d_slots or None, num_reads, max_candidates, band_pad, max_drift,
+                                                   None if scoring is None else C.byref(scoring), max_ops, max_rows, C.byref(outputs),
+                                                   d_scratch or None, stream or None))
+
+    def score_chains_matrix(self, inputs, num_reads, outputs, max_candidates=4, band_pad=8, max_drift=15, scoring=None, min_score=0,
+                            mapq_cap=60, stream=0):
+        """awfmGpuScoreChainsMatrix: score_chains_affine with scoring a matrix_scoring(...) (None: the call's NULL); the struct may be
+        changed as soon as the call returns; one launch, no scratch"""
+        _check("awfmGpuScoreChainsMatrix",
+               _lib.lib().awfmGpuScoreChainsMatrix(self.handle, C.byref(inputs), num_reads, max_candidates, band_pad, max_drift,
+                                                   None if scoring is None else C.byref(scoring), min_score, mapq_cap, C.byref(outputs),
+                                                   stream or None))
 
     # alignment strings (include/awfm_gpu.h) ------------------------------
     def alignment_strings_scratch_bytes(self, num_reads):

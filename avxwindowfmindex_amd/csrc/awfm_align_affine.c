@@ -169,17 +169,19 @@ static void awfmAffineRange(void *p, uint64_t begin, uint64_t end, unsigned tid)
   c->truncated[tid & 63u] += truncated;
 }
 
-enum AwFmReturnCode awfmAlignChainsAffine(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
-                                          uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
-                                          const struct AwFmAlignScoring *scoring, uint32_t maxOps, const uint8_t *text, uint64_t length,
-                                          const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
-                                          const struct AwFmAffineOutputs *out, unsigned threads) {
+/* the call behind both entry points; scoring or matrix is given, the other is NULL */
+static enum AwFmReturnCode awfmAlignChainsScored(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
+                                                 uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                                 const struct AwFmAlignScoring *scoring, const struct AwFmMatrixScoring *matrix,
+                                                 uint32_t maxOps, const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds,
+                                                 uint64_t numRecords, enum AwFmAlphabetType alphabet, const struct AwFmAffineOutputs *out,
+                                                 unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
-  const enum AwFmReturnCode rc =
-      awfmBandCheckArguments(in, out && slots && scoring, text, length, sequenceEnds, numRecords, numReads, maxCandidates, bandPad, maxDrift);
+  const enum AwFmReturnCode rc = awfmBandCheckArguments(in, out && slots && (scoring || matrix), text, length, sequenceEnds, numRecords,
+                                                        numReads, maxCandidates, bandPad, maxDrift);
   if (rc != AwFmSuccess) return rc;
   if (maxOps < 1 || maxOps > AWFM_ALIGN_MAX_OPS) return AwFmIllegalPositionError;
-  if (!awfmScoringOk(scoring)) return AwFmIllegalPositionError;
+  if (!(matrix ? awfmMatrixScoringOk(matrix) : awfmScoringOk(scoring))) return AwFmIllegalPositionError;
   struct awfmAffineCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.in = in;
@@ -193,7 +195,7 @@ enum AwFmReturnCode awfmAlignChainsAffine(const struct AwFmVerifyInputs *in, con
   ctx.pad = bandPad;
   ctx.drift = maxDrift;
   ctx.maxOps = maxOps;
-  ctx.costs = awfmAffineCostsOf(scoring, alphabet);
+  ctx.costs = matrix ? awfmMatrixCostsOf(matrix, alphabet) : awfmAffineCostsOf(scoring, alphabet);
   awfmParallelFor(threads ? threads : 1, numReads, awfmAffineRange, &ctx);
   if (ctx.failed) return AwFmAllocationFailure;
   uint64_t unaligned = 0, truncated = 0;
@@ -204,4 +206,23 @@ enum AwFmReturnCode awfmAlignChainsAffine(const struct AwFmVerifyInputs *in, con
   if (out->numUnaligned) *out->numUnaligned += unaligned;
   if (out->numTruncated) *out->numTruncated += truncated;
   return AwFmSuccess;
+}
+
+enum AwFmReturnCode awfmAlignChainsAffine(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
+                                          uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                          const struct AwFmAlignScoring *scoring, uint32_t maxOps, const uint8_t *text, uint64_t length,
+                                          const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
+                                          const struct AwFmAffineOutputs *out, unsigned threads) {
+  return awfmAlignChainsScored(in, slots, numReads, maxCandidates, bandPad, maxDrift, scoring, NULL, maxOps, text, length, sequenceEnds,
+                               numRecords, alphabet, out, threads);
+}
+
+/* "substitution matrices" (include/awfm_gpu.h): the same call with s from the matrix */
+enum AwFmReturnCode awfmAlignChainsMatrix(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
+                                          uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                          const struct AwFmMatrixScoring *scoring, uint32_t maxOps, const uint8_t *text, uint64_t length,
+                                          const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
+                                          const struct AwFmAffineOutputs *out, unsigned threads) {
+  return awfmAlignChainsScored(in, slots, numReads, maxCandidates, bandPad, maxDrift, NULL, scoring, maxOps, text, length, sequenceEnds,
+                               numRecords, alphabet, out, threads);
 }

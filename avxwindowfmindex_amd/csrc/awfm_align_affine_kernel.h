@@ -103,10 +103,11 @@ struct AffineRuns {
   }
 };
 
-/* the status of read r (header: UNUSED .. TOO LONG) or its score; every lane of the group returns the same */
-template <int G>
-__device__ __forceinline__ unsigned alignReadAffine(const DevAffineParams &p, const unsigned long long r, unsigned *sRead, unsigned *sText,
-                                                    const unsigned char *sAmino, unsigned char *trace, const unsigned k,
+/* the status of read r (header: UNUSED .. TOO LONG) or its score; every lane of the group returns the same.  scorer: the
+ * diagonal's, IdentityScore or MatrixScore (awfm_band_kernel.h); '=' and 'X' go by verification's sub under either */
+template <int G, typename S>
+__device__ __forceinline__ unsigned alignReadAffine(const DevAffineParams &p, const S &scorer, const unsigned long long r, unsigned *sRead,
+                                                    unsigned *sText, const unsigned char *sAmino, unsigned char *trace, const unsigned k,
                                                     const unsigned groupShift, DevAffineAlignment &a) {
   const unsigned j = p.chosen[r];
   if (j == AWFM_CHAINS_NO_SLOT) return AWFM_VERIFY_NONE;
@@ -134,8 +135,9 @@ __device__ __forceinline__ unsigned alignReadAffine(const DevAffineParams &p, co
     for (int q = 0; q < rows; q++) {
       const int u = i0 + q + 1 + (int)k;
       const bool inMatrix = inBand && u >= uMin && u <= uMax;
-      const bool sub = stagedSub(chunk, band, sRead, sText, sAmino, p.amino, q, u, inMatrix);
-      const AffineCell c = affineRow<G>(p, prevH, prevF, sub, inMatrix, kExtend, k);
+      const StagedLetters letters = stagedLetters(chunk, band, sRead, sText, sAmino, p.amino, q, u, inMatrix);
+      const bool sub = lettersSub(letters, p.amino);
+      const AffineCell c = affineRow<G>(p, prevH, prevF, scorer(p, letters, sub), inMatrix, kExtend, k);
       int leftH = __shfl_up(c.h, 1, G);
       leftH = k == 0u ? kBandNeg : leftH;
       const unsigned source = !inMatrix || c.h == 0 ? 0u : c.M == c.h ? (sub ? 2u : 1u) : c.F == c.h ? 3u : 4u;
@@ -208,12 +210,9 @@ __device__ __forceinline__ unsigned alignReadAffine(const DevAffineParams &p, co
   return score;
 }
 
-template <int G>
-__global__ void __launch_bounds__(kAffineThreads, 4) alignChainsAffineKernel(const DevAffineParams args) {
-  constexpr unsigned kGroupsPerWave = 64u / (unsigned)G;
-  /* the arguments live in vector registers, as in alignChainsKernel: the addresses, the nested loops' masks and five ballots a
-   * row are more scalar registers than a wave has, and the compiler would spill some of them into lanes of a vector register */
-  DevAffineParams p = args;
+/* the arguments live in vector registers, as in alignChainsKernel: the addresses, the nested loops' masks and five ballots a
+ * row are more scalar registers than a wave has, and the compiler would spill some of them into lanes of a vector register */
+__device__ __forceinline__ void pinAffineParams(DevAffineParams &p) {
   asm volatile("" : "+v"(p.in.sequences), "+v"(p.in.chainAnchors), "+v"(p.in.chainReadBegins), "+v"(p.in.chainReadEnds));
   asm volatile("" : "+v"(p.in.chainBeginDiagonals), "+v"(p.in.chainEndDiagonals), "+v"(p.out.scores), "+v"(p.out.editDistances));
   asm volatile("" : "+v"(p.out.readBegins), "+v"(p.out.readEnds), "+v"(p.out.textBegins), "+v"(p.out.textEnds));
@@ -221,12 +220,15 @@ __global__ void __launch_bounds__(kAffineThreads, 4) alignChainsAffineKernel(con
   asm volatile("" : "+v"(p.in.readChars), "+v"(p.in.numReadChars), "+v"(p.text), "+v"(p.ends));
   asm volatile("" : "+v"(p.length), "+v"(p.out.numUnaligned), "+v"(p.out.numTruncated), "+v"(p.numReads));
   asm volatile("" : "+v"(p.numRecords), "+v"(p.slots), "+v"(p.pad), "+v"(p.drift), "+v"(p.maxOps), "+v"(p.maxRows));
-  __shared__ unsigned sStage[kAffineThreads / (unsigned)G][kVerifyGroupWords];
-  __shared__ unsigned char sAmino[32];
-  if (threadIdx.x < 32u) sAmino[threadIdx.x] = kAminoTables.letterOfAscii[threadIdx.x];
-  __syncthreads();
+}
+
+/* the reads of the grid's groups, behind the workgroup's __syncthreads(): sStage is the staging words of its groups, kAffineThreads /
+ * G times kVerifyGroupWords */
+template <int G, typename S>
+__device__ __forceinline__ void alignChainsAffineReads(const DevAffineParams &p, const S &score, unsigned *sStage, const unsigned char *sAmino) {
+  constexpr unsigned kGroupsPerWave = 64u / (unsigned)G;
   const unsigned lane = threadIdx.x & 63u, k = lane % (unsigned)G, groupInWave = lane / (unsigned)G;
-  unsigned *sRead = sStage[threadIdx.x / (unsigned)G], *sText = sRead + kVerifyReadWords;
+  unsigned *sRead = sStage + (threadIdx.x / (unsigned)G) * kVerifyGroupWords, *sText = sRead + kVerifyReadWords;
   const unsigned long long wave = (unsigned long long)blockIdx.x * (kAffineThreads / 64u) + threadIdx.x / 64u;
   const unsigned long long numGroups = (unsigned long long)gridDim.x * (kAffineThreads / 64u) * kGroupsPerWave;
   /* the wave's arena, and in it the group's rows */
@@ -235,7 +237,7 @@ __global__ void __launch_bounds__(kAffineThreads, 4) alignChainsAffineKernel(con
   unsigned unaligned = 0, truncated = 0;
   for (unsigned long long r = wave * kGroupsPerWave + groupInWave; r < p.numReads; r += numGroups) {
     DevAffineAlignment a = {0u, 0u, 0u, 0u, 0ull, 0ull};
-    const unsigned value = alignReadAffine<G>(p, r, sRead, sText, sAmino, trace, k, groupInWave * (unsigned)G, a);
+    const unsigned value = alignReadAffine<G>(p, score, r, sRead, sText, sAmino, trace, k, groupInWave * (unsigned)G, a);
     if (value >= AWFM_VERIFY_TOO_LONG) {
       unaligned += value != AWFM_VERIFY_NONE && k == 0u ? 1u : 0u;
     } else {
@@ -259,6 +261,74 @@ __global__ void __launch_bounds__(kAffineThreads, 4) alignChainsAffineKernel(con
   }
   if (lane == 0u && unaligned && p.out.numUnaligned) atomicAdd((unsigned long long *)p.out.numUnaligned, (unsigned long long)unaligned);
   if (lane == 0u && truncated && p.out.numTruncated) atomicAdd((unsigned long long *)p.out.numTruncated, (unsigned long long)truncated);
+}
+
+template <int G>
+__global__ void __launch_bounds__(kAffineThreads, 4) alignChainsAffineKernel(const DevAffineParams args) {
+  DevAffineParams p = args;
+  pinAffineParams(p);
+  __shared__ unsigned sStage[kAffineThreads / (unsigned)G][kVerifyGroupWords];
+  __shared__ unsigned char sAmino[32];
+  if (threadIdx.x < 32u) sAmino[threadIdx.x] = kAminoTables.letterOfAscii[threadIdx.x];
+  __syncthreads();
+  alignChainsAffineReads<G>(p, IdentityScore(), &sStage[0][0], sAmino);
+}
+
+/* ---- the launcher (host side), shared with awfm_gpu_align_matrix.hip ---- */
+
+/* the waves of the persistent grid: the launch and the arena's size come from this one number */
+inline uint64_t affineGridWaves(const AwFmGpuIndex *g) { return (uint64_t)g->numCUs * kAffineBlocksPerCU * (kAffineThreads / 64u); }
+
+/* The argument checks of awfmGpuAlignChainsAffine and awfmGpuAlignChainsMatrix after "null image" and numReads == 0, in the
+ * header's order, before the device is switched or a lock taken (scoring: the call's scoring or matrix; refused: the call's
+ * own check of its ranges, run in its place in that order) */
+template <class Refused>
+inline enum AwFmReturnCode alignChainsArgumentsRefused(const char *name, const struct AwFmVerifyInputs *dIn, const uint32_t *dSlots,
+                                                       const void *scoring, Refused refused, const uint64_t numReads, const uint32_t maxCandidates,
+                                                       const uint32_t bandPad, const uint32_t maxDrift, const uint32_t maxOps,
+                                                       const uint32_t maxRows, const struct AwFmAffineOutputs *dOut, const void *dScratch) {
+  const uint64_t band = (uint64_t)maxDrift + 2ull * bandPad + 1ull;
+  enum AwFmReturnCode rc = chainArgumentsRefused(name, dIn, dOut && dSlots && dScratch && scoring, numReads, maxCandidates, band);
+  if (rc != AwFmSuccess) return rc;
+  if (maxOps < 1 || maxOps > AWFM_ALIGN_MAX_OPS || maxRows < 1 || maxRows > AWFM_ALIGN_MAX_LENGTH) {
+    setCallError(name, "maxOps is 1 to 4096 and maxRows 1 to 65536");
+    return AwFmIllegalPositionError;
+  }
+  if ((rc = refused()) != AwFmSuccess) return rc;
+  if ((uintptr_t)dScratch & 15u) {
+    setCallError(name, "the scratch is aligned to 16 bytes");
+    return AwFmIllegalPositionError;
+  }
+  return AwFmSuccess;
+}
+
+/* The parameters of either call but for the costs, the lanes per group and the grid.  The caller holds image->recordMutex from
+ * before this call until after the launch and has seen that the image has a text */
+inline void alignChainsParams(const AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, const uint32_t *dSlots, const uint64_t numReads,
+                              const uint32_t maxCandidates, const uint32_t bandPad, const uint32_t maxDrift, const uint32_t maxOps,
+                              const uint32_t maxRows, const struct AwFmAffineOutputs *dOut, void *dScratch, DevAffineParams &p, unsigned &group,
+                              dim3 &grid) {
+  const AwFmGpuImage *image = g->image;
+  p.in = *dIn;
+  p.out = *dOut;
+  p.chosen = dSlots;
+  p.text = (const unsigned char *)image->dText;
+  p.length = image->textLength;
+  p.ends = image->records.ends;
+  p.numRecords = image->records.numRecords;
+  p.numReads = numReads;
+  p.arena = (unsigned char *)dScratch;
+  p.slots = maxCandidates;
+  p.pad = bandPad;
+  p.drift = maxDrift;
+  p.amino = g->amino ? 1u : 0u;
+  p.maxOps = maxOps;
+  p.maxRows = maxRows;
+  group = bandGroup((uint64_t)maxDrift + 2ull * bandPad + 1ull, "affine_group");
+  /* persistent grid over reads, a group each: never more waves than the arena has room for */
+  const uint64_t perBlock = (uint64_t)(kAffineThreads / group), blocks = (numReads + perBlock - 1u) / perBlock;
+  const uint64_t resident = affineGridWaves(g) / (kAffineThreads / 64u);
+  grid = dim3((unsigned)(blocks < resident ? blocks : resident));
 }
 
 }  // namespace

@@ -1,13 +1,15 @@
 /*
  * awfm_band.h -- what the host twins of the read path share (awfm_verify.c, awfm_align.c, awfm_align_affine.c, awfm_score_affine.c,
  * awfm_window_affine.c): the letter comparison, the arithmetic on "minus infinity", a record's bounds, the classification of a
- * chain slot up to TOO WIDE, the argument checks of the entry points and the rows of the banded affine recurrence.  The device's
+ * chain slot up to TOO WIDE, the argument checks of the entry points and the rows of the banded affine recurrence, whose diagonal
+ * scores by two costs or by a substitution matrix.  The device's
  * definitions of the same things are awfm_band_kernel.h.  Plain C11, static inline and header-only on purpose: a twin is also
  * compiled on its own, by naming its source files.  Exact and readable rather than fast.
  */
 #ifndef AWFM_BAND_H
 #define AWFM_BAND_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "awfm_gpu.h"
@@ -90,16 +92,42 @@ static inline int awfmScoringOk(const struct AwFmAlignScoring *scoring) {
            scoring->gapExtend > 255);
 }
 
-/* the costs of the affine recurrence as the scoring struct gives them, and the alphabet of the comparison */
+/* the class of a character in a substitution matrix (include/awfm_gpu.h, "substitution matrices"): the letter's index, every
+ * byte that is no proper letter -- the sentinel included -- in the last class, 20 or 4 */
+static inline uint32_t awfmMatrixClass(int amino, uint8_t c) {
+  const uint32_t x = amino ? awfmAminoAsciiToIndex(c) : awfmNucAsciiToIndex(c), other = amino ? 20u : 4u;
+  return x < other ? x : other;
+}
+
+/* the costs of the affine recurrence as the scoring struct gives them, and the alphabet of the comparison; matrix: NULL, or the
+ * AWFM_MATRIX_CLASSES x AWFM_MATRIX_CLASSES substitution scores that take the place of match and mismatch */
 struct awfmAffineCosts {
   int32_t match, mismatch, open, extend;
   int amino;
+  const int8_t *matrix;
 };
 
 static inline struct awfmAffineCosts awfmAffineCostsOf(const struct AwFmAlignScoring *scoring, enum AwFmAlphabetType alphabet) {
   const struct awfmAffineCosts c = {(int32_t)scoring->match, (int32_t)scoring->mismatch, (int32_t)scoring->gapOpen, (int32_t)scoring->gapExtend,
-                                    alphabet == AwFmAlphabetAmino};
+                                    alphabet == AwFmAlphabetAmino, NULL};
   return c;
+}
+
+/* gapOpen 0 to 255, gapExtend 1 to 255; every substitution value is legal */
+static inline int awfmMatrixScoringOk(const struct AwFmMatrixScoring *scoring) {
+  return !(scoring->gapOpen > 255 || scoring->gapExtend < 1 || scoring->gapExtend > 255);
+}
+
+static inline struct awfmAffineCosts awfmMatrixCostsOf(const struct AwFmMatrixScoring *scoring, enum AwFmAlphabetType alphabet) {
+  const struct awfmAffineCosts c = {0, 0, (int32_t)scoring->gapOpen, (int32_t)scoring->gapExtend, alphabet == AwFmAlphabetAmino,
+                                    scoring->substitution};
+  return c;
+}
+
+/* s(a, b) of the recurrence, a of the read and b of the text: the one place the diagonal's score comes from.  sub: verification's */
+static inline int32_t awfmAffineDiagonal(const struct awfmAffineCosts *c, uint32_t sub, uint8_t a, uint8_t b) {
+  if (c->matrix) return c->matrix[awfmMatrixClass(c->amino, a) * AWFM_MATRIX_CLASSES + awfmMatrixClass(c->amino, b)];
+  return sub ? -c->mismatch : c->match;
 }
 
 /* a trace byte: the source of H in its low three bits, then whether F and E of the cell open their gap at its neighbour */
@@ -138,7 +166,7 @@ static inline struct awfmAffineEnd awfmAffineRows(const struct awfmAffineCosts *
       if (t >= 0 && t <= L) {
         /* (i-1, t-1) lies on the same diagonal, (i-1, t) on the next one up, (i, t-1) on the one below */
         const uint32_t sub = t >= 1 ? awfmBandSub(c->amino, R[i - 1], T[t - 1]) : 1u;
-        const int32_t M = t >= 1 ? awfmBandMinus(prevH[k], sub ? c->mismatch : -c->match) : AWFM_BAND_NEG;
+        const int32_t M = t >= 1 ? awfmBandMinus(prevH[k], -awfmAffineDiagonal(c, sub, R[i - 1], T[t - 1])) : AWFM_BAND_NEG;
         const int32_t fOpens = awfmBandMinus(k + 1 < width ? prevH[k + 1] : AWFM_BAND_NEG, open);
         const int32_t fExtends = awfmBandMinus(k + 1 < width ? prevF[k + 1] : AWFM_BAND_NEG, extend);
         const int32_t eOpens = awfmBandMinus(k >= 1 ? curH[k - 1] : AWFM_BAND_NEG, open);

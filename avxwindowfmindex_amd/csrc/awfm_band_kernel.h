@@ -1,8 +1,9 @@
 /*
  * awfm_band_kernel.h -- what the kernels of the read path share (awfm_verify_kernel.h, awfm_align_kernel.h,
- * awfm_align_affine_kernel.h, awfm_score_affine_kernel.h; awfm_window_affine_kernel.h takes the letters): a group's staging of
+ * awfm_align_affine_kernel.h, awfm_score_affine_kernel.h, awfm_matrix_kernel.h; awfm_window_affine_kernel.h takes the letters): a group's staging of
  * read and text bytes into LDS, the letter comparison, the classification of a chain slot up to TOO WIDE, the band of a whole
- * read and the staging of one of its chunks, the row and the end cell of the banded affine recurrence -- and what their
+ * read and the staging of one of its chunks, the row and the end cell of the banded affine recurrence, the two sources of the
+ * diagonal's score (two costs, or a substitution matrix in LDS) -- and what their
  * launchers share: the argument checks with their messages, the choice of the lanes per group and the dispatch over it.  The
  * host's definitions of the same things are awfm_band.h.
  *
@@ -124,14 +125,62 @@ __device__ __forceinline__ StagedChunk stageChunk(const unsigned char *R, const 
   return c;
 }
 
-/* whether row q of the chunk and column u differ: true unless both characters map to the same proper letter, and for a cell
- * without a diagonal predecessor */
+/* the letters of row q of the chunk and of column u; the text's is 0xFF for a cell without a diagonal predecessor */
+struct StagedLetters {
+  unsigned read, text;
+};
+
+__device__ __forceinline__ StagedLetters stagedLetters(const StagedChunk &c, const ReadBand &band, const unsigned *sRead, const unsigned *sText,
+                                                       const unsigned char *sAmino, const unsigned amino, const int q, const int u,
+                                                       const bool inMatrix) {
+  StagedLetters l;
+  l.read = verifyLetter(sAmino, amino, ((const unsigned char *)sRead)[c.rOff + (unsigned)q]);
+  l.text = 0xFFu;
+  if (inMatrix && u >= band.uOne) l.text = verifyLetter(sAmino, amino, ((const unsigned char *)sText)[c.tOff + (unsigned)(u - 1 - c.uFrom)]);
+  return l;
+}
+
+/* whether they differ: true unless both characters map to the same proper letter, and for a cell without a diagonal predecessor */
+__device__ __forceinline__ bool lettersSub(const StagedLetters &l, const unsigned amino) {
+  return !(l.read == l.text && l.read < (amino ? 20u : 4u));
+}
+
 __device__ __forceinline__ bool stagedSub(const StagedChunk &c, const ReadBand &band, const unsigned *sRead, const unsigned *sText,
                                           const unsigned char *sAmino, const unsigned amino, const int q, const int u, const bool inMatrix) {
-  const unsigned rLetter = verifyLetter(sAmino, amino, ((const unsigned char *)sRead)[c.rOff + (unsigned)q]);
-  unsigned tLetter = 0xFFu;
-  if (inMatrix && u >= band.uOne) tLetter = verifyLetter(sAmino, amino, ((const unsigned char *)sText)[c.tOff + (unsigned)(u - 1 - c.uFrom)]);
-  return !(rLetter == tLetter && rLetter < (amino ? 20u : 4u));
+  return lettersSub(stagedLetters(c, band, sRead, sText, sAmino, amino, q, u, inMatrix), amino);
+}
+
+/* The diagonal's score s(R[i-1], T[t-1]) of a cell, from its two letters and verification's sub: what affineRow adds to the
+ * previous row's H.  IdentityScore is "affine alignment"'s, + match or - mismatch out of the launch's parameters */
+struct IdentityScore {
+  template <typename P>
+  __device__ __forceinline__ int operator()(const P &p, const StagedLetters &, const bool sub) const {
+    return sub ? -p.mismatch : p.match;
+  }
+};
+
+/* MatrixScore is "substitution matrices"' (include/awfm_gpu.h): a signed byte out of the workgroup's copy of the launch's matrix in
+ * LDS, rows kMatrixStride bytes apart so that a row lies inside 32 bytes -- eight banks.  The class of a letter is the letter
+ * capped at `other` (20 or 4): the sentinel, every ambiguity code and the 0xFF of a cell without a diagonal predecessor (whose
+ * score meets kBandNeg and counts for nothing) fold into the last class.  The row index is uniform over a group in a row */
+constexpr unsigned kMatrixStride = 32;
+constexpr unsigned kMatrixLdsBytes = AWFM_MATRIX_CLASSES * kMatrixStride;
+
+struct MatrixScore {
+  const signed char *sMatrix;
+  unsigned other;
+  template <typename P>
+  __device__ __forceinline__ int operator()(const P &, const StagedLetters &l, const bool) const {
+    const unsigned r = l.read < other ? l.read : other, t = l.text < other ? l.text : other;
+    return (int)sMatrix[r * kMatrixStride + t];
+  }
+};
+
+/* the workgroup's copy of a launch's matrix: `matrix` is the struct's array in the kernel's argument segment; the caller's
+ * __syncthreads() follows */
+__device__ __forceinline__ void stageMatrix(const __attribute__((address_space(4))) signed char *matrix, signed char *sMatrix) {
+  for (unsigned at = threadIdx.x; at < AWFM_MATRIX_CLASSES * AWFM_MATRIX_CLASSES; at += blockDim.x)
+    sMatrix[(at / AWFM_MATRIX_CLASSES) * kMatrixStride + at % AWFM_MATRIX_CLASSES] = matrix[at];
 }
 
 /* lane k's cell of a row of "affine alignment" */
@@ -143,15 +192,18 @@ struct AffineCell {
  * exclusive max-prefix-scan per row over the group: E[k] = max over k' < k of (H~[k'] + k' e) - o - k e with H~ = max(0, M, F)
  * -- a gap that extends from a cell whose H came from E pays o twice and is dominated, so the scan's E is the
  * recurrence's.  Lanes and rows without a cell carry kBandNeg and need no other case: max(0, ...) is taken for existing cells
- * only.  p.open is what the first character of a gap costs, o + e; kExtend is k * p.extend */
+ * only.  p.open is what the first character of a gap costs, o + e; kExtend is k * p.extend; s is the diagonal's score, of
+ * IdentityScore or MatrixScore, -128 <= s <= 255.  Neither the scan nor its dominance argument involves s.  kBandNeg survives a
+ * row whatever s is: a lane resets it every row, and between two resets it takes one s, o + e and twice 63 e, at most 255 +
+ * 510 + 2 * 63 * 255 < 2^16 either way, against 2^30 */
 template <int G, typename P>
-__device__ __forceinline__ AffineCell affineRow(const P &p, const int prevH, const int prevF, const bool sub, const bool inMatrix, const int kExtend,
+__device__ __forceinline__ AffineCell affineRow(const P &p, const int prevH, const int prevF, const int s, const bool inMatrix, const int kExtend,
                                                 const unsigned k) {
   AffineCell c;
   int upH = __shfl_down(prevH, 1, G), upF = __shfl_down(prevF, 1, G);
   upH = k == (unsigned)(G - 1) ? kBandNeg : upH;
   upF = k == (unsigned)(G - 1) ? kBandNeg : upF;
-  c.M = prevH + (sub ? -p.mismatch : p.match); /* (prevH is kBandNeg when t = 0) */
+  c.M = prevH + s; /* (prevH is kBandNeg when t = 0) */
   c.fOpens = upH - p.open;
   c.fExtends = upF - p.extend;
   c.F = c.fOpens > c.fExtends ? c.fOpens : c.fExtends;
@@ -219,6 +271,14 @@ inline enum AwFmReturnCode scoringRefused(const char *name, const struct AwFmAli
   if (scoring->match < 1 || scoring->match > 255 || scoring->mismatch > 255 || scoring->gapOpen > 255 || scoring->gapExtend < 1 ||
       scoring->gapExtend > 255) {
     setCallError(name, "match and gapExtend are 1 to 255, mismatch and gapOpen 0 to 255");
+    return AwFmIllegalPositionError;
+  }
+  return AwFmSuccess;
+}
+
+inline enum AwFmReturnCode matrixScoringRefused(const char *name, const struct AwFmMatrixScoring *scoring) {
+  if (scoring->gapOpen > 255 || scoring->gapExtend < 1 || scoring->gapExtend > 255) {
+    setCallError(name, "gapOpen is 0 to 255 and gapExtend 1 to 255");
     return AwFmIllegalPositionError;
   }
   return AwFmSuccess;

@@ -10,9 +10,6 @@
 
 #include "awfm_align_affine_kernel.h"
 
-/* the waves of the persistent grid: the launch and the arena's size come from this one number */
-static uint64_t affineGridWaves(const AwFmGpuIndex *g) { return (uint64_t)g->numCUs * kAffineBlocksPerCU * (kAffineThreads / 64u); }
-
 extern "C" {
 
 uint64_t awfmGpuAlignChainsAffineScratchBytes(const AwFmGpuIndex *g, uint32_t maxRows) {
@@ -30,47 +27,23 @@ enum AwFmReturnCode awfmGpuAlignChainsAffine(AwFmGpuIndex *g, const struct AwFmV
   }
   if (numReads == 0) return AwFmSuccess;
   const char *name = "awfmGpuAlignChainsAffine";
-  const uint64_t band = (uint64_t)maxDrift + 2ull * bandPad + 1ull;
-  enum AwFmReturnCode rc = chainArgumentsRefused(name, dIn, dOut && dSlots && dScratch && scoring, numReads, maxCandidates, band);
+  enum AwFmReturnCode rc = alignChainsArgumentsRefused(
+      name, dIn, dSlots, scoring, [&] { return scoringRefused(name, scoring); }, numReads, maxCandidates, bandPad, maxDrift, maxOps, maxRows, dOut,
+      dScratch);
   if (rc != AwFmSuccess) return rc;
-  if (maxOps < 1 || maxOps > AWFM_ALIGN_MAX_OPS || maxRows < 1 || maxRows > AWFM_ALIGN_MAX_LENGTH) {
-    setCallError(name, "maxOps is 1 to 4096 and maxRows 1 to 65536");
-    return AwFmIllegalPositionError;
-  }
-  if ((rc = scoringRefused(name, scoring)) != AwFmSuccess) return rc;
-  if ((uintptr_t)dScratch & 15u) {
-    setCallError(name, "the scratch is aligned to 16 bytes");
-    return AwFmIllegalPositionError;
-  }
   DeviceGuard guard(g->device);
   AwFmGpuImage *image = g->image;
   std::shared_lock<std::shared_mutex> lock(image->recordMutex); /* neither text nor record table is replaced before the launch */
   if ((rc = textMissing(name, image)) != AwFmSuccess) return rc;
   DevAffineParams p{};
-  p.in = *dIn;
-  p.out = *dOut;
-  p.chosen = dSlots;
-  p.text = (const unsigned char *)image->dText;
-  p.length = image->textLength;
-  p.ends = image->records.ends;
-  p.numRecords = image->records.numRecords;
-  p.numReads = numReads;
-  p.arena = (unsigned char *)dScratch;
-  p.slots = maxCandidates;
-  p.pad = bandPad;
-  p.drift = maxDrift;
-  p.amino = g->amino ? 1u : 0u;
-  p.maxOps = maxOps;
-  p.maxRows = maxRows;
+  unsigned group;
+  dim3 grid;
+  const dim3 block(kAffineThreads);
+  alignChainsParams(g, dIn, dSlots, numReads, maxCandidates, bandPad, maxDrift, maxOps, maxRows, dOut, dScratch, p, group, grid);
   p.match = (int)scoring->match;
   p.mismatch = (int)scoring->mismatch;
   p.open = (int)(scoring->gapOpen + scoring->gapExtend);
   p.extend = (int)scoring->gapExtend;
-  const unsigned group = bandGroup(band, "affine_group");
-  /* persistent grid over reads, a group each: never more waves than the arena has room for */
-  const uint64_t perBlock = (uint64_t)(kAffineThreads / group), blocks = (numReads + perBlock - 1u) / perBlock;
-  const uint64_t resident = affineGridWaves(g) / (kAffineThreads / 64u);
-  const dim3 grid((unsigned)(blocks < resident ? blocks : resident)), block(kAffineThreads);
   AWFM_LAUNCH_BAND_KERNEL(alignChainsAffineKernel, group, grid, block, stream, p);
   AWFM_HIP_TRY(hipGetLastError(), AwFmGeneralFailure);
   return AwFmSuccess;

@@ -100,16 +100,18 @@ static void awfmScoreRange(void *p, uint64_t begin, uint64_t end, unsigned tid) 
   c->mapped[tid & 63u] += mapped;
 }
 
-enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
-                                          uint32_t maxDrift, const struct AwFmAlignScoring *scoring, uint32_t minScore, uint32_t mapqCap,
-                                          const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
-                                          enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads) {
+/* the call behind both entry points; scoring or matrix is given, the other is NULL */
+static enum AwFmReturnCode awfmScoreChainsScored(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
+                                                 uint32_t maxDrift, const struct AwFmAlignScoring *scoring,
+                                                 const struct AwFmMatrixScoring *matrix, uint32_t minScore, uint32_t mapqCap,
+                                                 const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
+                                                 enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
-  const enum AwFmReturnCode rc =
-      awfmBandCheckArguments(in, out && scoring, text, length, sequenceEnds, numRecords, numReads, maxCandidates, bandPad, maxDrift);
+  const enum AwFmReturnCode rc = awfmBandCheckArguments(in, out && (scoring || matrix), text, length, sequenceEnds, numRecords, numReads,
+                                                        maxCandidates, bandPad, maxDrift);
   if (rc != AwFmSuccess) return rc;
   if (mapqCap > AWFM_SCORE_MAX_MAPQ) return AwFmIllegalPositionError;
-  if (!awfmScoringOk(scoring)) return AwFmIllegalPositionError;
+  if (!(matrix ? awfmMatrixScoringOk(matrix) : awfmScoringOk(scoring))) return AwFmIllegalPositionError;
   struct awfmScoreCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.in = in;
@@ -123,7 +125,7 @@ enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uin
   ctx.drift = maxDrift;
   ctx.minScore = minScore;
   ctx.cap = mapqCap;
-  ctx.costs = awfmAffineCostsOf(scoring, alphabet);
+  ctx.costs = matrix ? awfmMatrixCostsOf(matrix, alphabet) : awfmAffineCostsOf(scoring, alphabet);
   awfmParallelFor(threads ? threads : 1, numReads, awfmScoreRange, &ctx);
   uint64_t unscored = 0, mapped = 0;
   for (unsigned t = 0; t < 64; t++) {
@@ -133,4 +135,21 @@ enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uin
   if (out->numUnscored) *out->numUnscored += unscored;
   if (out->numMapped) *out->numMapped += mapped;
   return AwFmSuccess;
+}
+
+enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
+                                          uint32_t maxDrift, const struct AwFmAlignScoring *scoring, uint32_t minScore, uint32_t mapqCap,
+                                          const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
+                                          enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads) {
+  return awfmScoreChainsScored(in, numReads, maxCandidates, bandPad, maxDrift, scoring, NULL, minScore, mapqCap, text, length, sequenceEnds,
+                               numRecords, alphabet, out, threads);
+}
+
+/* "substitution matrices" (include/awfm_gpu.h): the same call with s from the matrix */
+enum AwFmReturnCode awfmScoreChainsMatrix(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
+                                          uint32_t maxDrift, const struct AwFmMatrixScoring *scoring, uint32_t minScore, uint32_t mapqCap,
+                                          const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
+                                          enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads) {
+  return awfmScoreChainsScored(in, numReads, maxCandidates, bandPad, maxDrift, NULL, scoring, minScore, mapqCap, text, length, sequenceEnds,
+                               numRecords, alphabet, out, threads);
 }

@@ -50,9 +50,10 @@ struct DevScoreParams {
 typedef const __attribute__((address_space(4))) DevScoreParams *ScoreParamsRef;
 
 /* the value of slot `at` of read r (header: UNUSED .. TOO LONG, else the score) with its end cell; every lane of the group
- * returns the same */
-template <int G>
-__device__ __forceinline__ unsigned scoreSlot(const ScoreParamsRef p, const unsigned long long at, const unsigned s,
+ * returns the same.  Ref: ScoreParamsRef, or such a pointer to a struct that begins with a DevScoreParams; score: the diagonal's,
+ * IdentityScore or MatrixScore (awfm_band_kernel.h) */
+template <int G, typename Ref, typename S>
+__device__ __forceinline__ unsigned scoreSlot(const Ref p, const S &score, const unsigned long long at, const unsigned s,
                                               const unsigned long long readBegin, const unsigned long long n64, const bool readOk,
                                               unsigned *sRead, unsigned *sText, const unsigned char *sAmino, const unsigned k,
                                               unsigned &endRead, unsigned long long &endText) {
@@ -77,7 +78,8 @@ __device__ __forceinline__ unsigned scoreSlot(const ScoreParamsRef p, const unsi
     for (int q = 0; q < rows; q++) {
       const int u = i0 + q + 1 + (int)k;
       const bool inMatrix = inBand && u >= band.uMin && u <= band.uMax;
-      const AffineCell c = affineRow<G>(*p, prevH, prevF, stagedSub(chunk, band, sRead, sText, sAmino, p->amino, q, u, inMatrix), inMatrix, kExtend, k);
+      const StagedLetters letters = stagedLetters(chunk, band, sRead, sText, sAmino, p->amino, q, u, inMatrix);
+      const AffineCell c = affineRow<G>(*p, prevH, prevF, score(*p, letters, lettersSub(letters, p->amino)), inMatrix, kExtend, k);
       if (c.h > bestH) { /* (strictly: the smallest i of the lane's largest H) */
         bestH = c.h;
         bestI = i0 + q + 1;
@@ -103,23 +105,18 @@ __device__ __forceinline__ unsigned scoreMaxOfSixteen(unsigned key) {
   return key;
 }
 
-template <int G>
-__global__ void __launch_bounds__(kScoreThreads) scoreChainsAffineKernel(const DevScoreParams args) {
+/* The reads of the grid's waves, behind the workgroup's __syncthreads(): sStage is the staging words of its groups, kScoreThreads /
+ * G times kVerifyGroupWords, sSlots the slot words of its waves.  Thirty-odd parameters, the nested loops' masks and a slot's own
+ * values are more scalar registers than a wave has, and pinned into vector registers they cost a wave its occupancy: the
+ * parameters stay in the argument segment (the struct is the kernel's only argument, so it begins the segment) and every trip
+ * of the read loop takes the address anew, so that what a field's load yields lives no longer than the trip needs it */
+template <int G, typename Ref, typename S>
+__device__ __forceinline__ void scoreChainsAffineReads(Ref p, const S &score, unsigned *sStage, unsigned *sSlots, const unsigned char *sAmino) {
   constexpr unsigned kGroupsPerWave = 64u / (unsigned)G;
-  /* thirty-odd parameters, the nested loops' masks and a slot's own values are more scalar registers than a wave has, and pinned
-   * into vector registers they cost a wave its occupancy: the parameters stay in the argument segment (the struct is the
-   * kernel's only argument, so it begins the segment) and every trip of the read loop takes the address anew, so that what a
-   * field's load yields lives no longer than the trip needs it */
-  (void)args;
-  ScoreParamsRef p = (ScoreParamsRef)__builtin_amdgcn_kernarg_segment_ptr();
-  __shared__ unsigned sStage[kScoreThreads / (unsigned)G][kVerifyGroupWords];
-  __shared__ unsigned sSlots[kScoreThreads / 64u][kScoreSlotWords];
-  __shared__ unsigned char sAmino[32];
-  if (threadIdx.x < 32u) sAmino[threadIdx.x] = kAminoTables.letterOfAscii[threadIdx.x];
-  __syncthreads();
   const unsigned lane = threadIdx.x & 63u, k = lane % (unsigned)G, groupInWave = lane / (unsigned)G;
-  unsigned *sRead = sStage[threadIdx.x / (unsigned)G], *sText = sRead + kVerifyReadWords;
-  unsigned *sValue = sSlots[threadIdx.x / 64u], *sEndRead = sValue + 16, *sEndLow = sValue + 32, *sEndHigh = sValue + 48, *sSequence = sValue + 64;
+  unsigned *sRead = sStage + (threadIdx.x / (unsigned)G) * kVerifyGroupWords, *sText = sRead + kVerifyReadWords;
+  unsigned *sValue = sSlots + (threadIdx.x / 64u) * kScoreSlotWords, *sEndRead = sValue + 16, *sEndLow = sValue + 32, *sEndHigh = sValue + 48,
+           *sSequence = sValue + 64;
   const unsigned long long numWaves = (unsigned long long)gridDim.x * (kScoreThreads / 64u);
   const unsigned long long numReads = p->numReads;
   unsigned unscored = 0, mapped = 0;
@@ -133,7 +130,7 @@ __global__ void __launch_bounds__(kScoreThreads) scoreChainsAffineKernel(const D
       const unsigned s = p->in.sequences[at];
       unsigned endRead;
       unsigned long long endText;
-      const unsigned value = scoreSlot<G>(p, at, s, readBegin, readEnd - readBegin, readOk, sRead, sText, sAmino, k, endRead, endText);
+      const unsigned value = scoreSlot<G>(p, score, at, s, readBegin, readEnd - readBegin, readOk, sRead, sText, sAmino, k, endRead, endText);
       if (k == 0u) {
         sValue[j] = value;
         sEndRead[j] = endRead;
@@ -178,6 +175,63 @@ __global__ void __launch_bounds__(kScoreThreads) scoreChainsAffineKernel(const D
   for (int offset = 32; offset > 0; offset >>= 1) unscored += (unsigned)__shfl_xor((int)unscored, offset, 64);
   if (lane == 0u && unscored && p->out.numUnscored) atomicAdd((unsigned long long *)p->out.numUnscored, (unsigned long long)unscored);
   if (lane == 0u && mapped && p->out.numMapped) atomicAdd((unsigned long long *)p->out.numMapped, (unsigned long long)mapped);
+}
+
+template <int G>
+__global__ void __launch_bounds__(kScoreThreads) scoreChainsAffineKernel(const DevScoreParams args) {
+  (void)args;
+  ScoreParamsRef p = (ScoreParamsRef)__builtin_amdgcn_kernarg_segment_ptr();
+  __shared__ unsigned sStage[kScoreThreads / (unsigned)G][kVerifyGroupWords];
+  __shared__ unsigned sSlots[kScoreThreads / 64u][kScoreSlotWords];
+  __shared__ unsigned char sAmino[32];
+  if (threadIdx.x < 32u) sAmino[threadIdx.x] = kAminoTables.letterOfAscii[threadIdx.x];
+  __syncthreads();
+  scoreChainsAffineReads<G>(p, IdentityScore(), &sStage[0][0], &sSlots[0][0], sAmino);
+}
+
+/* ---- the launcher (host side), shared with awfm_gpu_score_matrix.hip ---- */
+
+/* The argument checks of awfmGpuScoreChainsAffine and awfmGpuScoreChainsMatrix after "null image" and numReads == 0, in the
+ * header's order, before the device is switched or a lock taken (scoring: the call's scoring or matrix; refused: the call's
+ * own check of its ranges, run in its place in that order) */
+template <class Refused>
+inline enum AwFmReturnCode scoreChainsArgumentsRefused(const char *name, const struct AwFmVerifyInputs *dIn, const void *scoring, Refused refused,
+                                                       const uint64_t numReads, const uint32_t maxCandidates, const uint32_t bandPad,
+                                                       const uint32_t maxDrift, const uint32_t mapqCap, const struct AwFmSlotScoreOutputs *dOut) {
+  const uint64_t band = (uint64_t)maxDrift + 2ull * bandPad + 1ull;
+  const enum AwFmReturnCode rc = chainArgumentsRefused(name, dIn, dOut && scoring, numReads, maxCandidates, band);
+  if (rc != AwFmSuccess) return rc;
+  if (mapqCap > AWFM_SCORE_MAX_MAPQ) {
+    setCallError(name, "mapqCap is 0 to 254");
+    return AwFmIllegalPositionError;
+  }
+  return refused();
+}
+
+/* The parameters of either call but for the costs, the lanes per group and the grid.  The caller holds image->recordMutex from
+ * before this call until after the launch and has seen that the image has a text */
+inline void scoreChainsParams(const AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, const uint64_t numReads, const uint32_t maxCandidates,
+                              const uint32_t bandPad, const uint32_t maxDrift, const uint32_t minScore, const uint32_t mapqCap,
+                              const struct AwFmSlotScoreOutputs *dOut, DevScoreParams &p, unsigned &group, dim3 &grid) {
+  const AwFmGpuImage *image = g->image;
+  p.in = *dIn;
+  p.out = *dOut;
+  p.text = (const unsigned char *)image->dText;
+  p.length = image->textLength;
+  p.ends = image->records.ends;
+  p.numRecords = image->records.numRecords;
+  p.numReads = numReads;
+  p.slots = maxCandidates;
+  p.pad = bandPad;
+  p.drift = maxDrift;
+  p.amino = g->amino ? 1u : 0u;
+  p.floor = minScore > 1u ? minScore : 1u;
+  p.cap = mapqCap;
+  group = bandGroup((uint64_t)maxDrift + 2ull * bandPad + 1ull, "score_group");
+  /* persistent grid over reads, a wave each */
+  const uint64_t perBlock = kScoreThreads / 64u, blocks = (numReads + perBlock - 1u) / perBlock;
+  const uint64_t resident = (uint64_t)g->numCUs * kScoreBlocksPerCU;
+  grid = dim3((unsigned)(blocks < resident ? blocks : resident));
 }
 
 }  // namespace

@@ -85,8 +85,8 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   verify_group=16|32|64   awfmGpuVerifyChains: lanes per slot, where that is more than the band's diagonals need (a smaller
  *                       value than the band needs is ignored); the default is the smallest that holds the band
  *   align_group=16|32|64    awfmGpuAlignChains: lanes per read, in the same way
- *   affine_group=32|64      awfmGpuAlignChainsAffine: lanes per read, in the same way
- *   score_group=32|64       awfmGpuScoreChainsAffine: lanes per slot, in the same way
+ *   affine_group=32|64      awfmGpuAlignChainsAffine, awfmGpuAlignChainsMatrix: lanes per read, in the same way
+ *   score_group=32|64       awfmGpuScoreChainsAffine, awfmGpuScoreChainsMatrix: lanes per slot, in the same way
  *   window_q=4|8|12         awfmGpuScoreWindowsAffine: columns per lane for every read (narrower column blocks)
  *   pair_group=64           awfmGpuPairMates: a wave per pair also where 16 lanes hold the candidates
  *   insert_tier=global      awfmGpuInsertHistogram: global atomics at any bin count (default: a private histogram in LDS per
@@ -885,6 +885,90 @@ enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uin
 enum AwFmReturnCode awfmGpuScoreChainsAffine(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
                                              uint32_t bandPad, uint32_t maxDrift, const struct AwFmAlignScoring *scoring, uint32_t minScore,
                                              uint32_t mapqCap, const struct AwFmSlotScoreOutputs *dOut, void *stream);
+
+/* ---- substitution matrices: slot scores and affine alignment with s(a, b) from a table ----
+ * Twins of the two calls above for callers whose substitutions are not all alike: protein alignments (I/V is not W/P), or
+ * nucleotide scorings that tell N from a mismatch and transitions from transversions.  NEW CALLS ONLY: nothing above changes.
+ *
+ * struct AwFmMatrixScoring: substitution[class(read character) * AWFM_MATRIX_CLASSES + class(text character)], any int8 anywhere,
+ * not necessarily symmetric -- a positive value between two different letters, a non-positive diagonal and a positive "other x
+ * other" are all legal --, and gapOpen o 0..255, gapExtend e 1..255 as in struct AwFmAlignScoring (outside: AwFmIllegalPositionError).
+ *   CLASSES.  Amino: class(c) = min(awfmAminoAsciiToIndex(c), 20): 0..19 the twenty letters in index order (A C D E F G H I K L
+ *   M N P Q R S T V W Y, either case), 20 every other byte, the sentinel '$' included.  Nucleotide: class(c) =
+ *   min(awfmNucAsciiToIndex(c), 4): 0..3 are A C G T/U (either case), 4 every other byte, the sentinel included (whose letter index
+ *   is 5).  Entries with an index >= 5 on either side are never read for nucleotides and may hold anything.
+ *
+ * awfmScoreChainsMatrix / awfmGpuScoreChainsMatrix are awfmScoreChainsAffine / awfmGpuScoreChainsAffine, and awfmAlignChainsMatrix /
+ * awfmGpuAlignChainsMatrix are awfmAlignChainsAffine / awfmGpuAlignChainsAffine, with the matrix in place of the scoring: the same
+ * inputs, outputs (struct AwFmSlotScoreOutputs, struct AwFmAffineOutputs), per-read rules, status order, counters, NULL rules
+ * (scoring == NULL: AwFmNullPtrError, where the sibling reports it), order of the argument checks, maxOps, maxRows, and dScratch
+ * of awfmGpuAlignChainsAffineScratchBytes(g, maxRows) bytes with the same five trace bits per cell; the score call is one launch
+ * without scratch, host wait or allocation.  awfmGpuAlignmentStrings takes the alignment's outputs unchanged.  The DEFINITION is
+ * "affine alignment"'s word for word, except:
+ *   s(R[i-1], T[t-1]) = substitution[class(R[i-1]) * 21 + class(T[t-1])];
+ *   '=' and 'X', in the trace and in the script, stay BY IDENTITY: '=' exactly when verification's sub is 0 (both characters map
+ *   to the same proper letter).  An 'X' may therefore carry a positive score and an '=' a negative one; editDistance counts X +
+ *   I + D characters as before;
+ *   bounds: H <= 2^16 * 127 < 2^24, so the end cell's key and the 32-bit arithmetic hold as they are.  The device's stand-in for
+ *   minus infinity, -2^30, is reset by its lane every row; between two resets it takes one s (at most +127 or -128), one o + e
+ *   and twice 63 e, less than 2^16 in either direction, so it neither reaches the real values (>= -2^16 below 0 at most) nor
+ *   wraps;
+ *   INVARIANTS: the runs' read lengths sum to n, their text lengths to textEnd - textBegin; the script re-scored from the text
+ *   with the matrix and the gap costs (s per '=' or 'X' column, - o - g e per run of g 'I' or 'D') equals score; the script neither
+ *   begins nor ends with 'I' or 'D' next to a clip or a read end; its first and its last aligned column have s > 0 (a first
+ *   column with s <= 0 would start from H = 0 at no gain, a last one would leave an earlier cell with at least the score).
+ *   "Neither begins nor ends with 'X'" NO LONGER HOLDS: a substitution may score positively.  0 <= textBegin <= textEnd <= L, and the
+ *   score never exceeds the unbanded local score under the same matrix.
+ * Under awfmMatrixScoringUniform's matrix every output of the four calls equals the affine sibling's under that scoring.
+ *
+ * THE MATRIX TRAVELS IN THE LAUNCH'S ARGUMENTS: the caller may change or free its struct as soon as the call returns, two streams
+ * may run different matrices on one image at once, and nothing is stored in the image or the handle.  On the device a workgroup
+ * copies it once into LDS (rows 32 bytes apart); per cell the two staged characters become letters, then classes, then one
+ * signed byte load.  $AWFM_GPU_DIAG score_group / affine_group force G as for the siblings.
+ *
+ * awfmMatrixScoringUniform(alphabet, scoring, out): + match where both classes are the same proper letter, - mismatch everywhere
+ * else ("other x other" included, all 21 x 21 entries), gaps copied.  AwFmNullPtrError for a NULL; AwFmIllegalPositionError for an
+ * alphabet that is none, a scoring affine alignment refuses, match > 127 or mismatch > 128.
+ *
+ * awfmMatrixScoringFromText(alphabet, text, bytes, gapOpen, gapExtend, out): the usual matrix text format out of memory, no I/O,
+ * nothing read outside [text, text + bytes), no terminator needed.  Lines end with '\n' (a '\r' before it is blank); lines whose
+ * first non-blank character is '#' and blank lines are skipped; the first remaining line is the column letters, blank-separated
+ * (at most 64); every further line is a row letter followed by one integer (optional sign, decimal) per column.  Letters are
+ * case-insensitive; U is T.  The "other" class takes the row and column of X (amino) or N (nucleotide) where the text has them;
+ * entries of that class the text does not give take the smallest proper x proper entry.  Every other letter that is not proper
+ * (B, Z, J, ... / R, Y, ...) and every other single character ('*') is skipped as a row and as a column, its values still
+ * counted and checked.  Entries of classes the alphabet does not have are 0.  *out is written on success only.  Refused:
+ *   AwFmNullPtrError          out == NULL, or text == NULL with bytes != 0;
+ *   AwFmIllegalPositionError  an alphabet that is none, gapOpen > 255, gapExtend outside 1..255; a value outside -128..127;
+ *   AwFmFileFormatError       a proper letter (or X / N) repeated as a row or as a column; a proper letter missing as a row or as
+ *                             a column (also: no lines at all); a row or column name of more than one character; more than 64
+ *                             columns; a value that is no integer; a row with more or fewer values than columns -- which is
+ *                             also what a text that ends inside a row is. */
+#define AWFM_MATRIX_CLASSES 21u
+struct AwFmMatrixScoring {
+  int8_t substitution[AWFM_MATRIX_CLASSES * AWFM_MATRIX_CLASSES]; /* [class(read) * 21 + class(text)] */
+  uint32_t gapOpen, gapExtend;                                    /* 0..255, 1..255: affine alignment's */
+};
+enum AwFmReturnCode awfmMatrixScoringUniform(enum AwFmAlphabetType alphabet, const struct AwFmAlignScoring *scoring,
+                                             struct AwFmMatrixScoring *out);
+enum AwFmReturnCode awfmMatrixScoringFromText(enum AwFmAlphabetType alphabet, const char *text, uint64_t bytes, uint32_t gapOpen,
+                                              uint32_t gapExtend, struct AwFmMatrixScoring *out);
+enum AwFmReturnCode awfmScoreChainsMatrix(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
+                                          uint32_t maxDrift, const struct AwFmMatrixScoring *scoring, uint32_t minScore, uint32_t mapqCap,
+                                          const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
+                                          enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads);
+enum AwFmReturnCode awfmGpuScoreChainsMatrix(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
+                                             uint32_t bandPad, uint32_t maxDrift, const struct AwFmMatrixScoring *scoring, uint32_t minScore,
+                                             uint32_t mapqCap, const struct AwFmSlotScoreOutputs *dOut, void *stream);
+enum AwFmReturnCode awfmAlignChainsMatrix(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
+                                          uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                          const struct AwFmMatrixScoring *scoring, uint32_t maxOps, const uint8_t *text, uint64_t length,
+                                          const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
+                                          const struct AwFmAffineOutputs *out, unsigned threads);
+enum AwFmReturnCode awfmGpuAlignChainsMatrix(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, const uint32_t *dSlots, uint64_t numReads,
+                                             uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                             const struct AwFmMatrixScoring *scoring, uint32_t maxOps, uint32_t maxRows,
+                                             const struct AwFmAffineOutputs *dOut, void *dScratch, void *stream);
 
 /* ---- window scores: the full-width local affine alignment of a read against a text window the caller names, as a slot ----
  * The stage for reads WITHOUT a chain: a mate with a burst of errors, a read across a divergent stretch, a read shorter than a
