@@ -49,6 +49,7 @@ GPU_SYMBOLS = [
     "awfmScoreChainsAffine", "awfmGpuScoreChainsAffine",
     "awfmMatrixScoringUniform", "awfmMatrixScoringFromText", "awfmScoreChainsMatrix", "awfmGpuScoreChainsMatrix", "awfmAlignChainsMatrix",
     "awfmGpuAlignChainsMatrix",
+    "awfmScoreChainsEndBonus", "awfmGpuScoreChainsEndBonus", "awfmAlignChainsEndBonus", "awfmGpuAlignChainsEndBonus",
     "awfmScoreWindowsAffine", "awfmGpuScoreWindowsAffineScratchBytes", "awfmGpuScoreWindowsAffine",
     "awfmPairMates", "awfmGpuPairMates", "awfmReverseComplementReads", "awfmGpuReverseComplementReads",
     "awfmInsertHistogram", "awfmGpuInsertHistogram", "awfmInsertInterval", "awfmGpuInsertInterval", "awfmGpuPairMatesEstimated",
@@ -379,6 +380,17 @@ def lib():
                                             C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmSlotScoreOutputs), C.c_uint]),
         "awfmGpuScoreChainsMatrix": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.POINTER(AwFmMatrixScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmSlotScoreOutputs), vp]),
+        "awfmAlignChainsEndBonus": (C.c_int, [C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmMatrixScoring),
+                                              C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmAffineOutputs), C.c_uint]),
+        "awfmGpuAlignChainsEndBonus": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.POINTER(AwFmMatrixScoring), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmAffineOutputs),
+                                                 vp, vp]),
+        "awfmScoreChainsEndBonus": (C.c_int, [C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmMatrixScoring),
+                                              C.c_uint32, C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.c_int, C.POINTER(AwFmSlotScoreOutputs),
+                                              C.c_uint]),
+        "awfmGpuScoreChainsEndBonus": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.POINTER(AwFmMatrixScoring), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmSlotScoreOutputs),
+                                                 vp]),
         "awfmGpuAlignChainsAffine": (C.c_int, [vp, C.POINTER(AwFmVerifyInputs), vp, u64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.POINTER(AwFmAlignScoring), C.c_uint32, C.c_uint32, C.POINTER(AwFmAffineOutputs), vp, vp]),
         "awfmScoreChainsAffine": (C.c_int, [C.POINTER(AwFmVerifyInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AwFmAlignScoring),

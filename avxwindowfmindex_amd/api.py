@@ -602,6 +602,10 @@ def align_scoring(match=1, mismatch=4, gap_open=6, gap_extend=1):
 MATRIX_CLASSES = 21  # AWFM_MATRIX_CLASSES
 
 
+END_BONUS = 5         # the end bonus the *_end_bonus calls take by default: BWA-MEM's clip penalty
+END_BONUS_MAX = 255   # AWFM_END_BONUS_MAX
+
+
 def matrix_scoring(substitution, gap_open=6, gap_extend=1):
     """struct AwFmMatrixScoring (include/awfm_gpu.h, "substitution matrices") from 21 x 21 int8 values, [class of the read's character,
     class of the text's], and the gap costs"""
@@ -671,9 +675,19 @@ def align_chains_matrix_host(read_chars, read_offsets, slots, chosen, text, matr
                                      band_pad, max_drift, max_ops, threads, outputs, num_read_chars, fill, unaligned_before, truncated_before)
 
 
+def align_chains_end_bonus_host(read_chars, read_offsets, slots, chosen, text, matrix, end_bonus=END_BONUS, sequence_ends=None,
+                                alphabet=AwFmAlphabetDna, band_pad=8, max_drift=15, max_ops=32, threads=4, outputs=None, num_read_chars=None,
+                                fill=None, unaligned_before=0, truncated_before=0):
+    """awfmAlignChainsEndBonus (include/awfm_gpu.h, "end bonus"): align_chains_matrix_host with end_bonus, 0 to 255, earned by an
+    alignment at each read end it reaches; the scores include it"""
+    return _align_chains_scored_host("awfmAlignChainsEndBonus", matrix, read_chars, read_offsets, slots, chosen, text, sequence_ends, alphabet,
+                                     band_pad, max_drift, max_ops, threads, outputs, num_read_chars, fill, unaligned_before, truncated_before,
+                                     behind=(end_bonus,))
+
+
 def _align_chains_scored_host(symbol, costs, read_chars, read_offsets, slots, chosen, text, sequence_ends, alphabet, band_pad, max_drift, max_ops,
-                              threads, outputs, num_read_chars, fill, unaligned_before, truncated_before):
-    """the two calls above: `symbol` with `costs`, the struct it takes"""
+                              threads, outputs, num_read_chars, fill, unaligned_before, truncated_before, behind=()):
+    """the calls above: `symbol` with `costs`, the struct it takes, and what the call takes behind it"""
     chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
     t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
     o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
@@ -705,7 +719,7 @@ def _align_chains_scored_host(symbol, costs, read_chars, read_offsets, slots, ch
         if name in outputs:
             setattr(aout, name, counter.ctypes.data)
     rc = getattr(_lib.lib(), symbol)(C.byref(vin), address(which), n, shape[1], band_pad, max_drift, None if costs is None else C.byref(costs),
-                                     max_ops, address(t), t.size, None if ends is None or not ends.size else ends.ctypes.data,
+                                     *behind, max_ops, address(t), t.size, None if ends is None or not ends.size else ends.ctypes.data,
                                      0 if ends is None else ends.size, alphabet, C.byref(aout), threads)
     _check(symbol, rc)
     for name, counter in counters.items():
@@ -839,9 +853,19 @@ def score_chains_matrix_host(read_chars, read_offsets, slots, text, matrix, sequ
                                      max_drift, min_score, mapq_cap, threads, outputs, num_read_chars, fill, unscored_before, mapped_before)
 
 
+def score_chains_end_bonus_host(read_chars, read_offsets, slots, text, matrix, end_bonus=END_BONUS, sequence_ends=None, alphabet=AwFmAlphabetDna,
+                                band_pad=8, max_drift=15, min_score=0, mapq_cap=60, threads=4, outputs=None, num_read_chars=None, fill=None,
+                                unscored_before=0, mapped_before=0):
+    """awfmScoreChainsEndBonus (include/awfm_gpu.h, "end bonus"): score_chains_matrix_host with end_bonus, 0 to 255; the slot scores,
+    min_score and the mapping quality work on scores that include it"""
+    return _score_chains_scored_host("awfmScoreChainsEndBonus", matrix, read_chars, read_offsets, slots, text, sequence_ends, alphabet, band_pad,
+                                     max_drift, min_score, mapq_cap, threads, outputs, num_read_chars, fill, unscored_before, mapped_before,
+                                     behind=(end_bonus,))
+
+
 def _score_chains_scored_host(symbol, costs, read_chars, read_offsets, slots, text, sequence_ends, alphabet, band_pad, max_drift, min_score,
-                              mapq_cap, threads, outputs, num_read_chars, fill, unscored_before, mapped_before):
-    """the two calls above: `symbol` with `costs`, the struct it takes"""
+                              mapq_cap, threads, outputs, num_read_chars, fill, unscored_before, mapped_before, behind=()):
+    """the calls above: `symbol` with `costs`, the struct it takes, and what the call takes behind it"""
     chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
     t = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
     o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
@@ -870,8 +894,8 @@ def _score_chains_scored_host(symbol, costs, read_chars, read_offsets, slots, te
     for name, counter in counters.items():
         if name in outputs:
             setattr(sout, name, counter.ctypes.data)
-    rc = getattr(_lib.lib(), symbol)(C.byref(vin), n, shape[1], band_pad, max_drift, None if costs is None else C.byref(costs), min_score,
-                                     mapq_cap, address(t), t.size, None if ends is None or not ends.size else ends.ctypes.data,
+    rc = getattr(_lib.lib(), symbol)(C.byref(vin), n, shape[1], band_pad, max_drift, None if costs is None else C.byref(costs), *behind,
+                                     min_score, mapq_cap, address(t), t.size, None if ends is None or not ends.size else ends.ctypes.data,
                                      0 if ends is None else ends.size, alphabet, C.byref(sout), threads)
     _check(symbol, rc)
     for name, counter in counters.items():
@@ -1394,6 +1418,24 @@ class GpuIndex:
                _lib.lib().awfmGpuScoreChainsMatrix(self.handle, C.byref(inputs), num_reads, max_candidates, band_pad, max_drift,
                                                    None if scoring is None else C.byref(scoring), min_score, mapq_cap, C.byref(outputs),
                                                    stream or None))
+
+    # end bonus (include/awfm_gpu.h) --------------------------------------
+    def align_chains_end_bonus(self, inputs, d_slots, num_reads, outputs, d_scratch, max_candidates=4, band_pad=8, max_drift=15, scoring=None,
+                               end_bonus=END_BONUS, max_ops=32, max_rows=4096, stream=0):
+        """awfmGpuAlignChainsEndBonus: align_chains_matrix with end_bonus, 0 to 255, earned at each read end the alignment reaches;
+        the scores include it; d_scratch is align_chains_affine_scratch_bytes(max_rows) bytes"""
+        _check("awfmGpuAlignChainsEndBonus",
+               _lib.lib().awfmGpuAlignChainsEndBonus(self.handle, C.byref(inputs), d_slots or None, num_reads, max_candidates, band_pad, max_drift,
+                                                     None if scoring is None else C.byref(scoring), end_bonus, max_ops, max_rows,
+                                                     C.byref(outputs), d_scratch or None, stream or None))
+
+    def score_chains_end_bonus(self, inputs, num_reads, outputs, max_candidates=4, band_pad=8, max_drift=15, scoring=None, end_bonus=END_BONUS,
+                               min_score=0, mapq_cap=60, stream=0):
+        """awfmGpuScoreChainsEndBonus: score_chains_matrix with end_bonus, 0 to 255; one launch, no scratch"""
+        _check("awfmGpuScoreChainsEndBonus",
+               _lib.lib().awfmGpuScoreChainsEndBonus(self.handle, C.byref(inputs), num_reads, max_candidates, band_pad, max_drift,
+                                                     None if scoring is None else C.byref(scoring), end_bonus, min_score, mapq_cap,
+                                                     C.byref(outputs), stream or None))
 
     # alignment strings (include/awfm_gpu.h) ------------------------------
     def alignment_strings_scratch_bytes(self, num_reads):

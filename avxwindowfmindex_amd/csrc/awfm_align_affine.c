@@ -3,7 +3,9 @@
  * gap costs of every read against the record its chosen slot names, with soft clipping and the edit script.  The host twin of
  * awfmGpuAlignChainsAffine and its checker: a read at a time, the classification of the slot and the rows of the recurrence from
  * awfm_band.h (awfmClassifySlot, awfmAffineRows: three rows of at most 64 cells, shared with awfm_score_affine.c) with a trace
- * byte per cell in an n x width table, then the walk back through the three states.  Exact and readable rather than fast.  The reference has no analogue (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
+ * byte per cell in an n x width table, then the walk back through the three states.  awfmAlignChainsMatrix and
+ * awfmAlignChainsEndBonus are the same call with the diagonal's score from a matrix, and with a bonus for a reached read end.
+ * Exact and readable rather than fast.  The reference has no analogue (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
  */
 #include <stdlib.h>
 #include <string.h>
@@ -169,11 +171,11 @@ static void awfmAffineRange(void *p, uint64_t begin, uint64_t end, unsigned tid)
   c->truncated[tid & 63u] += truncated;
 }
 
-/* the call behind both entry points; scoring or matrix is given, the other is NULL */
+/* the call behind the entry points; scoring or matrix is given, the other is NULL; endBonus: 0 but for "end bonus" */
 static enum AwFmReturnCode awfmAlignChainsScored(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
                                                  uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
                                                  const struct AwFmAlignScoring *scoring, const struct AwFmMatrixScoring *matrix,
-                                                 uint32_t maxOps, const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds,
+                                                 uint32_t endBonus, uint32_t maxOps, const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds,
                                                  uint64_t numRecords, enum AwFmAlphabetType alphabet, const struct AwFmAffineOutputs *out,
                                                  unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
@@ -181,7 +183,7 @@ static enum AwFmReturnCode awfmAlignChainsScored(const struct AwFmVerifyInputs *
                                                         numReads, maxCandidates, bandPad, maxDrift);
   if (rc != AwFmSuccess) return rc;
   if (maxOps < 1 || maxOps > AWFM_ALIGN_MAX_OPS) return AwFmIllegalPositionError;
-  if (!(matrix ? awfmMatrixScoringOk(matrix) : awfmScoringOk(scoring))) return AwFmIllegalPositionError;
+  if (!(matrix ? awfmMatrixScoringOk(matrix) : awfmScoringOk(scoring)) || endBonus > AWFM_END_BONUS_MAX) return AwFmIllegalPositionError;
   struct awfmAffineCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.in = in;
@@ -195,7 +197,7 @@ static enum AwFmReturnCode awfmAlignChainsScored(const struct AwFmVerifyInputs *
   ctx.pad = bandPad;
   ctx.drift = maxDrift;
   ctx.maxOps = maxOps;
-  ctx.costs = matrix ? awfmMatrixCostsOf(matrix, alphabet) : awfmAffineCostsOf(scoring, alphabet);
+  ctx.costs = matrix ? awfmEndBonusCostsOf(matrix, endBonus, alphabet) : awfmAffineCostsOf(scoring, alphabet);
   awfmParallelFor(threads ? threads : 1, numReads, awfmAffineRange, &ctx);
   if (ctx.failed) return AwFmAllocationFailure;
   uint64_t unaligned = 0, truncated = 0;
@@ -213,7 +215,7 @@ enum AwFmReturnCode awfmAlignChainsAffine(const struct AwFmVerifyInputs *in, con
                                           const struct AwFmAlignScoring *scoring, uint32_t maxOps, const uint8_t *text, uint64_t length,
                                           const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
                                           const struct AwFmAffineOutputs *out, unsigned threads) {
-  return awfmAlignChainsScored(in, slots, numReads, maxCandidates, bandPad, maxDrift, scoring, NULL, maxOps, text, length, sequenceEnds,
+  return awfmAlignChainsScored(in, slots, numReads, maxCandidates, bandPad, maxDrift, scoring, NULL, 0, maxOps, text, length, sequenceEnds,
                                numRecords, alphabet, out, threads);
 }
 
@@ -223,6 +225,16 @@ enum AwFmReturnCode awfmAlignChainsMatrix(const struct AwFmVerifyInputs *in, con
                                           const struct AwFmMatrixScoring *scoring, uint32_t maxOps, const uint8_t *text, uint64_t length,
                                           const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
                                           const struct AwFmAffineOutputs *out, unsigned threads) {
-  return awfmAlignChainsScored(in, slots, numReads, maxCandidates, bandPad, maxDrift, NULL, scoring, maxOps, text, length, sequenceEnds,
+  return awfmAlignChainsScored(in, slots, numReads, maxCandidates, bandPad, maxDrift, NULL, scoring, 0, maxOps, text, length, sequenceEnds,
                                numRecords, alphabet, out, threads);
+}
+
+/* "end bonus" (include/awfm_gpu.h): the matrix call with B for a read end that is reached */
+enum AwFmReturnCode awfmAlignChainsEndBonus(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
+                                            uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                            const struct AwFmMatrixScoring *scoring, uint32_t endBonus, uint32_t maxOps, const uint8_t *text,
+                                            uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
+                                            const struct AwFmAffineOutputs *out, unsigned threads) {
+  return awfmAlignChainsScored(in, slots, numReads, maxCandidates, bandPad, maxDrift, NULL, scoring, endBonus, maxOps, text, length,
+                               sequenceEnds, numRecords, alphabet, out, threads);
 }

@@ -100,16 +100,18 @@ static inline uint32_t awfmMatrixClass(int amino, uint8_t c) {
 }
 
 /* the costs of the affine recurrence as the scoring struct gives them, and the alphabet of the comparison; matrix: NULL, or the
- * AWFM_MATRIX_CLASSES x AWFM_MATRIX_CLASSES substitution scores that take the place of match and mismatch */
+ * AWFM_MATRIX_CLASSES x AWFM_MATRIX_CLASSES substitution scores that take the place of match and mismatch; bonus: "end bonus"'s
+ * B, 0 for every call without one */
 struct awfmAffineCosts {
   int32_t match, mismatch, open, extend;
   int amino;
   const int8_t *matrix;
+  int32_t bonus;
 };
 
 static inline struct awfmAffineCosts awfmAffineCostsOf(const struct AwFmAlignScoring *scoring, enum AwFmAlphabetType alphabet) {
   const struct awfmAffineCosts c = {(int32_t)scoring->match, (int32_t)scoring->mismatch, (int32_t)scoring->gapOpen, (int32_t)scoring->gapExtend,
-                                    alphabet == AwFmAlphabetAmino, NULL};
+                                    alphabet == AwFmAlphabetAmino, NULL, 0};
   return c;
 }
 
@@ -120,7 +122,14 @@ static inline int awfmMatrixScoringOk(const struct AwFmMatrixScoring *scoring) {
 
 static inline struct awfmAffineCosts awfmMatrixCostsOf(const struct AwFmMatrixScoring *scoring, enum AwFmAlphabetType alphabet) {
   const struct awfmAffineCosts c = {0, 0, (int32_t)scoring->gapOpen, (int32_t)scoring->gapExtend, alphabet == AwFmAlphabetAmino,
-                                    scoring->substitution};
+                                    scoring->substitution, 0};
+  return c;
+}
+
+/* "end bonus" (include/awfm_gpu.h): the matrix's costs and B, 0 to AWFM_END_BONUS_MAX */
+static inline struct awfmAffineCosts awfmEndBonusCostsOf(const struct AwFmMatrixScoring *scoring, uint32_t endBonus, enum AwFmAlphabetType alphabet) {
+  struct awfmAffineCosts c = awfmMatrixCostsOf(scoring, alphabet);
+  c.bonus = (int32_t)endBonus;
   return c;
 }
 
@@ -133,8 +142,8 @@ static inline int32_t awfmAffineDiagonal(const struct awfmAffineCosts *c, uint32
 /* a trace byte: the source of H in its low three bits, then whether F and E of the cell open their gap at its neighbour */
 enum { AWFM_SRC_STOP = 0, AWFM_SRC_EQ = 1, AWFM_SRC_X = 2, AWFM_SRC_F = 3, AWFM_SRC_E = 4, AWFM_TRACE_F_OPENS = 8, AWFM_TRACE_E_OPENS = 16 };
 
-/* the end cell of a banded local alignment: the largest H over existing cells with i >= 1, then the smallest i, then the
- * smallest t = i + lo + k; score 0: there is none */
+/* the end cell of a banded local alignment: the largest V over existing cells with i >= 1 -- V is H, and H + bonus for a cell of
+ * row n with H > 0 ("end bonus") --, then the smallest i, then the smallest t = i + lo + k; score is that V, 0: there is none */
 struct awfmAffineEnd {
   int32_t score;
   int64_t i, k;
@@ -155,7 +164,7 @@ static inline struct awfmAffineEnd awfmAffineRows(const struct awfmAffineCosts *
   struct awfmAffineEnd end = {0, 0, 0};
   for (int64_t k = 0; k < width; k++) { /* row 0 */
     const int64_t t = lo + k;
-    prevH[k] = t >= 0 && t <= L ? 0 : AWFM_BAND_NEG;
+    prevH[k] = t >= 0 && t <= L ? c->bonus : AWFM_BAND_NEG;
     prevF[k] = AWFM_BAND_NEG;
   }
   for (int64_t i = 1; i <= n; i++) {
@@ -178,8 +187,9 @@ static inline struct awfmAffineEnd awfmAffineRows(const struct awfmAffineCosts *
         E[k] = e;
         code = H == 0 ? AWFM_SRC_STOP : M == H ? (sub ? AWFM_SRC_X : AWFM_SRC_EQ) : F == H ? AWFM_SRC_F : AWFM_SRC_E;
         code |= (fOpens >= fExtends ? AWFM_TRACE_F_OPENS : 0) | (eOpens >= eExtends ? AWFM_TRACE_E_OPENS : 0);
-        if (H > end.score) { /* rows in ascending order, then columns: the smallest i, then the smallest t of the largest H */
-          end.score = H;
+        const int32_t V = i == n && H > 0 ? H + c->bonus : H;
+        if (V > end.score) { /* rows in ascending order, then columns: the smallest i, then the smallest t of the largest V */
+          end.score = V;
           end.i = i;
           end.k = k;
         }

@@ -1,6 +1,6 @@
 /*
  * awfm_band_kernel.h -- what the kernels of the read path share (awfm_verify_kernel.h, awfm_align_kernel.h,
- * awfm_align_affine_kernel.h, awfm_score_affine_kernel.h, awfm_matrix_kernel.h; awfm_window_affine_kernel.h takes the letters): a group's staging of
+ * awfm_align_affine_kernel.h, awfm_score_affine_kernel.h, awfm_matrix_kernel.h, awfm_end_bonus_kernel.h; awfm_window_affine_kernel.h takes the letters): a group's staging of
  * read and text bytes into LDS, the letter comparison, the classification of a chain slot up to TOO WIDE, the band of a whole
  * read and the staging of one of its chunks, the row and the end cell of the banded affine recurrence, the two sources of the
  * diagonal's score (two costs, or a substitution matrix in LDS) -- and what their
@@ -151,8 +151,11 @@ __device__ __forceinline__ bool stagedSub(const StagedChunk &c, const ReadBand &
 }
 
 /* The diagonal's score s(R[i-1], T[t-1]) of a cell, from its two letters and verification's sub: what affineRow adds to the
- * previous row's H.  IdentityScore is "affine alignment"'s, + match or - mismatch out of the launch's parameters */
+ * previous row's H.  IdentityScore is "affine alignment"'s, + match or - mismatch out of the launch's parameters.  A scorer also
+ * says what a reached read end earns, endBonus(): the constant 0 for these two, so that row 0 starts from 0 and row n's
+ * value behind the row loop folds away; "end bonus"' B for EndBonusScore (awfm_end_bonus_kernel.h) */
 struct IdentityScore {
+  static constexpr __device__ __forceinline__ int endBonus() { return 0; }
   template <typename P>
   __device__ __forceinline__ int operator()(const P &p, const StagedLetters &, const bool sub) const {
     return sub ? -p.mismatch : p.match;
@@ -169,6 +172,7 @@ constexpr unsigned kMatrixLdsBytes = AWFM_MATRIX_CLASSES * kMatrixStride;
 struct MatrixScore {
   const signed char *sMatrix;
   unsigned other;
+  static constexpr __device__ __forceinline__ int endBonus() { return 0; }
   template <typename P>
   __device__ __forceinline__ int operator()(const P &, const StagedLetters &l, const bool) const {
     const unsigned r = l.read < other ? l.read : other, t = l.text < other ? l.text : other;
@@ -279,6 +283,17 @@ inline enum AwFmReturnCode scoringRefused(const char *name, const struct AwFmAli
 inline enum AwFmReturnCode matrixScoringRefused(const char *name, const struct AwFmMatrixScoring *scoring) {
   if (scoring->gapOpen > 255 || scoring->gapExtend < 1 || scoring->gapExtend > 255) {
     setCallError(name, "gapOpen is 0 to 255 and gapExtend 1 to 255");
+    return AwFmIllegalPositionError;
+  }
+  return AwFmSuccess;
+}
+
+/* "end bonus": the matrix's ranges, then B */
+inline enum AwFmReturnCode endBonusScoringRefused(const char *name, const struct AwFmMatrixScoring *scoring, const uint32_t endBonus) {
+  const enum AwFmReturnCode rc = matrixScoringRefused(name, scoring);
+  if (rc != AwFmSuccess) return rc;
+  if (endBonus > AWFM_END_BONUS_MAX) {
+    setCallError(name, "endBonus is 0 to 255");
     return AwFmIllegalPositionError;
   }
   return AwFmSuccess;

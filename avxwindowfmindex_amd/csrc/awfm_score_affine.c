@@ -4,7 +4,9 @@
  * of awfmGpuScoreChainsAffine and its checker: a read at a time, the classification of a slot and the rows of "affine alignment"
  * from awfm_band.h, without a trace table and without the walk; then the per-read rules, written plainly over the read's C results.
  * A slot gets what awfmAlignChainsAffine (awfm_align_affine.c) puts into scores, readEnds and textEnds when slots[r] names it:
- * both files call the same rows, and tests/test_score_chains.py checks it.  Exact and readable rather than fast.  The reference has no analogue
+ * both files call the same rows, and tests/test_score_chains.py checks it.  awfmScoreChainsMatrix and awfmScoreChainsEndBonus are
+ * the same call with the diagonal's score from a matrix, and with a bonus for a reached read end.  Exact and readable rather than
+ * fast.  The reference has no analogue
  * (it stops at positions: ref src/AwFmParallelSearch.c:315-365).
  */
 #include <stdlib.h>
@@ -100,10 +102,10 @@ static void awfmScoreRange(void *p, uint64_t begin, uint64_t end, unsigned tid) 
   c->mapped[tid & 63u] += mapped;
 }
 
-/* the call behind both entry points; scoring or matrix is given, the other is NULL */
+/* the call behind the entry points; scoring or matrix is given, the other is NULL; endBonus: 0 but for "end bonus" */
 static enum AwFmReturnCode awfmScoreChainsScored(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
                                                  uint32_t maxDrift, const struct AwFmAlignScoring *scoring,
-                                                 const struct AwFmMatrixScoring *matrix, uint32_t minScore, uint32_t mapqCap,
+                                                 const struct AwFmMatrixScoring *matrix, uint32_t endBonus, uint32_t minScore, uint32_t mapqCap,
                                                  const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
                                                  enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads) {
   if (numReads == 0) return AwFmSuccess;
@@ -111,7 +113,7 @@ static enum AwFmReturnCode awfmScoreChainsScored(const struct AwFmVerifyInputs *
                                                         maxCandidates, bandPad, maxDrift);
   if (rc != AwFmSuccess) return rc;
   if (mapqCap > AWFM_SCORE_MAX_MAPQ) return AwFmIllegalPositionError;
-  if (!(matrix ? awfmMatrixScoringOk(matrix) : awfmScoringOk(scoring))) return AwFmIllegalPositionError;
+  if (!(matrix ? awfmMatrixScoringOk(matrix) : awfmScoringOk(scoring)) || endBonus > AWFM_END_BONUS_MAX) return AwFmIllegalPositionError;
   struct awfmScoreCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.in = in;
@@ -125,7 +127,7 @@ static enum AwFmReturnCode awfmScoreChainsScored(const struct AwFmVerifyInputs *
   ctx.drift = maxDrift;
   ctx.minScore = minScore;
   ctx.cap = mapqCap;
-  ctx.costs = matrix ? awfmMatrixCostsOf(matrix, alphabet) : awfmAffineCostsOf(scoring, alphabet);
+  ctx.costs = matrix ? awfmEndBonusCostsOf(matrix, endBonus, alphabet) : awfmAffineCostsOf(scoring, alphabet);
   awfmParallelFor(threads ? threads : 1, numReads, awfmScoreRange, &ctx);
   uint64_t unscored = 0, mapped = 0;
   for (unsigned t = 0; t < 64; t++) {
@@ -141,7 +143,7 @@ enum AwFmReturnCode awfmScoreChainsAffine(const struct AwFmVerifyInputs *in, uin
                                           uint32_t maxDrift, const struct AwFmAlignScoring *scoring, uint32_t minScore, uint32_t mapqCap,
                                           const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
                                           enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads) {
-  return awfmScoreChainsScored(in, numReads, maxCandidates, bandPad, maxDrift, scoring, NULL, minScore, mapqCap, text, length, sequenceEnds,
+  return awfmScoreChainsScored(in, numReads, maxCandidates, bandPad, maxDrift, scoring, NULL, 0, minScore, mapqCap, text, length, sequenceEnds,
                                numRecords, alphabet, out, threads);
 }
 
@@ -150,6 +152,16 @@ enum AwFmReturnCode awfmScoreChainsMatrix(const struct AwFmVerifyInputs *in, uin
                                           uint32_t maxDrift, const struct AwFmMatrixScoring *scoring, uint32_t minScore, uint32_t mapqCap,
                                           const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords,
                                           enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out, unsigned threads) {
-  return awfmScoreChainsScored(in, numReads, maxCandidates, bandPad, maxDrift, NULL, scoring, minScore, mapqCap, text, length, sequenceEnds,
+  return awfmScoreChainsScored(in, numReads, maxCandidates, bandPad, maxDrift, NULL, scoring, 0, minScore, mapqCap, text, length, sequenceEnds,
                                numRecords, alphabet, out, threads);
+}
+
+/* "end bonus" (include/awfm_gpu.h): the matrix call with B for a read end that is reached */
+enum AwFmReturnCode awfmScoreChainsEndBonus(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
+                                            uint32_t maxDrift, const struct AwFmMatrixScoring *scoring, uint32_t endBonus, uint32_t minScore,
+                                            uint32_t mapqCap, const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds,
+                                            uint64_t numRecords, enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out,
+                                            unsigned threads) {
+  return awfmScoreChainsScored(in, numReads, maxCandidates, bandPad, maxDrift, NULL, scoring, endBonus, minScore, mapqCap, text, length,
+                               sequenceEnds, numRecords, alphabet, out, threads);
 }

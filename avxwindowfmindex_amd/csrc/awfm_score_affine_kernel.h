@@ -70,7 +70,8 @@ __device__ __forceinline__ unsigned scoreSlot(const Ref p, const S &score, const
   const bool inBand = (int)k < band.width;
   const unsigned char *R = p->in.readChars + readBegin, *T = p->text + slot.S;
   const int kExtend = (int)k * p->extend;
-  int prevH = inBand && (int)k >= band.uMin && (int)k <= band.uMax ? 0 : kBandNeg, prevF = kBandNeg; /* row 0: H(0, t) = 0 */
+  const int bonus = score.endBonus(); /* the constant 0 but for "end bonus" */
+  int prevH = inBand && (int)k >= band.uMin && (int)k <= band.uMax ? bonus : kBandNeg, prevF = kBandNeg; /* row 0: H(0, t) = B */
   int bestH = 0, bestI = 0;
   for (int i0 = 0; i0 < n; i0 += (int)kVerifyChunk) {
     const int rows = n - i0 < (int)kVerifyChunk ? n - i0 : (int)kVerifyChunk;
@@ -86,6 +87,16 @@ __device__ __forceinline__ unsigned scoreSlot(const Ref p, const S &score, const
       }
       prevH = c.h;
       prevF = inMatrix ? c.F : kBandNeg;
+    }
+  }
+  /* V: a cell of row n reaches the read's end and is worth H + B when H > 0.  prevH is the lane's H(n, .) now, and bestH is at
+   * least that: taking row n's value behind the loop gives the lane's largest V and its smallest i, as the update on V in
+   * every row would, and costs the rows nothing */
+  if (bonus != 0) {
+    const int v = prevH > 0 ? prevH + bonus : prevH;
+    if (v > bestH) {
+      bestH = v;
+      bestI = n;
     }
   }
   const AffineEnd end = affineEndCell<G>(bestH, bestI, k);

@@ -85,8 +85,10 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *   verify_group=16|32|64   awfmGpuVerifyChains: lanes per slot, where that is more than the band's diagonals need (a smaller
  *                       value than the band needs is ignored); the default is the smallest that holds the band
  *   align_group=16|32|64    awfmGpuAlignChains: lanes per read, in the same way
- *   affine_group=32|64      awfmGpuAlignChainsAffine, awfmGpuAlignChainsMatrix: lanes per read, in the same way
- *   score_group=32|64       awfmGpuScoreChainsAffine, awfmGpuScoreChainsMatrix: lanes per slot, in the same way
+ *   affine_group=32|64      awfmGpuAlignChainsAffine, awfmGpuAlignChainsMatrix, awfmGpuAlignChainsEndBonus: lanes per read, in the
+ *                       same way
+ *   score_group=32|64       awfmGpuScoreChainsAffine, awfmGpuScoreChainsMatrix, awfmGpuScoreChainsEndBonus: lanes per slot, in the
+ *                       same way
  *   window_q=4|8|12         awfmGpuScoreWindowsAffine: columns per lane for every read (narrower column blocks)
  *   pair_group=64           awfmGpuPairMates: a wave per pair also where 16 lanes hold the candidates
  *   insert_tier=global      awfmGpuInsertHistogram: global atomics at any bin count (default: a private histogram in LDS per
@@ -970,7 +972,66 @@ enum AwFmReturnCode awfmGpuAlignChainsMatrix(AwFmGpuIndex *g, const struct AwFmV
                                              const struct AwFmMatrixScoring *scoring, uint32_t maxOps, uint32_t maxRows,
                                              const struct AwFmAffineOutputs *dOut, void *dScratch, void *stream);
 
-/* ---- window scores: the full-width local affine alignment of a read against a text window the caller names, as a slot ----
+/* ---- end bonus: slot scores and affine alignment whose reads reach their ends ----
+ * The calls above are purely local: under (1, 4, 6, 1) a substitution within four characters of a read end never pays and the end
+ * is soft-clipped, so a variant at position 148 of 150 vanishes from the script, from NM and from MD:Z.  The remedy of every
+ * short-read mapper (BWA-MEM's clip penalty, minimap2's end bonus): an alignment that reaches a read end earns B there.  NEW CALLS
+ * ONLY: nothing above changes.
+ *
+ * awfmScoreChainsEndBonus / awfmGpuScoreChainsEndBonus are awfmScoreChainsMatrix / awfmGpuScoreChainsMatrix, and
+ * awfmAlignChainsEndBonus / awfmGpuAlignChainsEndBonus are awfmAlignChainsMatrix / awfmGpuAlignChainsMatrix, with one more argument
+ * behind the matrix, endBonus B in 0 .. AWFM_END_BONUS_MAX = 255 (more: AwFmIllegalPositionError, where the siblings check the
+ * scoring): the same inputs, outputs, per-read rules, statuses and their order, counters, NULL rules, order of the argument
+ * checks, maxOps, maxRows and dScratch of awfmGpuAlignChainsAffineScratchBytes(g, maxRows) bytes; one launch, no host wait, no
+ * allocation; the matrix and B travel by value in the launch's arguments.  MATRIX ONLY: identity scoring is
+ * awfmMatrixScoringUniform's matrix.  The host twins (csrc/awfm_score_affine.c, csrc/awfm_align_affine.c) are the definition and
+ * the checkers.  The DEFINITION is "substitution matrices"' word for word, except:
+ *   row 0       H(0, t) = B for every existing cell of row 0 (it was 0); cells that do not exist stay minus infinity, and E = F =
+ *               -inf in row 0 as before.  Rows i >= 1 are unchanged, H = max(0, M, F, E): the floor 0 is a fresh start behind a
+ *               clipped prefix and carries no bonus;
+ *   value       V(i, t) = H(i, t) + B when i = n and H(i, t) > 0, else V(i, t) = H(i, t).  A cell of row n with H = 0 has V = 0:
+ *               the bonus never creates an empty alignment;
+ *   end cell    the existing cell with i >= 1 of the largest V; ties go to the smallest i, then the smallest t: on a tie the
+ *               clipped alignment wins over the one that reaches the read's end, as in BWA-MEM.  score is that V; 0 means
+ *               nothing aligned, as before;
+ *   walk back   unchanged: stop at H = 0 or at row 0, the same five trace bits, the same three states.  Reaching row 0 gives
+ *               readBegin = 0; an 'I' may now lead out of row 0, when B > o + e.
+ * THE SCORE IS THE OBJECTIVE THAT WAS MAXIMISED AND INCLUDES THE BONUSES.  The raw alignment score is
+ *   score - B * [readBegin == 0] - B * [readEnd == n],
+ * which a caller forms from the alignment call's outputs.  Slot scores, bestScores / secondScores, minScore, the duplicate rule
+ * and the mapping quality all work on V, and the two calls stay held to "a slot's score is what the alignment call reports for
+ * that slot".
+ *   bounds: H <= 2^16 * 127 + 2 * 255 < 2^24, so the end cell's key holds; the device's -2^30 is reset every row and never meets B.
+ *   INVARIANTS: the runs' read lengths sum to n, their text lengths to textEnd - textBegin; the script re-scored from the text
+ *   with the matrix and the gap costs, plus B per read end that is not clipped, equals score; the script neither begins nor ends
+ *   with 'D'; next to a clip the first / last aligned column has s > 0 and is no 'I'; next to an unclipped read end it may be
+ *   'X', a column with s <= 0, or 'I' -- also when it is the alignment's ONLY column and a clip follows it (readBegin = 0,
+ *   readEnd = 1 < n: the cell before it lies in row 0, which is no end cell, so B + s > 0 or B - o - e > 0 is all it needs;
+ *   minScore is the caller's guard against such an alignment); 0 <= textBegin <= textEnd <= L; the score never exceeds the unbanded value under the same
+ *   B and equals it when an optimal unbanded path lies inside the band.
+ * With B = 0 every output of the four calls equals the matrix sibling's.  Under a uniform matrix a substitution k characters from
+ * a read end (k matching characters behind it) is kept exactly when k * match + B > mismatch.  $AWFM_GPU_DIAG score_group /
+ * affine_group force G as for the siblings. */
+#define AWFM_END_BONUS_MAX 255u
+enum AwFmReturnCode awfmScoreChainsEndBonus(const struct AwFmVerifyInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t bandPad,
+                                            uint32_t maxDrift, const struct AwFmMatrixScoring *scoring, uint32_t endBonus, uint32_t minScore,
+                                            uint32_t mapqCap, const uint8_t *text, uint64_t length, const uint64_t *sequenceEnds,
+                                            uint64_t numRecords, enum AwFmAlphabetType alphabet, const struct AwFmSlotScoreOutputs *out,
+                                            unsigned threads);
+enum AwFmReturnCode awfmGpuScoreChainsEndBonus(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
+                                               uint32_t bandPad, uint32_t maxDrift, const struct AwFmMatrixScoring *scoring, uint32_t endBonus,
+                                               uint32_t minScore, uint32_t mapqCap, const struct AwFmSlotScoreOutputs *dOut, void *stream);
+enum AwFmReturnCode awfmAlignChainsEndBonus(const struct AwFmVerifyInputs *in, const uint32_t *slots, uint64_t numReads,
+                                            uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                            const struct AwFmMatrixScoring *scoring, uint32_t endBonus, uint32_t maxOps, const uint8_t *text,
+                                            uint64_t length, const uint64_t *sequenceEnds, uint64_t numRecords, enum AwFmAlphabetType alphabet,
+                                            const struct AwFmAffineOutputs *out, unsigned threads);
+enum AwFmReturnCode awfmGpuAlignChainsEndBonus(AwFmGpuIndex *g, const struct AwFmVerifyInputs *dIn, const uint32_t *dSlots, uint64_t numReads,
+                                               uint32_t maxCandidates, uint32_t bandPad, uint32_t maxDrift,
+                                               const struct AwFmMatrixScoring *scoring, uint32_t endBonus, uint32_t maxOps, uint32_t maxRows,
+                                               const struct AwFmAffineOutputs *dOut, void *dScratch, void *stream);
+
+/* ---- window scores:the full-width local affine alignment of a read against a text window the caller names, as a slot ----
  * The stage for reads WITHOUT a chain: a mate with a burst of errors, a read across a divergent stretch, a read shorter than a
  * seed, whose place the caller knows to within some hundred positions (from its mate, from an earlier pass).  No seeds, no
  * chain, no band: every cell of read x window.  The result is the score with its begin and end cell, and a chain slot that
