@@ -54,6 +54,7 @@ GPU_SYMBOLS = [
     "awfmPairMates", "awfmGpuPairMates", "awfmReverseComplementReads", "awfmGpuReverseComplementReads",
     "awfmInsertHistogram", "awfmGpuInsertHistogram", "awfmInsertInterval", "awfmGpuInsertInterval", "awfmGpuPairMatesEstimated",
     "awfmAlignmentStrings", "awfmGpuAlignmentStringsScratchBytes", "awfmGpuAlignmentStrings",
+    "awfmSamRecords", "awfmGpuSamRecordsScratchBytes", "awfmGpuSamRecords", "awfmRecordNames", "awfmSamHeader",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -200,6 +201,22 @@ class AwFmStringOutputs(C.Structure):
     """struct AwFmStringOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL, and the arenas' capacities"""
     _fields_ = [("cigarOffsets", C.c_void_p), ("cigarChars", C.c_void_p), ("cigarCapacity", C.c_uint64), ("mdOffsets", C.c_void_p),
                 ("mdChars", C.c_void_p), ("mdCapacity", C.c_uint64), ("numSkipped", C.c_void_p), ("numOverflow", C.c_void_p)]
+
+
+class AwFmSamInputs(C.Structure):
+    """struct AwFmSamInputs (include/awfm_gpu.h, "SAM records"): host or device addresses; the optional ones may be NULL"""
+    _fields_ = [("readChars", C.c_void_p), ("numReadChars", C.c_uint64), ("readOffsets", C.c_void_p), ("qualities", C.c_void_p),
+                ("nameOffsets", C.c_void_p), ("nameChars", C.c_void_p), ("recordNameOffsets", C.c_void_p), ("recordNameChars", C.c_void_p),
+                ("numRecordNames", C.c_uint32), ("sequences", C.c_void_p), ("slots", C.c_void_p), ("scores", C.c_void_p),
+                ("editDistances", C.c_void_p), ("textBegins", C.c_void_p), ("textEnds", C.c_void_p), ("cigarOffsets", C.c_void_p),
+                ("cigarChars", C.c_void_p), ("mdOffsets", C.c_void_p), ("mdChars", C.c_void_p), ("mappingQualities", C.c_void_p),
+                ("secondScores", C.c_void_p), ("baseFlags", C.c_void_p), ("properPairs", C.c_void_p)]
+
+
+class AwFmSamOutputs(C.Structure):
+    """struct AwFmSamOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL, and the arena's capacity"""
+    _fields_ = [("lineOffsets", C.c_void_p), ("lineChars", C.c_void_p), ("lineCapacity", C.c_uint64), ("numUnaligned", C.c_void_p),
+                ("numOverflow", C.c_void_p)]
 
 
 class AwFmIndex(C.Structure):
@@ -409,6 +426,11 @@ def lib():
         "awfmGpuAlignmentStringsScratchBytes": (u64, [vp, u64]),
         "awfmGpuAlignmentStrings": (C.c_int, [vp, C.POINTER(AwFmStringInputs), u64, C.c_uint32, C.c_uint32, C.c_uint32,
                                               C.POINTER(AwFmStringOutputs), vp, vp]),
+        "awfmSamRecords": (C.c_int, [C.POINTER(AwFmSamInputs), u64, C.c_uint32, C.c_uint32, C.POINTER(AwFmSamOutputs), C.c_uint]),
+        "awfmGpuSamRecordsScratchBytes": (u64, [vp, u64]),
+        "awfmGpuSamRecords": (C.c_int, [vp, C.POINTER(AwFmSamInputs), u64, C.c_uint32, C.c_uint32, C.POINTER(AwFmSamOutputs), vp, vp]),
+        "awfmRecordNames": (C.c_int, [IP, vp, vp, u64]),
+        "awfmSamHeader": (u64, [IP, vp, u64]),
         "awfmGpuInsertInterval": (C.c_int, [vp, vp, C.POINTER(AwFmInsertParams), vp, vp]),
         "awfmGpuPairMatesEstimated": (C.c_int, [vp, C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmPairParams), vp,
                                                 C.POINTER(AwFmPairOutputs), vp]),

@@ -814,6 +814,109 @@ def alignment_strings_host(sequences, slots, text_begins, num_ops, ops, text, se
     return result
 
 
+SAM_PAIRED = 1  # AWFM_SAM_PAIRED: reads 2p and 2p + 1 are mates
+# field name, element type, required; in the order of struct AwFmSamInputs (numReadChars and numRecordNames are numbers)
+SAM_INPUTS = (("readChars", np.uint8, True), ("readOffsets", np.uint64, True), ("qualities", np.uint8, False), ("nameOffsets", np.uint64, False),
+              ("nameChars", np.uint8, False), ("recordNameOffsets", np.uint64, True), ("recordNameChars", np.uint8, True),
+              ("sequences", np.uint32, True), ("slots", np.uint32, True), ("scores", np.uint32, True), ("editDistances", np.uint32, True),
+              ("textBegins", np.uint64, True), ("textEnds", np.uint64, True), ("cigarOffsets", np.uint64, True), ("cigarChars", np.uint8, True),
+              ("mdOffsets", np.uint64, False), ("mdChars", np.uint8, False), ("mappingQualities", np.uint8, False),
+              ("secondScores", np.uint32, False), ("baseFlags", np.uint16, False), ("properPairs", np.uint8, False))
+
+
+def sam_inputs(num_read_chars=0, num_record_names=0, **addresses):
+    """struct AwFmSamInputs (include/awfm_gpu.h, "SAM records") from addresses by field name, host or device, and the two numbers;
+    a field left out is NULL"""
+    sin = _lib.AwFmSamInputs()
+    sin.numReadChars, sin.numRecordNames = int(num_read_chars), int(num_record_names)
+    known = {name for name, _, _ in SAM_INPUTS}
+    for name, value in addresses.items():
+        if name not in known:
+            raise ValueError(f"no input called {name}")
+        setattr(sin, name, value or None)
+    return sin
+
+
+def sam_outputs(**addresses):
+    """struct AwFmSamOutputs from addresses by field name (lineOffsets, lineChars, numUnaligned, numOverflow) and lineCapacity; a
+    field left out is NULL or 0"""
+    out = _lib.AwFmSamOutputs()
+    for name, value in addresses.items():
+        if name not in dict(_lib.AwFmSamOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, int(value) if name == "lineCapacity" else (value or None))
+    return out
+
+
+def sam_records_host(arrays, max_candidates=None, paired=False, line_capacity=None, outputs=None, threads=4, fill=None, unaligned_before=0,
+                     overflow_before=0, flags=None, num_reads=None, num_record_names=None):
+    """awfmSamRecords (include/awfm_gpu.h, "SAM records"), the host twin: arrays is a dict by the field names of struct
+    AwFmSamInputs (SAM_INPUTS; sequences shaped (reads, max_candidates); an optional one left out or None is NULL) -> a dict of
+    lineOffsets (uint64, reads + 1), lineChars (a uint8 arena of the capacity given; None: exactly what the lines need, found by
+    a first call for the offsets), numUnaligned and numOverflow (ints: the values before plus this call's).  outputs: the names to
+    compute (None: all); the others are passed as NULL and left out.  fill: the value (per byte) the arrays hold before the
+    call."""
+    held = {}
+    for name, dtype, _ in SAM_INPUTS:
+        if arrays.get(name) is not None:
+            held[name] = np.ascontiguousarray(arrays[name], dtype=dtype)
+    n = (held["readOffsets"].size - 1 if "readOffsets" in held else 0) if num_reads is None else num_reads
+    C_ = (held["sequences"].shape[1] if "sequences" in held and held["sequences"].ndim == 2 else 1) if max_candidates is None else max_candidates
+    records = (held["recordNameOffsets"].size - 1 if "recordNameOffsets" in held else 0) if num_record_names is None else num_record_names
+    flags = (SAM_PAIRED if paired else 0) if flags is None else flags
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a.size else dummy.ctypes.data
+
+    sin = sam_inputs(held["readChars"].size if "readChars" in held else 0, records, **{name: address(a) for name, a in held.items()})
+    names = ["lineOffsets", "lineChars", "numUnaligned", "numOverflow"]
+    outputs = names if outputs is None else list(outputs)
+
+    def call(sout):
+        _check("awfmSamRecords", _lib.lib().awfmSamRecords(C.byref(sin), n, C_, flags, C.byref(sout), threads))
+
+    if line_capacity is None and "lineChars" in outputs:
+        sizing = np.zeros(n + 1, np.uint64)
+        call(sam_outputs(lineOffsets=sizing.ctypes.data))
+        line_capacity = int(sizing[n])
+    result = {}
+    for name, size, dtype in (("lineOffsets", n + 1, np.uint64), ("lineChars", line_capacity or 0, np.uint8)):
+        if name in outputs:
+            result[name] = np.zeros(size, dtype)
+            if fill is not None:
+                result[name].view(np.uint8)[...] = fill
+    counters = {"numUnaligned": np.array([unaligned_before], np.uint64), "numOverflow": np.array([overflow_before], np.uint64)}
+    sout = sam_outputs(lineCapacity=line_capacity or 0, **{name: address(a) for name, a in result.items()})
+    for name, counter in counters.items():
+        if name in outputs:
+            setattr(sout, name, counter.ctypes.data)
+    call(sout)
+    for name, counter in counters.items():
+        if name in outputs:
+            result[name] = int(counter[0])
+    return result
+
+
+def record_names(index):
+    """awfmRecordNames: the first whitespace-delimited token of every record's header -> (offsets uint64 [records + 1], chars
+    uint8), what sam_records takes as recordNameOffsets and recordNameChars"""
+    records = int(_lib.lib().awFmGetNumSequences(index.ptr))
+    offsets = np.zeros(records + 1, np.uint64)
+    _check("awfmRecordNames", _lib.lib().awfmRecordNames(index.ptr, offsets.ctypes.data, None, 0))
+    chars = np.zeros(max(int(offsets[records]), 1), np.uint8)
+    _check("awfmRecordNames", _lib.lib().awfmRecordNames(index.ptr, offsets.ctypes.data, chars.ctypes.data, int(offsets[records])))
+    return offsets, chars[:int(offsets[records])]
+
+
+def sam_header(index):
+    """awfmSamHeader: the @HD line and one @SQ line per record of the index, as bytes (empty without records)"""
+    size = int(_lib.lib().awfmSamHeader(index.ptr, None, 0))
+    out = np.zeros(max(size, 1), np.uint8)
+    _lib.lib().awfmSamHeader(index.ptr, out.ctypes.data, size)
+    return out[:size].tobytes()
+
+
 SCORE_MAX_MAPQ = 254  # AWFM_SCORE_MAX_MAPQ: upper limit of mapq_cap (255 is SAM's "unavailable")
 SCORE_SLOT_OUTPUTS = (("slotScores", np.uint32), ("slotReadEnds", np.uint32), ("slotTextEnds", np.uint64))
 SCORE_READ_OUTPUTS = (("bestSlots", np.uint32), ("bestScores", np.uint32), ("secondSlots", np.uint32), ("secondScores", np.uint32),
@@ -1451,6 +1554,21 @@ class GpuIndex:
         _check("awfmGpuAlignmentStrings",
                _lib.lib().awfmGpuAlignmentStrings(self.handle, None if inputs is None else C.byref(inputs), num_reads, max_candidates, max_ops,
                                                   flags, None if outputs is None else C.byref(outputs), d_scratch or None, stream or None))
+
+    # SAM records (include/awfm_gpu.h) ------------------------------------
+    def sam_records_scratch_bytes(self, num_reads):
+        """awfmGpuSamRecordsScratchBytes: the bytes of device scratch sam_records needs for num_reads reads"""
+        return int(_lib.lib().awfmGpuSamRecordsScratchBytes(self.handle, num_reads))
+
+    def sam_records(self, inputs, num_reads, outputs, d_scratch, max_candidates=4, paired=False, flags=None, stream=0):
+        """awfmGpuSamRecords: inputs sam_inputs(...) and outputs sam_outputs(...) of device addresses -- the arrays as the alignment,
+        string, score and pairing calls left them --, d_scratch sam_records_scratch_bytes(num_reads) bytes of device memory of this
+        call's own, aligned to 16 bytes; one SAM line per read, packed behind lineOffsets; asynchronous on `stream`; *numUnaligned
+        and *numOverflow are added to"""
+        flags = (SAM_PAIRED if paired else 0) if flags is None else flags
+        _check("awfmGpuSamRecords",
+               _lib.lib().awfmGpuSamRecords(self.handle, None if inputs is None else C.byref(inputs), num_reads, max_candidates, flags,
+                                            None if outputs is None else C.byref(outputs), d_scratch or None, stream or None))
 
     # slot scores and mapping quality (include/awfm_gpu.h) -----------------
     def score_chains_affine(self, inputs, num_reads, outputs, max_candidates=4, band_pad=8, max_drift=15, scoring=AFFINE_SCORING,

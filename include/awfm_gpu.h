@@ -95,6 +95,8 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *                       workgroup up to 8192 bins)
  *   strings_tier=direct     awfmGpuAlignmentStrings: every wave stores its strings read by read in bytes (default: a span that
  *                       fits the LDS tile is formatted there and stored in dwords)
+ *   sam_tier=direct         awfmGpuSamRecords: every wave stores its line straight into the arena (default: a line that fits the
+ *                       LDS tile is built there and stored in dwords)
  *   second_window=0|1   the lookup kernel's second table window (a survivor's leftmost characters): 0 never, 1 on every trip;
  *                       unset, the kernel's own gate decides trip by trip (the results are the same either way)
  *   stream_trace=1, aos_trace=1  host timelines of the chunked pipelines / the AoS lanes on stderr */
@@ -1381,6 +1383,115 @@ uint64_t awfmGpuAlignmentStringsScratchBytes(const AwFmGpuIndex *g, uint64_t num
 enum AwFmReturnCode awfmGpuAlignmentStrings(AwFmGpuIndex *g, const struct AwFmStringInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
                                             uint32_t maxOps, uint32_t flags, const struct AwFmStringOutputs *dOut, void *dScratch,
                                             void *stream);
+
+/* ---- SAM records: one SAM line per read, packed behind offsets, on host and device ----
+ * The step that closes the read path: reads in, SAM text out.  Every field is a function of arrays the earlier calls leave on
+ * the device -- the slot table, the alignment's scores and positions, the two string arenas, the mapping qualities and the
+ * proper-pair marks -- and of the reads and names the caller holds; neither the text nor the image's record table is read.  The
+ * host twin (csrc/awfm_sam.c) is the definition and the checker of the device call.
+ *
+ * INPUTS (struct AwFmSamInputs; C = maxCandidates 1..16).  Required: readChars, readOffsets [numReads + 1], sequences [numReads *
+ * C], slots, scores, editDistances, textBegins, textEnds [numReads], cigarOffsets [numReads + 1] and cigarChars; and, when
+ * numRecordNames != 0, recordNameOffsets [numRecordNames + 1] and recordNameChars (awfmRecordNames).  Pairs of offsets and
+ * arena that come together or not at all (one without the other: AwFmNullPtrError): nameOffsets [numReads + 1] / nameChars,
+ * mdOffsets [numReads + 1] / mdChars.  Optional, NULL allowed: qualities (numReadChars bytes parallel to readChars),
+ * mappingQualities, secondScores, baseFlags [numReads], properPairs [numReads / 2].  flags: 0 or AWFM_SAM_PAIRED (reads 2p and
+ * 2p + 1 are mates, the mate of r is m = r ^ 1; numReads must be even).  The call TRUSTS the strings and the names: bytes are
+ * copied as they are, offsets arrays are taken to ascend, and a line is taken to stay below 2^32 bytes.
+ *
+ * Per read r, with n = readOffsets[r + 1] - readOffsets[r], or 0 when those two are inverted:
+ *   ALIGNED    scores[r] != 0 and < AWFM_VERIFY_TOO_LONG, slots[r] < C, s = sequences[r * C + slots[r]] < numRecordNames, and the
+ *              read offsets are not inverted.  Otherwise UNALIGNED, counted in *numUnaligned.
+ *   The line is these fields joined by tabs and ended by '\n'; integers are decimal without leading zeros:
+ *     QNAME    the bytes nameChars[nameOffsets[r] .. nameOffsets[r + 1]); without names the decimal of r, of r / 2 when paired.
+ *     FLAG     baseFlags[r] (NULL: 0), | 0x4 when unaligned; paired also | 0x1, | 0x40 (even r) or | 0x80 (odd r), | 0x2 when
+ *              properPairs[r / 2] != 0 and both mates are aligned, | 0x8 when the mate is unaligned, | 0x20 when baseFlags[m] has
+ *              0x10.
+ *     RNAME POS  aligned: record s's name (recordNameChars[recordNameOffsets[s] .. [s + 1])) and textBegins[r] + 1; unaligned
+ *              with an aligned mate: the mate's two; otherwise `*` and 0.
+ *     MAPQ     aligned: mappingQualities[r] (NULL: 255); unaligned: 0.
+ *     CIGAR    aligned: the bytes cigarChars[cigarOffsets[r] .. cigarOffsets[r + 1]), `*` when there are none; unaligned: `*`.
+ *     RNEXT PNEXT  unpaired, or the mate is unaligned: `*` and 0; otherwise `=` when this line's RNAME is the mate's record, else
+ *              the mate's record's name; then textBegins[m] + 1.
+ *     TLEN     both mates aligned in the same record: with b the smaller of the two textBegins and e the larger of the two
+ *              textEnds, the mate with the smaller textBegins (a tie: the even read) gets e - b, the other -(e - b), in 64-bit
+ *              two's complement; else 0.
+ *     SEQ      the n read bytes, `*` when n == 0.   QUAL  the n parallel bytes of qualities; `*` without them or when n == 0.
+ *     tags, for an aligned read only, in this order: NM:i:editDistances[r], AS:i:scores[r], XS:i:secondScores[r] when that
+ *              array is given, MD:Z: and the bytes mdChars[mdOffsets[r] .. mdOffsets[r + 1]) when the pair is given and there
+ *              are any.
+ *
+ * OUTPUTS (struct AwFmSamOutputs; every pointer may be NULL): lineOffsets [numReads + 1] are the exclusive prefix sums of the
+ * TRUE line lengths whatever lineCapacity is; lineChars is an arena of lineCapacity bytes.  An arena without its offsets:
+ * AwFmNullPtrError; offsets without an arena size one.  With an arena, a line is written exactly when lineOffsets[r + 1] <=
+ * lineCapacity and otherwise counted in *numOverflow; no byte beyond min(total, capacity) is written, nor any byte of a line
+ * that does not fit.  Both counters are ADDED to.  numReads == 0 succeeds and touches nothing.
+ *
+ * Refusals, in this order: a missing required array, half a pair, an arena without its offsets: AwFmNullPtrError; C outside
+ * 1..16, another flag bit, odd numReads with AWFM_SAM_PAIRED, numReads >= 2^32: AwFmIllegalPositionError.
+ *
+ * awfmSamRecords (csrc/awfm_sam.c): over `threads` threads of the pool; ONE formatter counts and writes.
+ * awfmGpuSamRecords (csrc/awfm_sam_kernel.h): every pointer is a device pointer of the caller's; asynchronous on `stream`, no
+ * host wait, no allocation.  A lengths kernel (a thread per read), the library's on-device scan, and a write kernel: a WAVE
+ * per read, whose lanes each own one field -- they compute the fields' places by a prefix sum over the lanes and the decimal
+ * digits in registers --, while the reads, names and strings are copied by all lanes; the line is staged in LDS and stored in
+ * whole dwords, bytes only at its two edges; a line beyond the LDS tile goes out in lane-consecutive bytes ($AWFM_GPU_DIAG
+ * sam_tier=direct: every line; tests, the result is the same).  dScratch: awfmGpuSamRecordsScratchBytes(g, numReads) bytes,
+ * 16-byte aligned (AwFmIllegalPositionError otherwise; NULL: AwFmNullPtrError), this call's own until it has finished -- two
+ * streams may run the call at once with a dScratch each.
+ *
+ * awfmRecordNames (host only): the first whitespace-delimited token of every record's header (the whole header when it has no
+ * whitespace; an index without a FASTA trailer: AwFmUnsupportedVersionError), packed behind offsets [numRecords + 1] (required);
+ * chars == NULL sizes the arena, otherwise the names that fit `capacity` whole are written (offsets[i + 1] <= capacity).
+ * awfmSamHeader (host only): "@HD\tVN:1.6\tSO:unknown\n" and one "@SQ\tSN:<that token>\tLN:<the record's length>\n" per
+ * record; returns the header's true length; out == NULL sizes it, otherwise the lines that fit `capacity` whole are written;
+ * 0 for an index without records.
+ * Out of scope: BAM bytes, header lines on the device, reversing SEQ or QUAL for reads the caller reverse-complemented,
+ * supplementary records, other optional tags; how pairing defines templateLengths is untouched (TLEN here is the SAM one). */
+#define AWFM_SAM_PAIRED 1u /* flags: reads 2p and 2p + 1 are mates; numReads must be even */
+struct AwFmSamInputs {
+  /* reads */
+  const uint8_t *readChars;
+  uint64_t numReadChars;
+  const uint64_t *readOffsets; /* [numReads + 1] */
+  const uint8_t *qualities;    /* NULL, or numReadChars bytes parallel to readChars, printed as they are */
+  const uint64_t *nameOffsets; /* [numReads + 1]; with nameChars, or both NULL: QNAME is a decimal number */
+  const uint8_t *nameChars;
+  /* records */
+  const uint64_t *recordNameOffsets; /* [numRecordNames + 1] */
+  const uint8_t *recordNameChars;
+  uint32_t numRecordNames;
+  /* the alignment, as the alignment and string calls left it */
+  const uint32_t *sequences;     /* [numReads * maxCandidates]  the slot table's */
+  const uint32_t *slots;         /* [numReads] */
+  const uint32_t *scores;        /* [numReads] */
+  const uint32_t *editDistances; /* [numReads] */
+  const uint64_t *textBegins;    /* [numReads]  sequence-local */
+  const uint64_t *textEnds;      /* [numReads]  sequence-local */
+  const uint64_t *cigarOffsets;  /* [numReads + 1]  awfmGpuAlignmentStrings' outputs, complete arenas */
+  const uint8_t *cigarChars;
+  const uint64_t *mdOffsets; /* [numReads + 1]; with mdChars, or both NULL: no MD tag */
+  const uint8_t *mdChars;
+  /* optional, NULL allowed */
+  const uint8_t *mappingQualities; /* [numReads]; NULL: 255 */
+  const uint32_t *secondScores;    /* [numReads]; NULL: no XS tag */
+  const uint16_t *baseFlags;       /* [numReads]; the caller's bits (0x10 strand, 0x100 secondary, ...); NULL: 0 */
+  const uint8_t *properPairs;      /* [numReads / 2]; read only with AWFM_SAM_PAIRED; NULL: no pair is proper */
+};
+struct AwFmSamOutputs {
+  uint64_t *lineOffsets; /* [numReads + 1] */
+  uint8_t *lineChars;    /* lineCapacity bytes */
+  uint64_t lineCapacity;
+  uint64_t *numUnaligned; /* one counter, added to */
+  uint64_t *numOverflow;  /* one counter, added to */
+};
+enum AwFmReturnCode awfmSamRecords(const struct AwFmSamInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t flags,
+                                   const struct AwFmSamOutputs *out, unsigned threads);
+uint64_t awfmGpuSamRecordsScratchBytes(const AwFmGpuIndex *g, uint64_t numReads);
+enum AwFmReturnCode awfmGpuSamRecords(AwFmGpuIndex *g, const struct AwFmSamInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
+                                      uint32_t flags, const struct AwFmSamOutputs *dOut, void *dScratch, void *stream);
+enum AwFmReturnCode awfmRecordNames(const struct AwFmIndex *index, uint64_t *offsets, uint8_t *chars, uint64_t capacity);
+uint64_t awfmSamHeader(const struct AwFmIndex *index, uint8_t *out, uint64_t capacity);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
