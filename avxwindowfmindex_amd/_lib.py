@@ -55,6 +55,7 @@ GPU_SYMBOLS = [
     "awfmInsertHistogram", "awfmGpuInsertHistogram", "awfmInsertInterval", "awfmGpuInsertInterval", "awfmGpuPairMatesEstimated",
     "awfmAlignmentStrings", "awfmGpuAlignmentStringsScratchBytes", "awfmGpuAlignmentStrings",
     "awfmSamRecords", "awfmGpuSamRecordsScratchBytes", "awfmGpuSamRecords", "awfmRecordNames", "awfmSamHeader",
+    "awfmChooseStrands", "awfmGpuChooseStrands", "awfmOrientReads", "awfmGpuOrientReads",
     "awfmGpuOrderBuckets", "awfmGpuOrderKmers", "awfmGpuSearchOrderedRecords", "awfmGpuSearchOrderedRecordsCounts", "awfmGpuSearchGeneralRecords", "awfmGpuMergeBucketRuns",
 ]
 # int sink(void *user, uint64 firstKmer, uint64 numKmers, const uint32 *counts, const uint64 *positions, uint64 numPositions)
@@ -211,6 +212,35 @@ class AwFmSamInputs(C.Structure):
                 ("editDistances", C.c_void_p), ("textBegins", C.c_void_p), ("textEnds", C.c_void_p), ("cigarOffsets", C.c_void_p),
                 ("cigarChars", C.c_void_p), ("mdOffsets", C.c_void_p), ("mdChars", C.c_void_p), ("mappingQualities", C.c_void_p),
                 ("secondScores", C.c_void_p), ("baseFlags", C.c_void_p), ("properPairs", C.c_void_p)]
+
+
+class AwFmStrandInputs(C.Structure):
+    """struct AwFmStrandInputs (include/awfm_gpu.h, "strands"): host or device addresses of the 2R rows"""
+    _fields_ = [("readOffsets", C.c_void_p), ("sequences", C.c_void_p), ("slotScores", C.c_void_p), ("slotReadEnds", C.c_void_p),
+                ("slotTextEnds", C.c_void_p)]
+
+
+class AwFmStrandOutputs(C.Structure):
+    """struct AwFmStrandOutputs (include/awfm_gpu.h): host or device addresses, each may be NULL"""
+    _fields_ = [("strands", C.c_void_p), ("strandSlots", C.c_void_p), ("bestScores", C.c_void_p), ("secondScores", C.c_void_p),
+                ("mappingQualities", C.c_void_p), ("baseFlags", C.c_void_p), ("rowSlots", C.c_void_p), ("windowSequences", C.c_void_p),
+                ("windowBegins", C.c_void_p), ("windowEnds", C.c_void_p), ("properPairs", C.c_void_p), ("pairScores", C.c_void_p),
+                ("pairSecondScores", C.c_void_p), ("templateLengths", C.c_void_p), ("pairQualities", C.c_void_p), ("numReverse", C.c_void_p),
+                ("numProper", C.c_void_p), ("numWindows", C.c_void_p), ("numMalformed", C.c_void_p)]
+
+
+class AwFmOrientInputs(C.Structure):
+    """struct AwFmOrientInputs (include/awfm_gpu.h, "strands"): the 2R rows, the optional score columns and qualities, the strands"""
+    _fields_ = [("rows", AwFmVerifyInputs), ("slotScores", C.c_void_p), ("slotReadEnds", C.c_void_p), ("slotTextEnds", C.c_void_p),
+                ("qualities", C.c_void_p), ("strands", C.c_void_p)]
+
+
+class AwFmOrientOutputs(C.Structure):
+    """struct AwFmOrientOutputs (include/awfm_gpu.h): host or device addresses; a column is given exactly when its input is"""
+    _fields_ = [("readChars", C.c_void_p), ("capacity", C.c_uint64), ("readOffsets", C.c_void_p), ("qualities", C.c_void_p),
+                ("sequences", C.c_void_p), ("chainAnchors", C.c_void_p), ("chainReadBegins", C.c_void_p), ("chainReadEnds", C.c_void_p),
+                ("chainBeginDiagonals", C.c_void_p), ("chainEndDiagonals", C.c_void_p), ("slotScores", C.c_void_p),
+                ("slotReadEnds", C.c_void_p), ("slotTextEnds", C.c_void_p), ("numMalformed", C.c_void_p)]
 
 
 class AwFmSamOutputs(C.Structure):
@@ -430,6 +460,12 @@ def lib():
         "awfmGpuSamRecordsScratchBytes": (u64, [vp, u64]),
         "awfmGpuSamRecords": (C.c_int, [vp, C.POINTER(AwFmSamInputs), u64, C.c_uint32, C.c_uint32, C.POINTER(AwFmSamOutputs), vp, vp]),
         "awfmRecordNames": (C.c_int, [IP, vp, vp, u64]),
+        "awfmChooseStrands": (C.c_int, [C.POINTER(AwFmStrandInputs), u64, C.c_uint32, C.c_uint32, C.POINTER(AwFmPairParams),
+                                        C.POINTER(AwFmStrandOutputs), C.c_uint]),
+        "awfmGpuChooseStrands": (C.c_int, [vp, C.POINTER(AwFmStrandInputs), u64, C.c_uint32, C.c_uint32, C.POINTER(AwFmPairParams),
+                                           C.POINTER(AwFmStrandOutputs), vp]),
+        "awfmOrientReads": (C.c_int, [C.POINTER(AwFmOrientInputs), u64, C.c_uint32, C.POINTER(AwFmOrientOutputs), C.c_uint]),
+        "awfmGpuOrientReads": (C.c_int, [vp, C.POINTER(AwFmOrientInputs), u64, C.c_uint32, C.POINTER(AwFmOrientOutputs), vp]),
         "awfmSamHeader": (u64, [IP, vp, u64]),
         "awfmGpuInsertInterval": (C.c_int, [vp, vp, C.POINTER(AwFmInsertParams), vp, vp]),
         "awfmGpuPairMatesEstimated": (C.c_int, [vp, C.POINTER(AwFmPairInputs), u64, C.c_uint32, C.POINTER(AwFmPairParams), vp,

@@ -1185,6 +1185,156 @@ def reverse_complement_reads_host(read_chars, read_offsets, which=COMPLEMENT_ODD
     return out, int(counter[0])
 
 
+STRANDS_PAIRED = 1  # AWFM_STRANDS_PAIRED: reads 2p and 2p + 1 are mates from opposite strands
+STRAND_READ_OUTPUTS = (("strands", np.uint8), ("strandSlots", np.uint32), ("bestScores", np.uint32), ("secondScores", np.uint32),
+                       ("mappingQualities", np.uint8), ("baseFlags", np.uint16))
+STRAND_ROW_OUTPUTS = (("rowSlots", np.uint32), ("windowSequences", np.uint32), ("windowBegins", np.uint64), ("windowEnds", np.uint64))
+STRAND_PAIR_OUTPUTS = PAIR_PAIR_OUTPUTS
+STRAND_COUNTERS = ("numReverse", "numProper", "numWindows", "numMalformed")
+ORIENT_SCORE_COLUMNS = (("slotScores", np.uint32), ("slotReadEnds", np.uint32), ("slotTextEnds", np.uint64))
+
+
+def strand_inputs(read_offsets, sequences, slot_scores, slot_read_ends, slot_text_ends):
+    """struct AwFmStrandInputs from addresses: the offsets of the 2R rows, the slot table's sequences and the three per-slot arrays
+    slot scores wrote"""
+    return _lib.AwFmStrandInputs(read_offsets or None, sequences or None, slot_scores or None, slot_read_ends or None, slot_text_ends or None)
+
+
+def strand_outputs(**addresses):
+    """struct AwFmStrandOutputs from addresses by field name (strands, strandSlots, bestScores, secondScores, mappingQualities,
+    baseFlags per read; rowSlots, windowSequences, windowBegins, windowEnds per row; properPairs, pairScores, pairSecondScores,
+    templateLengths, pairQualities per pair; numReverse, numProper, numWindows, numMalformed); a field left out is NULL"""
+    out = _lib.AwFmStrandOutputs()
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmStrandOutputs._fields_):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def orient_inputs(rows, strands, qualities=0, **score_addresses):
+    """struct AwFmOrientInputs from addresses: rows, a verify_inputs(...) of the 2R rows (slot columns left out are NULL), strands
+    [R], the qualities parallel to the read buffer (0: NULL) and slotScores, slotReadEnds, slotTextEnds by field name"""
+    oin = _lib.AwFmOrientInputs()
+    oin.rows = rows
+    oin.strands = strands or None
+    oin.qualities = qualities or None
+    for name, address in score_addresses.items():
+        if name not in dict(ORIENT_SCORE_COLUMNS):
+            raise ValueError(f"no score column called {name}")
+        setattr(oin, name, address or None)
+    return oin
+
+
+def orient_outputs(read_chars, capacity, read_offsets, **addresses):
+    """struct AwFmOrientOutputs from addresses: the output read buffer, its capacity, readOffsets [R + 1], and by field name
+    qualities, the six slot columns, the three score columns and numMalformed; a field left out is NULL"""
+    out = _lib.AwFmOrientOutputs(read_chars or None, capacity, read_offsets or None)
+    for name, address in addresses.items():
+        if name not in dict(_lib.AwFmOrientOutputs._fields_) or name in ("readChars", "capacity", "readOffsets"):
+            raise ValueError(f"no output called {name}")
+        setattr(out, name, address or None)
+    return out
+
+
+def choose_strands_host(read_offsets, slots, paired=False, min_insert=0, max_insert=0, min_score=0, unpaired_penalty=0, window_pad=0,
+                        mapq_cap=60, threads=4, outputs=None, fill=None, before=None, max_candidates=None, flags=None):
+    """awfmChooseStrands (include/awfm_gpu.h, "strands"), the host twin: read_offsets [2R + 1] of the rows -- the reads as
+    sequenced, then their reverse complements --; slots: a dict of sequences, slotScores, slotReadEnds, slotTextEnds shaped (2R,
+    max_candidates) as the slot score calls return them on the 2R rows -> a dict of strands, strandSlots, bestScores, secondScores,
+    mappingQualities, baseFlags per read, rowSlots, windowSequences, windowBegins, windowEnds per row, (paired only) properPairs,
+    pairScores, pairSecondScores, templateLengths, pairQualities per pair, and the counters numReverse, numProper, numWindows,
+    numMalformed (ints: the values `before`, a dict, plus this call's).  outputs: the names to compute (None: all); the others are
+    passed as NULL and left out.  fill: the value (per byte) the arrays hold before the call.  flags: what the call is told
+    instead of `paired`."""
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    rows = max(o.size - 1, 0)
+    if rows % 2:
+        raise ValueError("the rows are the reads and their reverse complements: an even number")
+    n = rows // 2
+    arrays = {name: np.ascontiguousarray(slots[name], dtype=dtype) for name, dtype in PAIR_SLOT_INPUTS}
+    shape = arrays["sequences"].shape
+    if len(shape) != 2 or shape[0] != rows or any(a.shape != shape for a in arrays.values()):
+        raise ValueError("the slot arrays are shaped (rows, max_candidates)")
+    pair_outputs_ = STRAND_PAIR_OUTPUTS if paired else ()
+    names = [name for name, _ in STRAND_READ_OUTPUTS + STRAND_ROW_OUTPUTS + pair_outputs_] + list(STRAND_COUNTERS)
+    outputs = names if outputs is None else list(outputs)
+    result = {name: np.zeros(n, dtype) for name, dtype in STRAND_READ_OUTPUTS if name in outputs}
+    result.update({name: np.zeros(rows, dtype) for name, dtype in STRAND_ROW_OUTPUTS if name in outputs})
+    result.update({name: np.zeros(n // 2, dtype) for name, dtype in pair_outputs_ if name in outputs})
+    for a in result.values():
+        if fill is not None:
+            a.view(np.uint8)[...] = fill
+    counters = {name: np.array([(before or {}).get(name, 0)], np.uint64) for name in STRAND_COUNTERS}
+    dummy = np.zeros(1, np.uint64)  # what an empty array points to: alive until the call has returned
+
+    def address(a):
+        return a.ctypes.data if a.size else dummy.ctypes.data
+
+    sin = strand_inputs(address(o), *(address(arrays[name]) for name, _ in PAIR_SLOT_INPUTS))
+    sout = strand_outputs(**{name: address(a) for name, a in result.items()})
+    for name, counter in counters.items():
+        if name in outputs:
+            setattr(sout, name, counter.ctypes.data)
+    params = pair_params(min_insert, max_insert, min_score, unpaired_penalty, window_pad, mapq_cap)
+    rc = _lib.lib().awfmChooseStrands(C.byref(sin), n, shape[1] if max_candidates is None else max_candidates,
+                                      (STRANDS_PAIRED if paired else 0) if flags is None else flags, C.byref(params), C.byref(sout), threads)
+    _check("awfmChooseStrands", rc)
+    for name, counter in counters.items():
+        if name in outputs:
+            result[name] = int(counter[0])
+    return result
+
+
+def orient_reads_host(read_chars, read_offsets, strands, slots=None, qualities=None, capacity=None, threads=4, fill=0, malformed_before=0,
+                      num_read_chars=None, max_candidates=None):
+    """awfmOrientReads (include/awfm_gpu.h, "strands"), the host twin: read_chars and read_offsets [2R + 1] of the 2R rows, strands
+    [R]; slots: a dict of any of the six slot columns and slotScores, slotReadEnds, slotTextEnds, shaped (2R, max_candidates);
+    qualities parallel to read_chars -> a dict of readChars (uint8[capacity]; None: what the reads need), readOffsets [R + 1],
+    qualities and the given columns shaped (R, max_candidates), and numMalformed.  fill: what the outputs hold before the call."""
+    chars = np.frombuffer(read_chars, np.uint8) if isinstance(read_chars, (bytes, bytearray)) else np.ascontiguousarray(read_chars, dtype=np.uint8)
+    o = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    rows = max(o.size - 1, 0)
+    if rows % 2:
+        raise ValueError("the rows are the reads and their reverse complements: an even number")
+    n = rows // 2
+    s = np.ascontiguousarray(strands, dtype=np.uint8)
+    if s.shape != (n,):
+        raise ValueError("strands is shaped (reads,)")
+    quals = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8)
+    if capacity is None:
+        capacity = int(o[n] - o[0]) if n and o[n] >= o[0] else 0
+    dtypes = dict(VERIFY_SLOT_INPUTS + ORIENT_SCORE_COLUMNS)
+    columns = {name: np.ascontiguousarray(a, dtype=dtypes[name]) for name, a in (slots or {}).items()}
+    widths = {a.shape[1] for a in columns.values() if a.ndim == 2}
+    if any(a.ndim != 2 or a.shape[0] != rows for a in columns.values()) or len(widths) > 1:
+        raise ValueError("the slot columns are shaped (rows, max_candidates)")
+    width = max_candidates if max_candidates is not None else widths.pop() if widths else 1
+    result = {"readChars": np.full(capacity, fill, np.uint8), "readOffsets": np.zeros(n + 1, np.uint64)}
+    if quals is not None:
+        result["qualities"] = np.full(capacity, fill, np.uint8)
+    for name, a in columns.items():
+        result[name] = np.zeros((n, width), a.dtype)
+        result[name].view(np.uint8)[...] = fill
+    counter = np.array([malformed_before], np.uint64)
+    dummy = np.zeros(2, np.uint64)
+
+    def address(a):
+        return a.ctypes.data if a.size else dummy.ctypes.data
+
+    rows_in = verify_inputs(address(chars), chars.size if num_read_chars is None else num_read_chars, address(o),
+                            **{name: address(a) for name, a in columns.items() if name in dict(VERIFY_SLOT_INPUTS)})
+    oin = orient_inputs(rows_in, address(s), 0 if quals is None else address(quals),
+                        **{name: address(a) for name, a in columns.items() if name in dict(ORIENT_SCORE_COLUMNS)})
+    oout = orient_outputs(result["readChars"].ctypes.data if capacity else dummy.ctypes.data + 8, capacity, address(result["readOffsets"]),
+                          numMalformed=counter.ctypes.data,
+                          **{name: (a.ctypes.data if a.size else dummy.ctypes.data + 8) for name, a in result.items()
+                             if name not in ("readChars", "readOffsets")})
+    _check("awfmOrientReads", _lib.lib().awfmOrientReads(C.byref(oin), n, width, C.byref(oout), threads))
+    result["numMalformed"] = int(counter[0])
+    return result
+
+
 INSERT_MAX_BINS, INSERT_MAX_SPREAD = 65536, 16  # AWFM_INSERT_MAX_BINS, AWFM_INSERT_MAX_SPREAD
 INSERT_ESTIMATE_FIELDS = ("minInsert", "maxInsert", "quartiles", "mean", "numSamples", "valid")
 
@@ -1648,6 +1798,27 @@ class GpuIndex:
         _check("awfmGpuReverseComplementReads",
                _lib.lib().awfmGpuReverseComplementReads(self.handle, d_read_chars or None, num_read_chars, d_read_offsets or None, num_reads,
                                                         which, d_out or None, d_num_malformed or None, stream or None))
+
+    # strands (include/awfm_gpu.h) -----------------------------------------
+    def choose_strands(self, inputs, num_reads, outputs, paired=False, min_insert=0, max_insert=0, max_candidates=4, min_score=0,
+                       unpaired_penalty=0, window_pad=0, mapq_cap=60, stream=0, flags=None):
+        """awfmGpuChooseStrands: inputs strand_inputs(...) of the 2 num_reads rows (the reads as sequenced, then their reverse
+        complements) and outputs strand_outputs(...) of device addresses; per read the strand and slot among its 2 max_candidates
+        strand slots, best and second score and the mapping quality; paired (reads 2p and 2p + 1 are mates from opposite strands)
+        also the pairing of pair_mates in both orientations and the rescue windows by row (what window_inputs takes on the
+        2 num_reads rows); one launch, no scratch, asynchronous on `stream`; the counters are added to"""
+        params = pair_params(min_insert, max_insert, min_score, unpaired_penalty, window_pad, mapq_cap)
+        _check("awfmGpuChooseStrands",
+               _lib.lib().awfmGpuChooseStrands(self.handle, C.byref(inputs), num_reads, max_candidates,
+                                               (STRANDS_PAIRED if paired else 0) if flags is None else flags, C.byref(params),
+                                               C.byref(outputs), stream or None))
+
+    def orient_reads(self, inputs, num_reads, outputs, max_candidates=4, stream=0):
+        """awfmGpuOrientReads: inputs orient_inputs(...) of the 2 num_reads rows and outputs orient_outputs(...) of device
+        addresses; the chosen strand of every read -- characters, qualities (reversed on strand 1) and slot columns -- gathered
+        into a batch of num_reads rows; one launch, asynchronous on `stream`; *numMalformed is added to"""
+        _check("awfmGpuOrientReads",
+               _lib.lib().awfmGpuOrientReads(self.handle, C.byref(inputs), num_reads, max_candidates, C.byref(outputs), stream or None))
 
     def locate_host_local(self, chars, offsets=None, fixed_length=0):
         """awfmGpuLocateHostLocal -> (ranges, hit offsets, sequence numbers uint32[total], local positions uint64[total],

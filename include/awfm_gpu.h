@@ -91,6 +91,7 @@ enum AwFmReturnCode awfmGpuLastBatchStatus(void);
  *                       same way
  *   window_q=4|8|12         awfmGpuScoreWindowsAffine: columns per lane for every read (narrower column blocks)
  *   pair_group=64           awfmGpuPairMates: a wave per pair also where 16 lanes hold the candidates
+ *   strand_group=64         awfmGpuChooseStrands: a wave per pair or per read also where 32 or 16 lanes hold the strand slots
  *   insert_tier=global      awfmGpuInsertHistogram: global atomics at any bin count (default: a private histogram in LDS per
  *                       workgroup up to 8192 bins)
  *   strings_tier=direct     awfmGpuAlignmentStrings: every wave stores its strings read by read in bytes (default: a span that
@@ -1121,7 +1122,7 @@ enum AwFmReturnCode awfmGpuScoreWindowsAffine(AwFmGpuIndex *g, const struct AwFm
  * The stage for PAIRED reads, between slot scores and affine alignment: reads 2p (mate A) and 2p + 1 (mate B) are a pair, both
  * GIVEN ON THE SAME STRAND.  For the usual inward-facing library the caller reverse-complements mate 2 where the reads lie
  * (awfmGpuReverseComplementReads, below) and a two-strand index finds fragments of either strand, each in its own record; with a
- * one-strand index the caller submits (m1, rc m2) and (m2, rc m1) and compares pairScores itself.  The call knows no strands:
+ * one-strand index "strands" below searches every read on both strands and pairs in both orientations.  This call knows no strands:
  * minInsert and maxInsert are signed, so other library geometries are a matter of sign and of which mate is complemented.  They
  * are the caller's here; a caller who does not know the library's insert distribution takes them from "insert size" below, which
  * estimates the interval from the batch's confidently placed pairs and hands it to awfmGpuPairMatesEstimated in device memory.
@@ -1446,8 +1447,9 @@ enum AwFmReturnCode awfmGpuAlignmentStrings(AwFmGpuIndex *g, const struct AwFmSt
  * awfmSamHeader (host only): "@HD\tVN:1.6\tSO:unknown\n" and one "@SQ\tSN:<that token>\tLN:<the record's length>\n" per
  * record; returns the header's true length; out == NULL sizes it, otherwise the lines that fit `capacity` whole are written;
  * 0 for an index without records.
- * Out of scope: BAM bytes, header lines on the device, reversing SEQ or QUAL for reads the caller reverse-complemented,
- * supplementary records, other optional tags; how pairing defines templateLengths is untouched (TLEN here is the SAM one). */
+ * Out of scope: BAM bytes, header lines on the device, reversing SEQ or QUAL inside this call ("strands" below: awfmGpuOrientReads
+ * hands over the chosen strand's bytes with the qualities reversed, awfmGpuChooseStrands writes baseFlags), supplementary
+ * records, other optional tags; how pairing defines templateLengths is untouched (TLEN here is the SAM one). */
 #define AWFM_SAM_PAIRED 1u /* flags: reads 2p and 2p + 1 are mates; numReads must be even */
 struct AwFmSamInputs {
   /* reads */
@@ -1492,6 +1494,160 @@ enum AwFmReturnCode awfmGpuSamRecords(AwFmGpuIndex *g, const struct AwFmSamInput
                                       uint32_t flags, const struct AwFmSamOutputs *dOut, void *dScratch, void *stream);
 enum AwFmReturnCode awfmRecordNames(const struct AwFmIndex *index, uint64_t *offsets, uint8_t *chars, uint64_t capacity);
 uint64_t awfmSamHeader(const struct AwFmIndex *index, uint8_t *out, uint64_t capacity);
+
+/* ---- strands: both strands of the reads on a one-strand index: choose, pair and orient ----
+ * The stage that lets an index of ONE strand place reads of either: the caller searches every read twice, as sequenced and
+ * reverse-complemented, and these two calls choose per read (or per pair) the strand and slot, name the rescue windows on the
+ * right strand, and gather the chosen strand of every read into a batch on which affine alignment, alignment strings and SAM
+ * records run as they are.  The host twins (csrc/awfm_strands.c) are the definition and the checkers of the device calls.
+ *
+ * LAYOUT.  ONE batch of 2R rows: rows [0, R) are the reads as sequenced (row F(r) = r), rows [R, 2R) their reverse
+ * complements (row V(r) = R + r), made by awfmGpuReverseComplementReads(..., AWFM_COMPLEMENT_ALL) into the second half of the
+ * buffer.  Seeds, candidates, chains and slot scores (affine, matrix or end bonus) run on the 2R rows as they are.  With C =
+ * maxCandidates (1..16), read r has 2C STRAND SLOTS u = sigma * C + j: slot j of row r + sigma * R, sigma = 0 as sequenced,
+ * sigma = 1 the reverse strand.
+ *
+ * awfmChooseStrands / awfmGpuChooseStrands.  Inputs (struct AwFmStrandInputs): readOffsets [2R + 1]; sequences, slotScores,
+ * slotReadEnds, slotTextEnds [2R * C] exactly as slot scores left them.  flags: 0, or AWFM_STRANDS_PAIRED: reads 2p and 2p + 1
+ * are mates (R even) that come from OPPOSITE strands of one fragment -- FR and RF libraries, told apart by the sign of the
+ * interval; same-strand libraries are out of scope.  params is pair mates' struct; unpaired, only minScore and mapqCap are read.
+ * n_r = readOffsets[r + 1] - readOffsets[r] is the length of read r (64-bit two's complement).  A read is MALFORMED when the
+ * offsets of F(r) or of V(r) are inverted or the two lengths differ: none of its strand slots counts, and it is counted in
+ * *numMalformed.  All sums of positions are 64-bit two's complement, values and qualities 64-bit, as in "pair mates".
+ *
+ * Per read r, in both modes:
+ *   1. a strand slot COUNTS by slot scores' rule 1: its score is none of the status values and is >= max(minScore, 1).
+ *   2. BEST(r) is the counting strand slot of the largest score, ties to the lowest u: the forward strand first, then the lowest
+ *      slot.  bestScores[r] is its score, 0 without one.
+ *   3. a counting strand slot DUPLICATES another when both lie on ONE strand, name one sequence and have one (readEnd, textEnd).
+ *      Strand slots on different strands are never duplicates: a palindromic read placed equally on both strands has a second
+ *      as good as its best and gets quality 0.
+ *   4. SECOND(r) is the largest-scoring counting strand slot that is neither the best nor its duplicate; secondScores[r] is its
+ *      score, 0 without one (what XS:i wants).
+ *   5. q_r = 0 without a best, else floor(mapqCap * (best - second) / best).
+ * UNPAIRED: the chosen strand slot is the best; mappingQualities[r] = q_r.
+ * PAIRED, per pair p (m1 = 2p, m2 = 2p + 1).  A CANDIDATE is (u1 of m1, u2 of m2), both counting.
+ *   6. it is CONCORDANT when the two lie on different strands, name one sequence and minInsert <= T <= maxInsert, where A is the
+ *      one on strand 0, B the one on strand 1, S = (int64) textEnd - readEnd and T = S(B) + n_B - S(A), n_B the length of B's
+ *      read.  Its value is the sum of the two scores.
+ *   7. the DISCORDANT candidate is (best(m1), best(m2)); it exists when both reads have a best and that pair is not concordant
+ *      (two bests on one strand never are).  Its value is max(0, sum - unpairedPenalty).
+ *   8. the WINNER: the largest value, then a concordant one first, then the lowest u1, then the lowest u2.  The winner's strand
+ *      slots are the chosen ones.  With one read placed and no candidate that read's best is chosen and the other read gets
+ *      none; with none placed neither gets one.
+ *   9. properPairs, pairScores, pairSecondScores, templateLengths, pairQualities and the reads' mappingQualities are pair mates'
+ *      rules 4 to 6 with "strand slot" for "slot", rule 3 above for sameness, and q_r as the given quality.
+ *  10. RESCUE WINDOWS, indexed by ROW [2R] so that awfmGpuScoreWindowsAffine takes them on the 2R-row batch unchanged: read r
+ *      gets a window when its pair is not proper and its mate m has a best (sigma_m, j), with S that slot's start:
+ *        sigma_m = 0: row V(r) gets [S + minInsert - n_r - windowPad, S + maxInsert + windowPad);
+ *        sigma_m = 1: with E = S + n_m, row F(r) gets [E - maxInsert - windowPad, E - minInsert + n_r + windowPad),
+ *      each bound signed 64-bit and then raised to 0; windowSequences is that slot's sequence.  Every other row -- all rows when
+ *      unpaired -- gets AWFM_CANDIDATES_NONE, 0, 0.
+ * Outputs (struct AwFmStrandOutputs; every pointer may be NULL, counters are added to, R == 0 touches nothing).  Per read [R]:
+ * strands (0 without a chosen slot), strandSlots (j, or AWFM_CHAINS_NO_SLOT), bestScores, secondScores, mappingQualities,
+ * baseFlags (0x10 when the chosen slot is on strand 1, else 0: what awfmGpuSamRecords takes).  Per row [2R]: rowSlots (the chosen
+ * j at the chosen row, AWFM_CHAINS_NO_SLOT at every other row: what the slot calls take on the 2R rows) and the windows.  Per
+ * pair [R / 2], written only when paired: properPairs, pairScores, pairSecondScores, templateLengths, pairQualities.  Counters:
+ * *numReverse (reads whose chosen slot is on strand 1), *numProper, *numWindows, *numMalformed.
+ * Refusals, in this order: in, out, params or a required array NULL: AwFmNullPtrError; C outside 1..16, 2R >= 2^32, another
+ * flag bit, odd R with AWFM_STRANDS_PAIRED, and -- paired -- minInsert > maxInsert or either beyond +-2^40, and mapqCap above
+ * AWFM_SCORE_MAX_MAPQ: AwFmIllegalPositionError.
+ * awfmChooseStrands: on the host over `threads` threads of the pool, the rules as written.  awfmGpuChooseStrands
+ * (csrc/awfm_strands_kernel.h): ONE launch, asynchronous on `stream`; no scratch, no allocation, no host wait, nothing of the
+ * image but its device: two streams may run it on one image at once.  Paired: 32 lanes a pair for C <= 4 (the orientation in
+ * the lane's fifth bit), a wave a pair above; unpaired: 16 lanes a read.  $AWFM_GPU_DIAG strand_group=64 forces the wave per
+ * pair or per read (tests; the result does not depend on it).
+ *
+ * awfmOrientReads / awfmGpuOrientReads: the gather that turns the 2R-row batch and strands [R] into an R-row batch.  Inputs
+ * (struct AwFmOrientInputs): `rows`, the struct AwFmVerifyInputs of the 2R rows (readChars, readOffsets [2R + 1] required; each
+ * of the six slot columns may be NULL); optionally slotScores, slotReadEnds, slotTextEnds [2R * C]; optionally qualities,
+ * numReadChars bytes parallel to readChars of which only the forward rows' are read; strands [R], required.  Outputs (struct
+ * AwFmOrientOutputs): readChars of `capacity` bytes and readOffsets [R + 1], required; qualities, the six slot columns and the
+ * three score columns [R * C], each required exactly when its input is given (one without the other: AwFmNullPtrError);
+ * *numMalformed, added to, may be NULL.
+ *   readOffsets[r] (out) = readOffsets[r] - readOffsets[0] (in) for r = 0 .. R, always written: read r's output bytes are
+ *   [readOffsets[r] - readOffsets[0], readOffsets[r + 1] - readOffsets[0]).
+ *   Read r is WELL FORMED when the offsets of F(r) and of V(r) ascend and stay within numReadChars, the two rows are equally
+ *   long, strands[r] <= 1, readOffsets[r] >= readOffsets[0] and its output bytes end within capacity.  Its characters are the
+ *   bytes of row r + strands[r] * R; its qualities the forward row's, copied when strands[r] = 0 and REVERSED (not
+ *   complemented) when 1; its slot and score columns that row's.
+ *   A MALFORMED read: no byte of characters or qualities is written; its columns are written as unused (sequences =
+ *   AWFM_CANDIDATES_NONE, slotScores = AWFM_VERIFY_NONE, everything else 0); it is counted in *numMalformed.
+ * Refusals, in this order: NULL in, out or a required array, an output without its input or the reverse: AwFmNullPtrError; C
+ * outside 1..16, 2R >= 2^32, input and output characters (numReadChars and capacity bytes) or input and output qualities
+ * overlapping as pointer ranges: AwFmIllegalPositionError.  R == 0 touches nothing.
+ * awfmOrientReads: on the host over `threads` threads.  awfmGpuOrientReads: one launch, asynchronous on `stream`, a wave per
+ * read: lanes own ALIGNED words of the output, their sources are funnelled from one or two aligned words of the input, bytes
+ * are stored singly only at a read's two edges; lanes 0 .. C - 1 copy the columns.
+ *
+ * THE LOOP, without a host wait: awfmGpuReverseComplementReads (ALL, into the second half), seeds .. slot scores on 2R rows,
+ * awfmGpuChooseStrands, awfmGpuScoreWindowsAffine on the windows it names (2R rows), slot scores and awfmGpuChooseStrands
+ * again, awfmGpuOrientReads, then awfmGpuAlignChainsAffine with strandSlots, awfmGpuAlignmentStrings and awfmGpuSamRecords with
+ * baseFlags, properPairs and mappingQualities on R rows.  Out of scope: same-strand libraries, per-orientation insert
+ * estimates (awfmGpuInsertHistogram keeps working on same-strand tables only), supplementary records. */
+#define AWFM_STRANDS_PAIRED 1u /* flags: reads 2p and 2p + 1 are mates from opposite strands; numReads must be even */
+struct AwFmStrandInputs {
+  const uint64_t *readOffsets;  /* [2 numReads + 1] */
+  const uint32_t *sequences;    /* [2 numReads * C]  the slot table's */
+  const uint32_t *slotScores;   /* [2 numReads * C]  struct AwFmSlotScoreOutputs' */
+  const uint32_t *slotReadEnds; /* [2 numReads * C] */
+  const uint64_t *slotTextEnds; /* [2 numReads * C] */
+};
+struct AwFmStrandOutputs {
+  /* per read */
+  uint8_t *strands;          /* [numReads]  0 or 1; 0 without a chosen slot */
+  uint32_t *strandSlots;     /* [numReads]  the shape of bestSlots, for the oriented batch */
+  uint32_t *bestScores;      /* [numReads] */
+  uint32_t *secondScores;    /* [numReads] */
+  uint8_t *mappingQualities; /* [numReads] */
+  uint16_t *baseFlags;       /* [numReads]  0x10 or 0: struct AwFmSamInputs' */
+  /* per row */
+  uint32_t *rowSlots;        /* [2 numReads]  the shape of bestSlots, for the 2R-row batch */
+  uint32_t *windowSequences; /* [2 numReads]  struct AwFmWindowInputs'; AWFM_CANDIDATES_NONE: no window */
+  uint64_t *windowBegins;    /* [2 numReads] */
+  uint64_t *windowEnds;      /* [2 numReads] */
+  /* per pair, written with AWFM_STRANDS_PAIRED only */
+  uint8_t *properPairs;       /* [numReads / 2] */
+  uint32_t *pairScores;       /* [numReads / 2] */
+  uint32_t *pairSecondScores; /* [numReads / 2] */
+  int64_t *templateLengths;   /* [numReads / 2]  T of a proper pair, else 0 */
+  uint8_t *pairQualities;     /* [numReads / 2] */
+  /* counters, added to */
+  uint64_t *numReverse, *numProper, *numWindows, *numMalformed;
+};
+struct AwFmOrientInputs {
+  struct AwFmVerifyInputs rows; /* the 2 numReads rows; the six slot columns may be NULL */
+  const uint32_t *slotScores;   /* [2 numReads * C]  may be NULL, like the two below */
+  const uint32_t *slotReadEnds;
+  const uint64_t *slotTextEnds;
+  const uint8_t *qualities; /* NULL, or rows.numReadChars bytes parallel to rows.readChars */
+  const uint8_t *strands;   /* [numReads] */
+};
+struct AwFmOrientOutputs {
+  uint8_t *readChars; /* capacity bytes */
+  uint64_t capacity;
+  uint64_t *readOffsets; /* [numReads + 1] */
+  uint8_t *qualities;    /* capacity bytes */
+  uint32_t *sequences;   /* the nine columns: [numReads * C] */
+  uint32_t *chainAnchors;
+  uint32_t *chainReadBegins;
+  uint32_t *chainReadEnds;
+  int64_t *chainBeginDiagonals;
+  int64_t *chainEndDiagonals;
+  uint32_t *slotScores;
+  uint32_t *slotReadEnds;
+  uint64_t *slotTextEnds;
+  uint64_t *numMalformed; /* one counter, added to */
+};
+enum AwFmReturnCode awfmChooseStrands(const struct AwFmStrandInputs *in, uint64_t numReads, uint32_t maxCandidates, uint32_t flags,
+                                      const struct AwFmPairParams *params, const struct AwFmStrandOutputs *out, unsigned threads);
+enum AwFmReturnCode awfmGpuChooseStrands(AwFmGpuIndex *g, const struct AwFmStrandInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
+                                         uint32_t flags, const struct AwFmPairParams *params, const struct AwFmStrandOutputs *dOut,
+                                         void *stream);
+enum AwFmReturnCode awfmOrientReads(const struct AwFmOrientInputs *in, uint64_t numReads, uint32_t maxCandidates,
+                                    const struct AwFmOrientOutputs *out, unsigned threads);
+enum AwFmReturnCode awfmGpuOrientReads(AwFmGpuIndex *g, const struct AwFmOrientInputs *dIn, uint64_t numReads, uint32_t maxCandidates,
+                                       const struct AwFmOrientOutputs *dOut, void *stream);
 
 /* -1 = automatic (default), 0 = never, 1 = whenever the ordered path applies */
 void awfmGpuIndexSetOrdered(AwFmGpuIndex *g, int mode);
